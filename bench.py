@@ -6,10 +6,15 @@ viscosity, periodic, second order in space and time, fp64.  One "step" = one ful
 second-order time step of the reference's time loop: calculate_timestep (CFL
 reduction) + advance_time (2 fused stages + 2 boundary updates).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N>1 is launched by torch.distributed.run, one rank per GPU; the 512^3 grid is split
 into z-slabs (strong scaling) with RCCL halo exchange.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times K steps and prints the headline (value,
+ms_per_step).  --full adds what takes work of its own: HIP-event kernel times and
+the roofline block, the CPU baselines (m1) and the strict (parity) build's rate.
+--dump-outputs DIR writes the state after the last timed step (see dump_outputs).
 """
 import argparse
 import json
@@ -25,6 +30,7 @@ import numpy as np  # noqa: E402
 from pion_amd import abi, driver, lib, problems, slab  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_BYTES = 48 << 20  # --dump-outputs: size of the sampled state and its cell indices (all files stay under 64 MB)
 
 
 def kernel_source_hash():
@@ -287,6 +293,107 @@ def check_exchange(sim, cfg, rank, world, periodic_z, dist):
         2 * world if periodic_z else 2 * (world - 1))
 
 
+def dump_outputs(out_dir, sim, cfg, cfg_g, rank, world, last_dt, dist):
+    """--dump-outputs DIR (untimed, right after the last timed step): what the time loop leaves its caller -- the
+    primitive state and the step's dt -- as float64 .npy files written by rank 0:
+      state_sample.npy        [nvar][K]  the state at K cells of the whole grid, a fixed seeded sample (the 512^3
+                                         state is 9.7 GB); K = min(cells, DUMP_BYTES / (8 (nvar + 1)))
+      state_sample_cells.npy  [K]        those cells' indices into the global grid (x fastest), ascending
+      state_sum.npy, state_min.npy, state_max.npy   [nvar]  over every cell of the grid, ghost cells excluded
+      dt.npy                  [1]        the time step the last timed step advanced by
+    The same arguments give the same inputs, so two builds can be compared file by file."""
+    A = sim.download(0)
+    lo = [int(cfg.nbc) if a < cfg.ndim else 0 for a in range(3)]
+    ng = [int(v) for v in cfg.ng[:3]]
+    own = A[:, lo[2]:lo[2] + ng[2], lo[1]:lo[1] + ng[1], lo[0]:lo[0] + ng[0]]
+    nx, ny, nz = (int(v) for v in cfg_g.ng[:3])
+    ncell = nx * ny * nz
+    k = min(ncell, DUMP_BYTES // (8 * (cfg.nvar + 1)))
+    cells = np.sort(np.random.default_rng(0).choice(ncell, size=k, replace=False))
+    iz, iy, ix = np.unravel_index(cells, (nz, ny, nx))
+    z0 = rank * ng[2]   # z-slab of this rank (slab.slab_config)
+    mine = (iz >= z0) & (iz < z0 + ng[2])
+    part = (own[:, iz[mine] - z0, iy[mine], ix[mine]], np.array([[v.sum(), v.min(), v.max()] for v in own]))
+    del A, own
+    every = [part]
+    if world > 1:
+        every = [None] * world
+        dist.all_gather_object(every, part)
+    if rank != 0:
+        return
+    # cells are sorted and z is the slowest index: the ranks' pieces follow each other in rank order
+    sample = np.concatenate([p[0] for p in every], axis=1)
+    red = np.stack([p[1] for p in every])
+    assert sample.shape == (cfg.nvar, k)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("state_sample", sample), ("state_sample_cells", cells), ("state_sum", red[:, :, 0].sum(axis=0)),
+                    ("state_min", red[:, :, 1].min(axis=0)), ("state_max", red[:, :, 2].max(axis=0)),
+                    ("dt", [last_dt])):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def roofline(args, cfg, eq, world, loopback, value, tm, ev_steps):
+    """--full: the roofline block of the JSON line -- the stage kernels' HIP-event times against the HBM peak, with
+    the committed PMC traffic / issue measurements quoted while the kernel sources still match them"""
+    n = args.n
+    nvar = cfg.nvar
+    # algorithmic bytes of one stage launch on this rank (DESIGN.md): a step moves 5*nvar*8 B per
+    # cell in two launches (stage 1: read P, write Ph; stage 2: read P and Ph, write P)
+    cells_rank = cfg.ng[0] * cfg.ng[1] * cfg.ng[2]
+    alg_bytes = 2.5 * nvar * 8 * cells_rank
+    # (N > 1 splits a stage into interior + 2 z-boundary launches: sum them per stage)
+    stage_ms = tm["stage_ms"] * tm["stage_n"] / (2.0 * ev_steps) if ev_steps else 0.0
+    achieved = alg_bytes / (stage_ms * 1e-3) / 1e9 if stage_ms > 0 else 0.0
+    # Bytes per stage launch that left L2, from the PMC passes of this same command (rocprofv3 --pmc
+    # FETCH_SIZE / WRITE_SIZE in separate runs, gfx950 read correction calibrated on 8 B/lane accesses):
+    # profiles/r03_pmc_traffic.json, written by profiles/tools/summarize_r03.py.  Counters cannot be read
+    # from inside this process, so the committed measurement is quoted -- only for the workload it was
+    # taken on (512^3, GLM, fast mode, 1 GPU) and only while the kernel sources still hash to what it was
+    # taken on; otherwise null.
+    traffic = None
+    valu = None
+    pdir = os.path.join(ROOT, "profiles")
+    tfile, sfile = os.path.join(pdir, "r03_pmc_traffic.json"), os.path.join(pdir, "r03_pmc_sq.json")
+    if (world == 1 and not loopback and n == 512 and not args.nz and eq == abi.EQGLM and not args.strict
+            and args.workload == "m1"):
+        src = kernel_source_hash()
+        if os.path.exists(tfile):
+            with open(tfile) as f:
+                t = json.load(f)
+            if t.get("kernel_source_hash") == src:
+                traffic = t.get("traffic_bytes_per_launch")
+        # where the time goes (the kernel is fp64-VALU bound, not HBM bound): instructions per launch,
+        # share of wave cycles issuing VALU / parked on s_waitcnt, from the committed SQ counter pass
+        if os.path.exists(sfile):
+            with open(sfile) as f:
+                t = json.load(f)
+            if t.get("kernel_source_hash") == src:
+                c = t["counters"]
+                valu = {"valu_insts_per_launch": c["SQ_INSTS_VALU"],
+                        "valu_active_frac_of_wave_cycles": c["SQ_ACTIVE_INST_VALU"] / c["SQ_WAVE_CYCLES"],
+                        "waitcnt_frac_of_wave_cycles": c["SQ_WAIT_ANY"] / c["SQ_WAVE_CYCLES"],
+                        "waves_per_simd": 2, "source": "profiles/r03_pmc_sq.json"}
+                # the roofline that actually binds: every wave-level VALU instruction of this fp64 kernel holds
+                # its SIMD's vector pipe for 4 cycles (16 fp64 lanes per clock per SIMD, 78.6 TFLOP/s spec);
+                # fraction of that issue capacity the launch used, at the nominal 2.4 GHz
+                if stage_ms > 0:
+                    valu["fp64_issue_frac_at_2.4GHz"] = c["SQ_INSTS_VALU"] * 4.0 / (1024 * 2.4e9 * stage_ms * 1e-3)
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_copy_ceiling_6290GBs": achieved / 6290.0,
+            "step_frac": value * 1e6 * 5 * nvar * 8 / (HBM_PEAK_GBS * 1e9 * world),
+            "step_frac_what": "SURVEY 8(d): whole-step rate x 5 nvar 8 B per cell-update / (peak x GPUs): "
+                              "prepass, boundary and reduction launches included",
+            "traffic": traffic, "traffic_unit": "bytes per launch that left L2 (PMC FETCH_SIZE + WRITE_SIZE, calibrated; profiles/r03_pmc_traffic.json; null when the kernel sources have changed since)",
+            "kernel": {"m1": "k_stage_rows2<GLM,0,HLLD>" if eq == abi.EQGLM else "k_stage_rows2<MHD,0,HLLD>",
+                       "m2": "k_stage_rows2<EUL,0,Roe-CV>", "m3": "k_stage_rows2<EUL,1,FVS>",
+                       "dmr2d": "2-D stage kernel <EUL,0,Roe-CV>", "mhd2d": "2-D stage kernel <GLM,0,HLLD>",
+                       "axi2d": "2-D cylindrical stage kernel <EUL,0,Roe-CV,CYL>",
+                       "mhdaxi2d": "2-D cylindrical stage kernel <GLM,0,HLLD,CYL>"}[args.workload]
+                      + " (first-order + second-order instance, mean per launch)",
+            "kernel_ms": stage_ms, "kernel_ms_from": "HIP events over %d steps after the timed region" % ev_steps, "launches_per_stage": (tm["stage_n"] / (2.0 * ev_steps) if ev_steps else 0.0), "prepass_ms": tm["prepass_ms"], "bc_ms": tm["bc_ms"],
+            "dt_ms": tm["dt_ms"], "algorithmic_bytes_per_launch": alg_bytes, "issue": valu}
+
+
 def main():
     if len(sys.argv) >= 3 and sys.argv[1] == "--cpu-worker":
         return cpu_worker(sys.argv[2])
@@ -297,10 +404,16 @@ def main():
     ap.add_argument("--n", "--grid", dest="n", type=int, default=512, help="cells per axis (headline: 512); use --grid under torch.distributed.run, whose own parser finds --n ambiguous")
     ap.add_argument("--eqn", default="glm", choices=["glm", "mhd"])
     ap.add_argument("--strict", type=int, default=0, help="1 = bit-parity kernels (no FMA contraction)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: HIP-event kernel times over a few extra steps and the roofline block, "
+                         "the CPU baselines (m1, one GPU) and the strict-build throughput run (one GPU, not --strict)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the state after the last timed step under DIR as .npy (float64, see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-kernel-timing", action="store_true",
-                    help="do not bracket the launches with HIP events (A/B of the event overhead; roofline fields are 0)")
-    ap.add_argument("--no-parity-build", action="store_true", help="skip the strict-build throughput run")
+                    help="--full: do not bracket the launches with HIP events (A/B of the event overhead; roofline "
+                         "fields are 0)")
+    ap.add_argument("--no-parity-build", action="store_true", help="--full: skip the strict-build throughput run")
     ap.add_argument("--no-exchange-check", action="store_true",
                     help="N > 1: skip the untimed end-of-run check that every rank's z ghosts equal its neighbours' planes")
     ap.add_argument("--cpu-n", type=int, default=256,
@@ -523,7 +636,7 @@ def main():
 
         def step():
             sc.calculate_timestep()
-            sc.advance_time()
+            return sc.advance_time()
     del P
 
     def barrier():
@@ -539,15 +652,17 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last_dt = step()
     barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sim, cfg, cfg_g, rank, world, last_dt, dist if world > 1 else None)
     # kernel durations for the roofline: HIP events around every launch, on the stream it is launched on, over
     # a few MORE steps after the timed region (event records between dependent kernels on two streams cost
     # ~0.5 ms per step in the slab path, so they stay out of `value`)
     ev_steps = 0
     tm = {"stage_ms": 0.0, "stage_n": 0, "prepass_ms": 0.0, "bc_ms": 0.0, "dt_ms": 0.0}
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         ev_steps = max(1, min(3, args.steps))
         sim.enable_timing(True)
         for _ in range(ev_steps):
@@ -566,47 +681,6 @@ def main():
         ncell = cfg_g.ng[0] * cfg_g.ng[1] * cfg_g.ng[2]
         value = ncell * args.steps / el / 1e6
         nvar = cfg.nvar
-        # algorithmic bytes of one stage launch on this rank: a step moves 5*nvar*8 B per
-        # cell in two launches (stage 1: read P, write Ph; stage 2: read P and Ph, write P)
-        cells_rank = cfg.ng[0] * cfg.ng[1] * cfg.ng[2]
-        alg_bytes = 2.5 * nvar * 8 * cells_rank
-        # (N > 1 splits a stage into interior + 2 z-boundary launches: sum them per stage)
-        stage_ms = tm["stage_ms"] * tm["stage_n"] / (2.0 * ev_steps) if ev_steps else 0.0
-        achieved = alg_bytes / (stage_ms * 1e-3) / 1e9 if stage_ms > 0 else 0.0
-        # Bytes per stage launch that left L2, from the PMC passes of this same command (rocprofv3 --pmc
-        # FETCH_SIZE / WRITE_SIZE in separate runs, gfx950 read correction calibrated on 8 B/lane accesses):
-        # profiles/r03_pmc_traffic.json, written by profiles/tools/summarize_r03.py.  Counters cannot be read
-        # from inside this process, so the committed measurement is quoted -- only for the workload it was
-        # taken on (512^3, GLM, fast mode, 1 GPU) and only while the kernel sources still hash to what it was
-        # taken on; otherwise null.
-        traffic = None
-        valu = None
-        pdir = os.path.join(ROOT, "profiles")
-        tfile, sfile = os.path.join(pdir, "r03_pmc_traffic.json"), os.path.join(pdir, "r03_pmc_sq.json")
-        if (world == 1 and not loopback and n == 512 and not args.nz and eq == abi.EQGLM and not args.strict
-                and args.workload == "m1"):
-            src = kernel_source_hash()
-            if os.path.exists(tfile):
-                with open(tfile) as f:
-                    t = json.load(f)
-                if t.get("kernel_source_hash") == src:
-                    traffic = t.get("traffic_bytes_per_launch")
-            # where the time goes (the kernel is fp64-VALU bound, not HBM bound): instructions per launch,
-            # share of wave cycles issuing VALU / parked on s_waitcnt, from the committed SQ counter pass
-            if os.path.exists(sfile):
-                with open(sfile) as f:
-                    t = json.load(f)
-                if t.get("kernel_source_hash") == src:
-                    c = t["counters"]
-                    valu = {"valu_insts_per_launch": c["SQ_INSTS_VALU"],
-                            "valu_active_frac_of_wave_cycles": c["SQ_ACTIVE_INST_VALU"] / c["SQ_WAVE_CYCLES"],
-                            "waitcnt_frac_of_wave_cycles": c["SQ_WAIT_ANY"] / c["SQ_WAVE_CYCLES"],
-                            "waves_per_simd": 2, "source": "profiles/r03_pmc_sq.json"}
-                    # the roofline that actually binds: every wave-level VALU instruction of this fp64 kernel holds
-                    # its SIMD's vector pipe for 4 cycles (16 fp64 lanes per clock per SIMD, 78.6 TFLOP/s spec);
-                    # fraction of that issue capacity the launch used, at the nominal 2.4 GHz
-                    if stage_ms > 0:
-                        valu["fp64_issue_frac_at_2.4GHz"] = c["SQ_INSTS_VALU"] * 4.0 / (1024 * 2.4e9 * stage_ms * 1e-3)
         out = {
             "metric": baseline_metric(),
             "value": value, "unit": "Mcell-updates/s", "n_gpus": world, "steps": args.steps,
@@ -622,24 +696,12 @@ def main():
                           "and `--transport torch` are the verified fall-backs" if (world > 1 and not transport_note and hs is not None) else ""),
                        "fp_mode": "strict (no FMA)" if args.strict else "fast (FMA contraction)",
                        "exchange_check": exchange_check},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_copy_ceiling_6290GBs": achieved / 6290.0,
-                         "step_frac": value * 1e6 * 5 * nvar * 8 / (HBM_PEAK_GBS * 1e9 * world),
-                         "step_frac_what": "SURVEY 8(d): whole-step rate x 5 nvar 8 B per cell-update / (peak x GPUs): "
-                                           "prepass, boundary and reduction launches included",
-                         "traffic": traffic, "traffic_unit": "bytes per launch that left L2 (PMC FETCH_SIZE + WRITE_SIZE, calibrated; profiles/r03_pmc_traffic.json; null when the kernel sources have changed since)",
-                         "kernel": {"m1": "k_stage_rows2<GLM,0,HLLD>" if eq == abi.EQGLM else "k_stage_rows2<MHD,0,HLLD>",
-                                    "m2": "k_stage_rows2<EUL,0,Roe-CV>", "m3": "k_stage_rows2<EUL,1,FVS>",
-                                    "dmr2d": "2-D stage kernel <EUL,0,Roe-CV>", "mhd2d": "2-D stage kernel <GLM,0,HLLD>",
-                                    "axi2d": "2-D cylindrical stage kernel <EUL,0,Roe-CV,CYL>",
-                                    "mhdaxi2d": "2-D cylindrical stage kernel <GLM,0,HLLD,CYL>"}[args.workload]
-                                   + " (first-order + second-order instance, mean per launch)",
-                         "kernel_ms": stage_ms, "kernel_ms_from": "HIP events over %d steps after the timed region" % ev_steps, "launches_per_stage": (tm["stage_n"] / (2.0 * ev_steps) if ev_steps else 0.0), "prepass_ms": tm["prepass_ms"], "bc_ms": tm["bc_ms"],
-                         "dt_ms": tm["dt_ms"], "algorithmic_bytes_per_launch": alg_bytes, "issue": valu},
         }
-        if world == 1 and not args.no_cpu_baseline and args.workload == "m1":
+        if args.full:
+            out["roofline"] = roofline(args, cfg, eq, world, loopback, value, tm, ev_steps)
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "m1":
             out["cpu_baseline"] = cpu_baseline(args.cpu_n, args.eqn)
-        if world == 1 and not loopback and not args.strict and not args.no_parity_build:
+        if args.full and world == 1 and not loopback and not args.strict and not args.no_parity_build:
             # the same workload through the PARITY build (strict_fp=1: -ffp-contract=off, the reference's
             # operation order, bit-identical to the oracle): its throughput beside the headline
             sim.close()

@@ -8,7 +8,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity-build"
+BENCH="python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity-build"
 run() { echo "== $1"; shift; "$@" || { echo "FAILED: $*"; exit 1; }; }
 run m1 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_r02_m1 -- $BENCH > $OUT/prof_r02_m1.log 2>&1
 run m2 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_r02_m2 -- $BENCH --workload m2 > $OUT/prof_r02_m2.log 2>&1

@@ -11,7 +11,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity-build"
+B="python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity-build"
 prof() { local tag=$1; shift; echo "== stats $tag"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_r03_$tag -- $B "$@" > $OUT/prof_r03_$tag.log 2>&1 || { echo "FAILED stats $tag"; tail -3 $OUT/prof_r03_$tag.log; }; }
 pmc() { local tag=$1; local ctrs=$2; shift; shift; echo "== pmc $tag"; rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $OUT/pmc_r03_$tag -- $B "$@" > $OUT/pmc_r03_$tag.log 2>&1 || { echo "FAILED pmc $tag"; tail -3 $OUT/pmc_r03_$tag.log; }; }
 SQ="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_SALU SQ_BUSY_CYCLES SQ_INSTS_VMEM_RD"
