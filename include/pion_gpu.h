@@ -164,6 +164,44 @@ int pion_gpu_synchronize(void *handle);
  * isbd=true,isdomain=false (stellar_wind_BC.cpp:277-278). */
 int pion_gpu_set_wind_cells(void *handle, long n, const long *idx, const double *states);
 
+/* Stellar-wind sources the device builds and updates itself (grid/stellar_wind_BC.cpp, stellar_wind and
+ * stellar_wind_evolution; boundaries/stellar_wind_boundaries.cpp).  WINDTYPE_CONSTANT (type 0) and
+ * WINDTYPE_EVOLVING (type 1) of grid/stellar_wind_BC.h:41-42, every geometry of pion_gpu_config:
+ * 1-D spherical (source at r = 0), 2-D cylindrical (z,R) (source on the axis), 2-D Cartesian (slab symmetry),
+ * 3-D Cartesian.  Euler, ideal MHD and GLM (not MHD in 1-D). */
+#define PION_MAX_WIND_SOURCES 8
+typedef struct pion_gpu_wind_source {
+  double pos[PION_MAX_DIM];   /* source position, physical units (unused axes ignored) */
+  double radius;              /* radius of the wind region, physical units (> 0) */
+  int type;                   /* 0 = constant, 1 = evolving (2, 3: angle / latitude-dependent: EINVAL) */
+  double mdot;                /* Msun/yr   (constant: converted to g/s as add_source does, stellar_wind_BC.cpp:166-172) */
+  double vinf, vrot;          /* km/s      (constant) */
+  double Tw, Rstar, Bstar;    /* K, cm, G  (constant; Bstar also for evolving sources) */
+  double tracers[PION_MAX_NVAR];  /* wind tracer values (the first ntracer are used) */
+  /* evolving sources (add_evolving_source, stellar_wind_BC.cpp:1109-1245): a table of npt >= 2 rows, cgs, the
+   * times already offset and scaled ((t + time_offset)/t_scalefactor, see pion_host_read_wind_evolution).
+   * The arrays are copied by pion_gpu_add_wind_source. */
+  int npt;
+  const double *evo_time, *evo_Teff, *evo_Mdot, *evo_vrot, *evo_vinf, *evo_R;
+  const double *evo_X[7];     /* element columns X_H, X_He, X_C, X_N, X_O, X_Z, X_D (NULL: not selected) */
+  int evo_tracer_elem[PION_MAX_NVAR];  /* per tracer: -1 = the constant value above, 0..6 = the evo_X column
+                                        * (set_element_indices, :992-1024; the caller maps the tracer names) */
+  double t_now;               /* simulation time when the source is set up (add_evolving_source's t_now) */
+  double update_freq;         /* SWP update_freq / t_scalefactor (only decides activity at set-up) */
+} pion_gpu_wind_source;
+
+/* stellar_wind::add_source / stellar_wind_evolution::add_evolving_source + BC_assign_STWIND_add_cells2src: every
+ * cell (ghosts included) with distance_vertex2cell <= radius joins the source, in cell-id order; the cells are
+ * marked isbd = true, isdomain = false.  Call after create, any number of times; sources are applied in id order
+ * (*id = 0, 1, ...).  EINVAL where the reference calls rep.error: a source off the axis (cylindrical) or off r = 0
+ * (spherical), MHD in 1-D, type 2 or 3, radius <= 0, an evolving table with npt < 2, more than
+ * PION_MAX_WIND_SOURCES sources. */
+int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int *id);
+/* The cells of source `id` in cell-id order and the states (n*nvar doubles, cell-major) the last boundary update
+ * wrote (zeros before the first one, or while an evolving source is inactive).  *n = number of cells; idx ==
+ * NULL: size query only; states may be NULL. */
+int pion_gpu_get_wind_cells(void *handle, int id, long *n, long *idx, double *states);
+
 /* jet_bc::BC_assign_JETBC / BC_update_JETBC (boundaries/jet_boundaries.cpp:36-208, 3-D Cartesian
  * branch :170-201, update :212-262) with JetParams (sim_params.h:331-341): every XN ghost cell of an
  * on-grid (y,z) column whose centre lies within jetradius*dx of the x axis holds `jetstate`
@@ -184,7 +222,8 @@ int pion_gpu_set_cooling_tables(void *handle, int nT, const double *T,
 
 /* assign_update_bcs::TimeUpdateInternalBCs + TimeUpdateExternalBCs
  * (boundaries/assign_update_bcs.cpp:134-252): fills ghost cells of Ph, and of
- * P too when cstep==maxstep.  `assign`!=0 additionally captures the constant
+ * P too when cstep==maxstep.  Internal boundaries first: the set_wind_cells list, then the wind sources of
+ * pion_gpu_add_wind_source at `simtime` (written to P and Ph), then the external faces.  `assign`!=0 additionally captures the constant
  * inflow/fixed reference states from P (BC_assign_*, inflow_boundaries.cpp,
  * fixed_boundaries.cpp) and must be used for the first call after upload. */
 int pion_gpu_update_bcs(void *handle, double simtime, int cstep, int maxstep, int assign);

@@ -36,6 +36,11 @@ int pion_host_sim_time_int(void *sim, int nsteps, double *simtime, double *last_
 int pion_host_sim_download(void *sim, int which, double *P);
 int pion_host_sim_finish_halo(void *sim);
 int pion_host_sim_set_comm(void *sim, void *comm);            /* before pion_host_sim_init */
+/* stellar_wind_bc::BC_assign_STWIND for one source (pion_gpu_add_wind_source on the loop's handle), before
+ * pion_host_sim_init; also the first-step limit 0.1 CFL dx / (vinf 1e5) of calc_timestep.cpp:318-322 (src->vinf in
+ * km/s, 0 = no limit), combined by min with init's first_step_dt_limit.  EINVAL on a backend other than
+ * libpion_gpu.so. */
+int pion_host_sim_add_wind_source(void *sim, const pion_gpu_wind_source *src, int *id);
 int pion_host_sim_last_error(void *sim, char *buf, int len);
 
 /* ---- z-slab communicators (both return a pion_host::slab_comm*) */
@@ -56,6 +61,24 @@ int pion_host_build_cooling_tables(double min_temp, double max_temp, int nT, dou
 double pion_host_cooling_rate_wss09(double T);
 double pion_host_hii_rrr(double T);
 double pion_host_hii_total_cooling(double T);
+
+/* ---- stellar_wind_evolution::read_evolution_file (grid/stellar_wind_BC.cpp:1026-1100): two header lines, then rows
+ * of 8 or 15 columns (time M L Teff Mdot vrot vcrit vinf [X_H X_He X_C X_N X_O X_Z X_D], cgs); a column a row lacks
+ * keeps the previous row's value (0 at first), as sscanf leaves it untouched; lines without any number are skipped.
+ * Writes table[col * cap + row] for the PION_WND_* columns, with time = (t + time_offset) / t_scalefac and
+ * R = sqrt(L / (4 pi sigma Teff^4)); table == NULL: count only.  Returns the number of rows, or < 0. */
+#define PION_WND_TIME 0
+#define PION_WND_M 1
+#define PION_WND_L 2
+#define PION_WND_TEFF 3
+#define PION_WND_MDOT 4
+#define PION_WND_VROT 5
+#define PION_WND_VCRIT 6
+#define PION_WND_VINF 7
+#define PION_WND_X 8      /* 8..14: X_H X_He X_C X_N X_O X_Z X_D */
+#define PION_WND_R 15
+#define PION_WND_NCOL 16
+long pion_host_read_wind_evolution(const char *path, double time_offset, double t_scalefac, long cap, double *table);
 
 /* the product's only backend table: libpion_gpu.so */
 const struct pion_backend *pion_backend_gpu(void);

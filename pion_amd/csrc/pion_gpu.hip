@@ -13,7 +13,10 @@
 #include <string>
 #include <vector>
 
+#include <hipcub/hipcub.hpp>
+
 #include "../../include/pion_gpu.h"
+#include "dev_wind.h"
 #include "kernels.h"
 
 using namespace pion;
@@ -417,6 +420,21 @@ __global__ void k_halo(double *A, double *buf, const GridDesc g, const int nvar,
   else A[v * g.ncell + c] = buf[t];
 }
 
+// one pion_gpu_add_wind_source source: its table, the parameters the next boundary update writes with, and the
+// activity bookkeeping of stellar_wind_evolution (evolving_wind_data: tstart, tfinish, t_next_update, is_active)
+struct WindSource {
+  int type = 0;
+  double pos[3] = {0.0, 0.0, 0.0};
+  double radius = 0.0, Bstar = 0.0;
+  std::vector<double> t, Teff, Mdot, vrot, vinf, R, X[7];
+  int elem[PION_MAX_NVAR];
+  double Mdot_c = 0.0, Vinf_c = 0.0, vrot_c = 0.0, Tw_c = 0.0, Rstar_c = 0.0;   // wind_source members, cgs
+  double tr[PION_MAX_NVAR];
+  bool active = true;
+  double tstart = 0.0, tfinish = 0.0, t_next_update = 1.0e99;
+  long off = 0, n = 0;   // range in the concatenated cell list
+};
+
 struct Handle {
   pion_gpu_config cfg;
   GridDesc g;
@@ -451,6 +469,11 @@ struct Handle {
   double *djet_state = nullptr;
   long *dwind_idx = nullptr;
   double *dwind_state = nullptr;
+  // wind sources (pion_gpu_add_wind_source): cells of all sources concatenated in id order, each in cell-id order
+  std::vector<WindSource> wsrc;
+  long nws = 0;              // cells of all sources
+  long *dws_idx = nullptr;
+  double *dws_dist = nullptr, *dws_off = nullptr, *dws_state = nullptr;   // off: [3][nws]; state: [nws][nvar]
   // cooling
   CoolDev cool;
   double *dcoolT = nullptr, *dcooltab = nullptr, *dcoolslope = nullptr;
@@ -567,6 +590,94 @@ int check_errword(Handle *h)
 static inline bool mp_dt_limited(const pion_gpu_config &cfg)
 {
   return cfg.cooling != 0 && cfg.mp_timestep_limit >= 1 && cfg.mp_timestep_limit <= 3;
+}
+
+// legacy wind list or wind sources present: the stage kernels read the cell flags, and the periodic ghost images
+// are not fused into one launch
+static inline bool any_wind(const Handle *h) { return h->nwind > 0 || h->nws > 0; }
+
+// constants::equalD (constants.cpp:48-68)
+static bool equalD(const double a, const double b)
+{
+  if (a == b) return true;
+  if (fabs(a) + fabs(b) < 1.0e-100) return true;
+  return (fabs(a - b) / (fabs(a) + fabs(b) + 1.0e-100)) < 1.0e-12;
+}
+
+// interpolate_arrays::root_find_linear_vec (tools/interpolate.cpp:121-161), as written: bisection, then linear
+// interpolation with the requested x clamped to the bracketing nodes (zero slope outside the table)
+static double root_find_linear_vec(const std::vector<double> &xarr, const std::vector<double> &yarr, const double xreq)
+{
+  const size_t len = xarr.size();
+  size_t ihi = len - 1, ilo = 0, imid = 0;
+  do {
+    imid = ilo + (size_t)floor((ihi - ilo) / 2.0);
+    if (xarr[imid] < xreq) ilo = imid;
+    else ihi = imid;
+  } while (ihi - ilo > 1);
+  double xval = 0.0;
+  if (xreq > xarr[ihi]) xval = xarr[ihi];
+  else if (xreq < xarr[ilo]) xval = xarr[ilo];
+  else xval = xreq;
+  return yarr[ilo] + (yarr[ihi] - yarr[ilo]) * (xval - xarr[ilo]) / (xarr[ihi] - xarr[ilo]);
+}
+
+// stellar_wind_evolution::set_cell_values (stellar_wind_BC.cpp:1334-1372) and update_source (:1250-1330) for every
+// source, then one launch per active source, in id order, that writes the reference states of its cells (no host
+// synchronisation: the parameters are scalars of the host, the launch carries them)
+int wind_sources_update(Handle *h, const double simtime)
+{
+  WindStateArgs a;
+  memset(&a, 0, sizeof a);
+  for (size_t s = 0; s < h->wsrc.size(); s++) {
+    WindSource &W = h->wsrc[s];
+    if (W.type == 1 && simtime >= W.t_next_update) {
+      // update_source: every step from tstart on (:1266), values clamped after tfinish
+      W.active = true;
+      W.t_next_update = std::min(simtime, W.tfinish);
+      W.Tw_c = root_find_linear_vec(W.t, W.Teff, simtime);
+      W.Mdot_c = root_find_linear_vec(W.t, W.Mdot, simtime);
+      W.vrot_c = root_find_linear_vec(W.t, W.vrot, simtime);
+      W.Vinf_c = root_find_linear_vec(W.t, W.vinf, simtime);
+      W.Rstar_c = root_find_linear_vec(W.t, W.R, simtime);
+      for (int v = 0; v < h->cfg.ntracer; v++)
+        if (W.elem[v] >= 0) W.tr[v] = root_find_linear_vec(W.t, W.X[W.elem[v]], simtime);
+    }
+    WindSrcDev &d = a.s[s];
+    d.Mdot = W.Mdot_c;
+    d.Vinf = W.Vinf_c;
+    d.v_rot = W.vrot_c;
+    d.Tw = W.Tw_c;
+    d.Rstar = W.Rstar_c;
+    d.Bstar = W.Bstar;
+    d.radius = W.radius;
+    for (int v = 0; v < PION_MAX_NTR; v++) d.tr[v] = (v < h->cfg.ntracer) ? W.tr[v] : 0.0;
+    d.off = W.off;
+    d.n = W.n;
+    d.active = W.active ? 1 : 0;
+  }
+  a.P = h->dP;
+  a.Ph = h->dPh;
+  a.states = h->dws_state;
+  a.idx = h->dws_idx;
+  a.dist = h->dws_dist;
+  a.off = h->dws_off;
+  a.ntot = h->nws;
+  a.ncell = h->g.ncell;
+  a.nsrc = (int)h->wsrc.size();
+  a.nvar = h->cfg.nvar;
+  a.ntracer = h->cfg.ntracer;
+  a.ndim = h->cfg.ndim;
+  a.cart2d = (h->cfg.ndim == 2 && h->cfg.coord_sys == 1) ? 1 : 0;
+  a.eqntype = h->cfg.eqntype;
+  a.cooling = (h->cfg.cooling != 0) ? 1 : 0;
+  a.Tmin = h->cfg.min_temp;   // EP.MinTemperature, as handed to the stellar_wind constructor
+  a.Mu_tot_over_kB = h->Mu_tot_over_kB;
+  // stellar_wind_evolution::set_cell_values: an inactive source keeps its cells flagged but does not write them
+  for (int s = 0; s < a.nsrc; s++)
+    if (a.s[s].active && a.s[s].n > 0)
+      hipLaunchKernelGGL(k_wind_state, dim3((unsigned)((a.s[s].n + 255) / 256)), dim3(256), 0, h->stream, a, s);
+  return 0;
 }
 
 // device scratch of the test seams: freed on every return path
@@ -819,6 +930,10 @@ void pion_gpu_destroy(void *handle)
   hipFree(h->ddt_init);
   hipFree(h->dwind_idx);
   hipFree(h->dwind_state);
+  hipFree(h->dws_idx);
+  hipFree(h->dws_dist);
+  hipFree(h->dws_off);
+  hipFree(h->dws_state);
   hipFree(h->djet_idx);
   hipFree(h->djet_state);
   hipFree(h->dcoolT);
@@ -935,6 +1050,185 @@ int pion_gpu_set_wind_cells(void *handle, long n, const long *idx, const double 
     }
     HCHECK(h, hipMemcpy(h->dflags, h->hflags.data(), h->g.ncell, hipMemcpyHostToDevice));
   }
+  return 0;
+}
+
+int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int *id)
+{
+  Handle *h = use(handle);
+  if (!h || !src) return PION_GPU_EINVAL;
+  const pion_gpu_config &cfg = h->cfg;
+  const GridDesc &g = h->g;
+  auto fail = [&](const char *m) {
+    h->err = m;
+    return PION_GPU_EINVAL;
+  };
+  // the reference's rep.error conditions (stellar_wind_BC.cpp:140-217, :331-360, :1140-1145, :517-519)
+  if (h->wsrc.size() >= PION_MAX_WIND_SOURCES) return fail("wind source: at most PION_MAX_WIND_SOURCES sources");
+  if (src->type == 2 || src->type == 3) return fail("wind source: angle / latitude-dependent winds are not supported");
+  if (src->type != 0 && src->type != 1) return fail("What type of source is this?  add a new type?");
+  if (!(src->radius > 0.0)) return fail("wind source: radius must be > 0");
+  if (cfg.coord_sys == 3 && !equalD(src->pos[0], 0.0)) return fail("Spherical symmetry but source not at origin!");
+  if (cfg.coord_sys == 2 && cfg.ndim == 2 && !equalD(src->pos[1], 0.0))
+    return fail("Axisymmetry but source not at R=0!");
+  if (cfg.ndim == 1 && cfg.eqntype != PION_EQEUL) return fail("1D spherical but MHD?");
+  if (src->type == 1) {
+    if (src->npt < 2) return fail("evolving wind source: the table needs at least 2 rows");
+    if (!src->evo_time || !src->evo_Teff || !src->evo_Mdot || !src->evo_vrot || !src->evo_vinf || !src->evo_R)
+      return fail("evolving wind source: missing table column");
+    for (int v = 0; v < cfg.ntracer; v++) {
+      const int e = src->evo_tracer_elem[v];
+      if (e < -1 || e > 6 || (e >= 0 && !src->evo_X[e])) return fail("evolving wind source: bad tracer selector");
+    }
+  }
+  WindSource W;
+  W.type = src->type;
+  for (int a = 0; a < 3; a++) W.pos[a] = (a < cfg.ndim) ? src->pos[a] : 0.0;
+  W.radius = src->radius;
+  W.Bstar = src->Bstar;
+  for (int v = 0; v < PION_MAX_NVAR; v++) {
+    W.tr[v] = (v < cfg.ntracer) ? src->tracers[v] : 0.0;
+    W.elem[v] = (src->type == 1 && v < cfg.ntracer) ? src->evo_tracer_elem[v] : -1;
+  }
+  double mdot = src->mdot, vinf = src->vinf, vrot = src->vrot, Tw = src->Tw, Rstar = src->Rstar;
+  if (src->type == 1) {
+    // add_evolving_source (:1109-1245): the source is active at set-up if it starts within one update interval
+    const int n = src->npt;
+    W.t.assign(src->evo_time, src->evo_time + n);
+    W.Teff.assign(src->evo_Teff, src->evo_Teff + n);
+    W.Mdot.assign(src->evo_Mdot, src->evo_Mdot + n);
+    W.vrot.assign(src->evo_vrot, src->evo_vrot + n);
+    W.vinf.assign(src->evo_vinf, src->evo_vinf + n);
+    W.R.assign(src->evo_R, src->evo_R + n);
+    for (int e = 0; e < 7; e++)
+      if (src->evo_X[e]) W.X[e].assign(src->evo_X[e], src->evo_X[e] + n);
+    W.tstart = W.t[0];
+    W.tfinish = W.t[n - 1];
+    const double t_now = src->t_now;
+    W.t_next_update = std::max(W.tstart, t_now);
+    double x[7] = {0, 0, 0, 0, 0, 0, 0};
+    if (((t_now + src->update_freq) > W.tstart || equalD(W.tstart, t_now)) && t_now < W.tfinish) {
+      W.active = true;
+      Tw = root_find_linear_vec(W.t, W.Teff, t_now);
+      mdot = root_find_linear_vec(W.t, W.Mdot, t_now);
+      vinf = root_find_linear_vec(W.t, W.vinf, t_now);
+      vrot = root_find_linear_vec(W.t, W.vrot, t_now);
+      Rstar = root_find_linear_vec(W.t, W.R, t_now);
+      for (int e = 0; e < 7; e++)
+        if (!W.X[e].empty()) x[e] = root_find_linear_vec(W.t, W.X[e], t_now);
+    }
+    else {
+      W.active = false;
+      mdot = -100.0;
+      vinf = -100.0;
+      Tw = -100.0;
+      vrot = 0.0;
+      Rstar = 0.0;
+    }
+    for (int v = 0; v < cfg.ntracer; v++)
+      if (W.elem[v] >= 0) W.tr[v] = x[W.elem[v]];
+  }
+  // stellar_wind::add_source (:166-176): Msun/yr and km/s to cgs (for an evolving source the table values, already
+  // cgs, pass through this conversion too; update_source overwrites them at the first update)
+  W.Mdot_c = mdot * 1.9891e33 / 3.1558150e7;
+  W.Vinf_c = vinf * 1.0e5;
+  W.vrot_c = vrot * 1.0e5;
+  W.Tw_c = Tw;
+  W.Rstar_c = Rstar;
+
+  // membership: every cell, ghosts included, in cell-id order (a scan: hipcub::DeviceSelect keeps the input order)
+  WindMember m;
+  m.g = g;
+  for (int a = 0; a < 3; a++) m.pos[a] = W.pos[a];
+  m.radius = W.radius;
+  unsigned long long *dcount = nullptr;
+  HCHECK(h, hipMalloc(&dcount, sizeof(unsigned long long)));
+  HCHECK(h, hipMemsetAsync(dcount, 0, sizeof(unsigned long long), h->stream));
+  hipLaunchKernelGGL(k_wind_count, dim3((unsigned)((g.ncell + 255) / 256)), dim3(256), 0, h->stream, m, dcount);
+  unsigned long long cnt = 0;
+  HCHECK(h, hipMemcpyAsync(&cnt, dcount, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  const long n = (long)cnt, ntot = h->nws + n;
+  long *nidx = nullptr;
+  double *ndist = nullptr, *noff = nullptr, *nstate = nullptr;
+  if (ntot > 0) {
+    HCHECK(h, hipMalloc(&nidx, sizeof(long) * ntot));
+    HCHECK(h, hipMalloc(&ndist, sizeof(double) * ntot));
+    HCHECK(h, hipMalloc(&noff, sizeof(double) * 3 * ntot));
+    HCHECK(h, hipMalloc(&nstate, sizeof(double) * ntot * cfg.nvar));
+    HCHECK(h, hipMemsetAsync(nstate, 0, sizeof(double) * ntot * cfg.nvar, h->stream));
+  }
+  if (h->nws > 0) {
+    // the earlier sources' cells keep their place at the front
+    const long o = h->nws;
+    HCHECK(h, hipMemcpyAsync(nidx, h->dws_idx, sizeof(long) * o, hipMemcpyDeviceToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(ndist, h->dws_dist, sizeof(double) * o, hipMemcpyDeviceToDevice, h->stream));
+    for (int a = 0; a < 3; a++)
+      HCHECK(h, hipMemcpyAsync(noff + a * ntot, h->dws_off + a * o, sizeof(double) * o, hipMemcpyDeviceToDevice,
+                               h->stream));
+    HCHECK(h, hipMemcpyAsync(nstate, h->dws_state, sizeof(double) * o * cfg.nvar, hipMemcpyDeviceToDevice, h->stream));
+  }
+  if (n > 0) {
+    hipcub::CountingInputIterator<long> cells(0);
+    long *dsel = nullptr;
+    HCHECK(h, hipMalloc(&dsel, sizeof(long)));
+    size_t tmp_bytes = 0;
+    HCHECK(h, hipcub::DeviceSelect::If(nullptr, tmp_bytes, cells, nidx + h->nws, dsel, g.ncell, m, h->stream));
+    void *tmp = nullptr;
+    HCHECK(h, hipMalloc(&tmp, tmp_bytes));
+    HCHECK(h, hipcub::DeviceSelect::If(tmp, tmp_bytes, cells, nidx + h->nws, dsel, g.ncell, m, h->stream));
+    long nsel = 0;
+    HCHECK(h, hipMemcpyAsync(&nsel, dsel, sizeof nsel, hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    hipFree(tmp);
+    hipFree(dsel);
+    if (nsel != n) {
+      h->err = "wind source: membership count and compaction disagree";
+      return PION_GPU_EDEVICE;
+    }
+    hipLaunchKernelGGL(k_wind_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, m, nidx + h->nws, n,
+                       ndist + h->nws, noff + h->nws, ntot, h->dflags);
+    // keep the host mirror of the flags in step (set_wind_cells uploads it whole)
+    std::vector<long> hidx(n);
+    HCHECK(h, hipMemcpyAsync(hidx.data(), nidx + h->nws, sizeof(long) * n, hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    for (long k = 0; k < n; k++) {
+      h->hflags[hidx[k]] |= PION_CELL_ISBD;
+      h->hflags[hidx[k]] &= ~PION_CELL_ISDOMAIN;
+    }
+  }
+  HCHECK(h, hipGetLastError());
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  hipFree(dcount);
+  hipFree(h->dws_idx);
+  hipFree(h->dws_dist);
+  hipFree(h->dws_off);
+  hipFree(h->dws_state);
+  h->dws_idx = nidx;
+  h->dws_dist = ndist;
+  h->dws_off = noff;
+  h->dws_state = nstate;
+  W.off = h->nws;
+  W.n = n;
+  h->nws = ntot;
+  h->wsrc.push_back(W);
+  h->dt_cached = false;   // the ISBD flags decide which cells enter the time-step reduction
+  if (id) *id = (int)h->wsrc.size() - 1;
+  return 0;
+}
+
+int pion_gpu_get_wind_cells(void *handle, int id, long *n, long *idx, double *states)
+{
+  Handle *h = use(handle);
+  if (!h || !n || id < 0 || id >= (int)h->wsrc.size()) return PION_GPU_EINVAL;
+  const WindSource &W = h->wsrc[id];
+  *n = W.n;
+  if (!idx || W.n == 0) return 0;
+  HCHECK(h, hipMemcpyAsync(idx, h->dws_idx + W.off, sizeof(long) * W.n, hipMemcpyDeviceToHost, h->stream));
+  if (states)
+    HCHECK(h, hipMemcpyAsync(states, h->dws_state + W.off * h->cfg.nvar, sizeof(double) * W.n * h->cfg.nvar,
+                             hipMemcpyDeviceToHost, h->stream));
+  HCHECK(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -1057,8 +1351,12 @@ int pion_gpu_update_bcs(void *handle, double simtime, int cstep, int maxstep, in
     hipLaunchKernelGGL(k_wind, dim3((unsigned)((h->nwind + 255) / 256)), dim3(256), 0, h->stream, T, h->dwind_idx,
                        h->dwind_state, h->nwind, cfg.nvar, g.ncell);
   }
+  // then the wind sources, in id order (assign_update_bcs.cpp:134-183 -> stellar_wind_boundaries.cpp:326-350)
+  if (h->nws > 0) {
+    if (int rc = wind_sources_update(h, simtime)) return rc;
+  }
   // every face periodic (z possibly handed to the neighbour ranks): one launch fills all ghosts
-  bool all_periodic = (h->nwind == 0 && !cfg.bc_dmach2 && h->fuse_bc);
+  bool all_periodic = (!any_wind(h) && !cfg.bc_dmach2 && h->fuse_bc);
   for (int d = 0; d < 2 * cfg.ndim && all_periodic; d++) {
     const bool zface = (d >= 4);
     if (!(cfg.bc_type[d] == PION_BC_PERIODIC || (zface && cfg.bc_type[d] == PION_BC_SLAB))) all_periodic = false;
@@ -1408,7 +1706,7 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
   a.kz2 = kz2;
   a.kz3 = (kz3 > kz2) ? kz3 : kz2;
   a.zslope_lds = h->zslope_lds;
-  a.plain_cells = (h->nwind == 0) ? 1 : 0;
+  a.plain_cells = any_wind(h) ? 0 : 1;
   a.dE = nullptr;
   // periodic x: k_stage_rows2 writes the x ghost images of its rows (the boundary launch then skips them)
   a.xwrap = (a.use_march != 0 && h->fuse_bc && cfg.bc_type[0] == PION_BC_PERIODIC

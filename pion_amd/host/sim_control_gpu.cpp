@@ -83,6 +83,17 @@ int sim_control_gpu::Init(const double *P_soa, double simtime)
   return err;
 }
 
+int sim_control_gpu::add_wind_source(const pion_gpu_wind_source &src, int *id)
+{
+  if (be_ != pion_backend_gpu()) return PION_GPU_EINVAL;   // the wind sources live in libpion_gpu.so
+  const int err = pion_gpu_add_wind_source(h_, &src, id);
+  if (err) return err;
+  // SWP.params[v]->Vinf is the parameter-file value in km/s (0 for most evolving sources: no limit)
+  const double lim = 0.1 * cfg.cfl * cfg.dx / (src.vinf * 1.0e5);
+  T.wind_dt_limit = (T.wind_dt_limit < 0.0) ? lim : std::min(T.wind_dt_limit, lim);
+  return 0;
+}
+
 int sim_control_gpu::calculate_timestep()
 {
   double t_dyn = 0.0, t_mp = 0.0;
@@ -95,6 +106,7 @@ int sim_control_gpu::calculate_timestep()
   dt_requested_ = false;
   if (err) return err;
   if (T.timestep == 0 && T.first_step_dt_limit > 0.0) t_dyn = std::min(t_dyn, T.first_step_dt_limit);
+  if (T.timestep == 0 && T.wind_dt_limit >= 0.0) t_dyn = std::min(t_dyn, T.wind_dt_limit);
   T.dt = std::min(t_dyn, t_mp);
   // Set_GLM_Speeds(td, dx, 0.25/dx) with the *dynamical* step (calc_timestep.cpp:119-131)
   if (cfg.eqntype == PION_EQGLM) err += be_->set_glm_speeds(h_, t_dyn, cfg.dx, 0.25 / cfg.dx);
@@ -184,6 +196,11 @@ int pion_host_sim_create(const pion_gpu_config *cfg, int device, void **sim)
 }
 void pion_host_sim_destroy(void *s) { delete static_cast<pion_host::sim_control_gpu *>(s); }
 void *pion_host_sim_handle(void *s) { return static_cast<pion_host::sim_control_gpu *>(s)->handle(); }
+int pion_host_sim_add_wind_source(void *s, const pion_gpu_wind_source *src, int *id)
+{
+  if (!s || !src) return PION_GPU_EINVAL;
+  return static_cast<pion_host::sim_control_gpu *>(s)->add_wind_source(*src, id);
+}
 int pion_host_sim_init(void *s, const double *P, double simtime, double finishtime, double first_dt_limit)
 {
   auto *c = static_cast<pion_host::sim_control_gpu *>(s);

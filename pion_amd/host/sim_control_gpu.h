@@ -27,6 +27,7 @@ struct SimTime {
   double simtime = 0.0, finishtime = 1e300, dt = 0.0, last_dt = 1e100, min_timestep = 0.0;
   int timestep = 0;
   double first_step_dt_limit = -1.0;  // wind / jet limit of calc_dynamics_dt (calc_timestep.cpp:313-323); <0: none
+  double wind_dt_limit = -1.0;        // the same for the sources of add_wind_source, min over them; <0: none
 };
 
 class sim_control_gpu {
@@ -51,6 +52,10 @@ class sim_control_gpu {
   // interior part of the next stage) and min-reduce the time step over the ranks
   // (sim_control_pllel, sim_control_MPI.cpp:482-583; MCMD_boundaries.cpp:122-237)
   int set_comm(slab_comm *c);
+  // stellar_wind_bc::BC_assign_STWIND (stellar_wind_boundaries.cpp:120-190) for one SWP source: a device-built wind
+  // source (pion_gpu_add_wind_source), and its first-step limit 0.1 CFL dx / (Vinf 1e5) (calc_timestep.cpp:318-322).
+  // Before Init.
+  int add_wind_source(const pion_gpu_wind_source &src, int *id);
   int update_boundaries(int cstep, int maxstep, int assign);
   int stage(double dt, int space_ooa, int is_full);
   int finish_halo();

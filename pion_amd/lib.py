@@ -50,6 +50,8 @@ def load_library():
     lib.pion_gpu_stage_part.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int]
     lib.pion_gpu_synchronize.argtypes = [C.c_void_p]
     lib.pion_gpu_set_wind_cells.argtypes = [C.c_void_p, C.c_long, C.POINTER(C.c_long), _dp]
+    lib.pion_gpu_add_wind_source.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    lib.pion_gpu_get_wind_cells.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long), _dp]
     lib.pion_gpu_set_cooling_tables.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     lib.pion_gpu_update_bcs.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int]
     lib.pion_gpu_calc_dt.argtypes = [C.c_void_p, _dp, _dp]
@@ -82,6 +84,7 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_calc_dt_device", "pion_gpu_read_dt", "pion_gpu_get_stream", "pion_gpu_dt_request", "pion_gpu_dt_wait",
     "pion_gpu_halo_spans", "pion_gpu_halo_begin", "pion_gpu_halo_end",
     "pion_gpu_get_timing", "pion_gpu_stage_part", "pion_gpu_set_comm_stream", "pion_gpu_set_jet",
+    "pion_gpu_add_wind_source", "pion_gpu_get_wind_cells",
 ]
 
 
@@ -171,6 +174,24 @@ class GpuSim:
         states = np.ascontiguousarray(states, dtype=np.float64)
         self._chk(self.lib.pion_gpu_set_wind_cells(self.h, idx.size, idx.ctypes.data_as(C.POINTER(C.c_long)),
                                                    _p(states)), "set_wind_cells")
+
+    def add_wind_source(self, src):
+        """pion_gpu_add_wind_source: src is a pion_amd.wind.WindSource; returns its id"""
+        st, keep = src.to_c()
+        i = C.c_int(-1)
+        self._chk(self.lib.pion_gpu_add_wind_source(self.h, C.byref(st), C.byref(i)), "add_wind_source")
+        del keep
+        return i.value
+
+    def get_wind_cells(self, sid):
+        """pion_gpu_get_wind_cells: (cell ids, states[n, nvar]) of source `sid`"""
+        n = C.c_long(0)
+        self._chk(self.lib.pion_gpu_get_wind_cells(self.h, sid, C.byref(n), None, None), "get_wind_cells")
+        idx = np.zeros(n.value, dtype=np.int64)
+        st = np.zeros((n.value, self.nvar))
+        self._chk(self.lib.pion_gpu_get_wind_cells(self.h, sid, C.byref(n), idx.ctypes.data_as(C.POINTER(C.c_long)),
+                                                   _p(st)), "get_wind_cells")
+        return idx, st
 
     def set_jet(self, jetradius, jetstate):
         st = np.ascontiguousarray(jetstate, dtype=np.float64)

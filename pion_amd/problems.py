@@ -417,3 +417,76 @@ def cooling_blast3d(n, strict_fp=0, solver=abi.FLUX_FVS):
     P[abi.PG] = P[abi.RO] * np.where(inside, 2.0e6, 7.5e3) / mu_over_kb
     P[5] = np.where(inside, 1.0, 0.0)
     return cfg, P
+
+
+# ---- device-built wind sources (pion_amd.wind, pion_gpu_add_wind_source) ------------------------------------------
+
+def wind2d_axi(n, ny=None, strict_fp=0):
+    """test_problems/Wind2D/params_Wind2D_HD_l3n0128.txt on one level of n x n cells: 2-D cylindrical (z,R), Euler +
+    1 tracer, Roe, FKJ98 eta 0.15, cooling 8 (no cooling-time limit), T in [5e3, 1e8], a 25 km/s stream entering
+    through XP, a rotating constant wind (1e-8 Msun/yr, 1500 km/s, vrot 200 km/s) on the axis.  The wind radius
+    (2e17 cm, ~20 cells of the finest of 3 levels) is kept at least 6 cells of this single level.
+    ny (default n) < n cuts the R extent at ny cells.  Returns (cfg, P, [WindSource])."""
+    from . import wind
+    ny = n if ny is None else ny
+    cfg = abi.make_config(2, [n, ny], abi.EQEUL, abi.FLUX_RSroe, ntracer=1, artvisc=abi.AV_FKJ98_1D, etav=0.15,
+                          gamma=1.6666666666666667, cfl=0.3, dx=5.0e18 / n, xmin=(-4.0e18, 0.0, 0.0),
+                          bcs=["one-way-outflow", "inflow", "axisymmetric", "one-way-outflow"],
+                          refvec=[7.0e-24, 7.0e-12, 25.0e5, 25.0e5, 25.0e5, 1.0], min_temp=5.0e3, max_temp=1.0e8,
+                          cooling=abi.COOL_WSS09_CIE_LINE_HEAT_COOL, mp_timestep_limit=0, strict_fp=strict_fp,
+                          coord_sys=2)
+    P = alloc(cfg)
+    P[abi.RO] = 7.0e-24
+    P[abi.PG] = 7.0e-12
+    P[abi.VX] = -25.0e5
+    src = wind.WindSource(pos=(0.0, 0.0), radius=max(2.0e17, 6.0 * cfg.dx), mdot=1.0e-8, vinf=1500.0, vrot=200.0,
+                          Tw=3.0e4, Rstar=1.0e12, Bstar=0.0, tracers=[1.0])
+    return cfg, P, [src]
+
+
+def wind3d_rot(n, strict_fp=0, eqntype=abi.EQGLM, vrot=200.0, Bstar=0.1):
+    """test_problems/Wind3D/params_Wind3Drot_n0128l2.txt on one level of n^3 cells: GLM-MHD + 1 tracer, HLL,
+    FKJ98 eta 0.15, cooling 8 with the cooling-time limit, T in [5e3, 1e10], one-way outflow everywhere, a rotating
+    magnetised constant wind (1e-7 Msun/yr, 200 km/s, vrot 200 km/s, Bsrf 0.1 G, Rstar 6.96e12 cm) at the origin.
+    The wind radius (6.96e12 cm) is kept at least 6 cells.  Returns (cfg, P, [WindSource])."""
+    from . import wind
+    L = 5.93920e13
+    nvb = {abi.EQEUL: 5, abi.EQMHD: 8, abi.EQGLM: 9}[eqntype]
+    ref = [2.124229813e-20, 2.209037632e-08, 1.0e6, 1.0e6, 1.0e6] + ([1.0e-4] * 3 if nvb >= 8 else []) \
+        + ([0.0] if nvb == 9 else []) + [1.0]
+    cfg = abi.make_config(3, [n, n, n], eqntype, abi.FLUX_RS_HLL, ntracer=1, artvisc=abi.AV_FKJ98_1D, etav=0.15,
+                          gamma=1.6666666666666667, cfl=0.3, xmin=(-L, -L, -L), xmax=(L, L, L),
+                          bcs=["one-way-outflow"] * 6, refvec=ref, min_temp=5.0e3, max_temp=1.0e10,
+                          cooling=abi.COOL_WSS09_CIE_LINE_HEAT_COOL, mp_timestep_limit=1, strict_fp=strict_fp)
+    P = alloc(cfg)
+    P[abi.RO] = 2.124229813e-20
+    P[abi.PG] = 2.209037632e-08
+    if nvb >= 8:
+        P[abi.BX] = 1.0e-4
+    src = wind.WindSource(pos=(0.0, 0.0, 0.0), radius=max(6.96e12, 6.0 * cfg.dx), mdot=1.0e-7, vinf=200.0,
+                          vrot=vrot, Tw=3.0e4, Rstar=6.96e12, Bstar=Bstar, tracers=[1.0])
+    return cfg, P, [src]
+
+
+def etacar2d_evolving(n, wnd_path, time_offset=0.0, t_scalefac=1.0, t_now=5.0e10, strict_fp=0):
+    """test_problems/EvolvingStar2D/params_EtaCar_LGM99_d2l3n256_xi043.txt on one level of n x n/2 cells, with the
+    product's microphysics: 2-D cylindrical (z,R), Euler + 1 tracer (WIND1), HLL, CFL 0.2, no artificial viscosity,
+    no cooling (the reference set-up runs MPv3 chemistry; without a microphysics object the wind's temperature
+    floor is the neutral-gas one), T_min 300 K, one-way outflow and the axis, an evolving wind from `wnd_path`
+    (eta_car.wnd.txt) on the axis.  The wind radius (1.32e16 cm, ~20 cells of the finest of 3 levels) is kept at
+    least 6 cells.  The source's parameter vinf (450 km/s, the table's first wind speed) only sets the first-step
+    limit, which the shipped set-up leaves off (WIND_0_vinf 0).  Returns (cfg, P, [WindSource])."""
+    from . import wind
+    L = 3.39e17
+    cfg = abi.make_config(2, [n, n // 2], abi.EQEUL, abi.FLUX_RS_HLL, ntracer=1, artvisc=abi.AV_NONE, etav=0.15,
+                          gamma=1.6666666666666667, cfl=0.2, xmin=(-L, 0.0, 0.0), xmax=(L, L, 0.0),
+                          bcs=["one-way-outflow", "one-way-outflow", "axisymmetric", "one-way-outflow"],
+                          refvec=[2.338e-22, 1.318e-11, 1.0e6, 1.0e6, 1.0e6, 1.0], min_temp=3.0e2, max_temp=1.0e9,
+                          strict_fp=strict_fp, coord_sys=2)
+    P = alloc(cfg)
+    P[abi.RO] = 2.338e-22
+    P[abi.PG] = 1.318e-11
+    ev = wind.read_wind_evolution(wnd_path, time_offset, t_scalefac)
+    src = wind.WindSource(pos=(0.0, 0.0), radius=max(13.2e15, 6.0 * cfg.dx), vinf=450.0, tracers=[1.0],
+                          type=wind.EVOLVING, evolution=ev, elements=[None], t_now=t_now, update_freq=1.0 / t_scalefac)
+    return cfg, P, [src]
