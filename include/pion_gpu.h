@@ -188,6 +188,15 @@ typedef struct pion_gpu_wind_source {
                                         * (set_element_indices, :992-1024; the caller maps the tracer names) */
   double t_now;               /* simulation time when the source is set up (add_evolving_source's t_now) */
   double update_freq;         /* SWP update_freq / t_scalefactor (only decides activity at set-up) */
+  /* orbital motion (BC_update_STWIND, boundaries/stellar_wind_boundaries.cpp:253-352; WIND_i_ecentricity_fac,
+   * WIND_i_periastron_vec_x/y, WIND_i_orbital_period of dataIO/dataio_base.cpp:934-980): with orbit_period != 0
+   * the source moves on an ellipse in the x-y plane around `pos`, re-placed at every boundary update from that
+   * update's simtime (pion_gpu_wind_orbit_position).  orbit_period = 0: the source stays at `pos`.
+   * Both periastron components and orbit_ecc_fac must be non-zero, else the position is NaN (as in the
+   * reference) and the source loses its cells at the first update. */
+  double orbit_ecc_fac;       /* ecentricity_fac */
+  double orbit_periastron[2]; /* periastron vector (x, y), cm */
+  double orbit_period;        /* years; 0 = fixed */
 } pion_gpu_wind_source;
 
 /* stellar_wind::add_source / stellar_wind_evolution::add_evolving_source + BC_assign_STWIND_add_cells2src: every
@@ -195,11 +204,23 @@ typedef struct pion_gpu_wind_source {
  * marked isbd = true, isdomain = false.  Call after create, any number of times; sources are applied in id order
  * (*id = 0, 1, ...).  EINVAL where the reference calls rep.error: a source off the axis (cylindrical) or off r = 0
  * (spherical), MHD in 1-D, type 2 or 3, radius <= 0, an evolving table with npt < 2, more than
- * PION_MAX_WIND_SOURCES sources. */
+ * PION_MAX_WIND_SOURCES sources.  Also EINVAL (a divergence: the reference would move the source off the axis or
+ * the origin) for orbit_period != 0 on a 1-D grid or a cylindrical or spherical one.
+ * A source with orbit_period != 0 is re-placed at every pion_gpu_update_bcs, before any state is written, in id
+ * order: the cells within `radius` of its current position lose isbd and become isdomain (whichever source they
+ * belong to, ghosts included), then the cells within `radius` of the new position join it in cell-id order. */
 int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int *id);
+/* Current position of source `id` (PION_MAX_DIM doubles; unused axes 0). */
+int pion_gpu_get_wind_source_pos(void *handle, int id, double *pos);
+/* The cell flags (PION_CELL_*, ncell_all bytes, ghosts included) as the device holds them now (synchronises). */
+int pion_gpu_get_flags(void *handle, unsigned char *out);
+/* The position the orbit of `src` gives at `simtime` on a grid of `ndim` (2 or 3) dimensions, in plain double as
+ * BC_update_STWIND computes it (src->pos for orbit_period == 0).  Host only: needs no device or handle.  EINVAL for
+ * ndim outside 2..3 or a NULL pointer. */
+int pion_gpu_wind_orbit_position(const pion_gpu_wind_source *src, int ndim, double simtime, double *pos);
 /* The cells of source `id` in cell-id order and the states (n*nvar doubles, cell-major) the last boundary update
  * wrote (zeros before the first one, or while an evolving source is inactive).  *n = number of cells; idx ==
- * NULL: size query only; states may be NULL. */
+ * NULL: size query only; states may be NULL.  For a moving source: its current cells (synchronises the stream). */
 int pion_gpu_get_wind_cells(void *handle, int id, long *n, long *idx, double *states);
 
 /* jet_bc::BC_assign_JETBC / BC_update_JETBC (boundaries/jet_boundaries.cpp:36-208, 3-D Cartesian

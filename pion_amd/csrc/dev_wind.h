@@ -112,11 +112,77 @@ __global__ __launch_bounds__(256) void k_wind_cells(const WindMember m, const lo
   flags[c] = (uint8_t)((flags[c] | PION_CELL_ISBD) & ~PION_CELL_ISDOMAIN);
 }
 
+// ---- moving sources (BC_update_STWIND, stellar_wind_boundaries.cpp:253-352) ------------------------------------
+// A moving source's cells are found in an index box around its sphere instead of the whole grid: all-cell indices
+// (ghosts included, 0 .. nga-1) lo[a] .. lo[a] + w[a] - 1, x fastest.  w is fixed when the source is added (the
+// sphere's extent plus a margin of one cell each side); lo follows the source.  Box entries off the grid with ghosts
+// are no cells.  Walking the box in its own order visits cells in increasing cell id.
+struct WindBox {
+  int lo[3], w[3];
+  long n;   // w[0] * w[1] * w[2]
+};
+
+__device__ inline long wind_box_cell(const GridDesc &g, const WindBox &b, const long k)
+{
+  const int i0 = b.lo[0] + (int)(k % b.w[0]);
+  const int i1 = b.lo[1] + (int)((k / b.w[0]) % b.w[1]);
+  const int i2 = b.lo[2] + (int)(k / ((long)b.w[0] * b.w[1]));
+  if (i0 < 0 || i0 >= g.nga[0] || i1 < 0 || i1 >= g.nga[1] || i2 < 0 || i2 >= g.nga[2]) return -1;
+  return (long)i0 + g.sy * i1 + g.sz * i2;
+}
+
+// hipcub input: box entry -> cell id (-1: none); predicate: a cell within the radius (the exact membership test)
+struct WindBoxCell {
+  GridDesc g;
+  WindBox b;
+  __device__ long operator()(const long k) const { return wind_box_cell(g, b, k); }
+};
+struct WindBoxMember {
+  WindMember m;
+  __device__ bool operator()(const long c) const { return c >= 0 && m(c); }
+};
+
+// stellar_wind::remove_cells (stellar_wind_BC.cpp:349-367) for every cell (ghosts included) within the radius of the
+// source's current position: isbd = false, isdomain = true, timestep = true -- whichever source the cell belongs to
+__global__ __launch_bounds__(256) void k_wind_unflag(const WindMember m, const WindBox b, uint8_t *flags)
+{
+  const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= b.n) return;
+  const long c = wind_box_cell(m.g, b, k);
+  if (c < 0 || !m(c)) return;
+  flags[c] = (uint8_t)((flags[c] & ~PION_CELL_ISBD) | PION_CELL_ISDOMAIN | PION_CELL_TIMESTEP);
+}
+
+// k_wind_cells for a moving source, whose count the compaction left on the device (*dn <= the launch's capacity)
+__global__ __launch_bounds__(256) void k_wind_cells_dn(const WindMember m, const long *idx, const long *dn,
+                                                       double *dist, double *off, const long ntot, uint8_t *flags)
+{
+  const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= *dn) return;
+  const long c = idx[k];
+  const WindGeo w = wind_geo(m.g, m.pos, c);
+  dist[k] = w.d;
+  off[k] = w.x;
+  off[ntot + k] = w.y;
+  off[2 * ntot + k] = w.z;
+  flags[c] = (uint8_t)((flags[c] | PION_CELL_ISBD) & ~PION_CELL_ISDOMAIN);
+}
+
+// the legacy list of pion_gpu_set_wind_cells: mark its cells boundary data (stellar_wind_BC.cpp:277-278)
+__global__ __launch_bounds__(256) void k_flag_wind_list(const long *idx, const long n, uint8_t *flags)
+{
+  const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const long c = idx[k];
+  flags[c] = (uint8_t)((flags[c] | PION_CELL_ISBD) & ~PION_CELL_ISDOMAIN);
+}
+
 // Parameters of one source at the time of the update (cgs, as stored in wind_source)
 struct WindSrcDev {
   double Mdot, Vinf, v_rot, Tw, Rstar, Bstar, radius;
   double tr[PION_MAX_NTR];
-  long off, n;   // the source's range in the concatenated cell list
+  long off, n;   // the source's range in the concatenated cell list (moving source: n = its capacity)
+  const long *dn;   // moving source: its cell count, on the device (nullptr: n)
   int active;
 };
 
@@ -139,7 +205,7 @@ __global__ __launch_bounds__(256) void k_wind_state(const WindStateArgs a, const
 #pragma clang fp contract(off)
   const WindSrcDev &W = a.s[s];
   const long k0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k0 >= W.n) return;
+  if (k0 >= (W.dn ? *W.dn : W.n)) return;
   const long k = W.off + k0;
   const double gamma = 5. / 3.;
   const double kB = 1.38064852e-16, m_p = 1.672621898e-24, pi = 3.14159265358979324;

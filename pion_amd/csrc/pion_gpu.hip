@@ -432,7 +432,15 @@ struct WindSource {
   double tr[PION_MAX_NVAR];
   bool active = true;
   double tstart = 0.0, tfinish = 0.0, t_next_update = 1.0e99;
-  long off = 0, n = 0;   // range in the concatenated cell list
+  long off = 0, n = 0;   // range in the concatenated cell list (moving source: n = its capacity, the box size)
+  // orbital motion (orbit_period != 0): the position at set-up (dpos_init), the orbit, the box the cells are found
+  // in, the device count the compaction writes, and the compaction's scratch (all sized at set-up)
+  bool moving = false;
+  pion_gpu_wind_source orbit;   // pos = dpos_init, orbit_* (the pointers are not used)
+  int box_w[3] = {1, 1, 1};
+  long *dn = nullptr;
+  void *dscan = nullptr;
+  size_t scan_bytes = 0;
 };
 
 struct Handle {
@@ -622,11 +630,194 @@ static double root_find_linear_vec(const std::vector<double> &xarr, const std::v
   return yarr[ilo] + (yarr[ihi] - yarr[ilo]) * (xval - xarr[ilo]) / (xarr[ihi] - xarr[ilo]);
 }
 
+// Append n slots to the concatenated wind-source lists (cell ids, dist, offsets, states; the new states zeroed); the
+// earlier sources' entries keep their place at the front.  h->nws grows by n.
+static int wind_lists_grow(Handle *h, const long n)
+{
+  const long o = h->nws, ntot = o + n;
+  const int nvar = h->cfg.nvar;
+  long *nidx = nullptr;
+  double *ndist = nullptr, *noff = nullptr, *nstate = nullptr;
+  if (ntot > 0) {
+    HCHECK(h, hipMalloc(&nidx, sizeof(long) * ntot));
+    HCHECK(h, hipMalloc(&ndist, sizeof(double) * ntot));
+    HCHECK(h, hipMalloc(&noff, sizeof(double) * 3 * ntot));
+    HCHECK(h, hipMalloc(&nstate, sizeof(double) * ntot * nvar));
+    HCHECK(h, hipMemsetAsync(nstate, 0, sizeof(double) * ntot * nvar, h->stream));
+  }
+  if (o > 0) {
+    HCHECK(h, hipMemcpyAsync(nidx, h->dws_idx, sizeof(long) * o, hipMemcpyDeviceToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(ndist, h->dws_dist, sizeof(double) * o, hipMemcpyDeviceToDevice, h->stream));
+    for (int a = 0; a < 3; a++)
+      HCHECK(h, hipMemcpyAsync(noff + a * ntot, h->dws_off + a * o, sizeof(double) * o, hipMemcpyDeviceToDevice,
+                               h->stream));
+    HCHECK(h, hipMemcpyAsync(nstate, h->dws_state, sizeof(double) * o * nvar, hipMemcpyDeviceToDevice, h->stream));
+  }
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  hipFree(h->dws_idx);
+  hipFree(h->dws_dist);
+  hipFree(h->dws_off);
+  hipFree(h->dws_state);
+  h->dws_idx = nidx;
+  h->dws_dist = ndist;
+  h->dws_off = noff;
+  h->dws_state = nstate;
+  h->nws = ntot;
+  return 0;
+}
+
+// BC_update_STWIND's new source position (stellar_wind_boundaries.cpp:294-314): the ellipse in the x-y plane, in
+// plain double, the reference's expressions in their order (no contraction).  abs is std::abs(double) there;
+// pconst.pi() and pconst.year() are constants.h:45,107.  z stays at dpos_init.
+static void wind_orbit_position(const pion_gpu_wind_source &s, const int ndim, const double simtime, double *pos)
+{
+#pragma clang fp contract(off)
+  for (int v = 0; v < 3; v++) pos[v] = (v < ndim) ? s.pos[v] : 0.0;
+  if (s.orbit_period == 0) return;
+  const double pi = 3.14159265358979324, year = 3.1558150e7;
+  const double px = s.orbit_periastron[0], py = s.orbit_periastron[1];
+  const double f = s.orbit_ecc_fac, P = s.orbit_period;
+  const double cos_a = -1 * px / std::abs(px) * cos(atan(py / px));
+  const double sin_a = sin(-1 * py / std::abs(py) * acos(cos_a));
+  const double a = sqrt(px * px + py * py) * f;
+  const double e = a * (f - 1) / f;
+  const double b = sqrt(a * a - e * e);
+  const double sin_t = sin(2 * pi * simtime / (P * year));
+  const double cos_t = cos(2 * pi * simtime / (P * year));
+  pos[0] = s.pos[0] - a * cos_a + cos_a * a * cos_t - sin_a * b * sin_t;
+  pos[1] = s.pos[1] - a * sin_a + sin_a * a * cos_t + cos_a * b * sin_t;
+}
+
+// The box of moving source W centred on `pos`: per axis the w cells from one below the first cell whose centre can
+// lie within the radius (the exact test runs in the kernels).  A NaN position gives some box; no cell passes there.
+static WindBox wind_box(const Handle *h, const WindSource &W, const double *pos)
+{
+  const GridDesc &g = h->g;
+  WindBox b;
+  b.n = 1;
+  for (int a = 0; a < 3; a++) {
+    b.w[a] = W.box_w[a];
+    b.lo[a] = 0;
+    if (a < g.ndim && b.w[a] < g.nga[a]) {
+      // all-cell index i has its centre at xmin + (i - nbc + 0.5) dx
+      double t = (pos[a] - W.radius - g.xmin[a]) / g.dx - 0.5 + g.nbc[a];
+      if (!(t == t)) t = 0.0;
+      t = std::min(std::max(t, -2.0 * g.nga[a]), 2.0 * g.nga[a]);
+      b.lo[a] = (int)floor(t) - 1;
+    }
+    b.n *= b.w[a];
+  }
+  return b;
+}
+
+static WindMember wind_member(const Handle *h, const WindSource &W)
+{
+  WindMember m;
+  m.g = h->g;
+  for (int a = 0; a < 3; a++) m.pos[a] = W.pos[a];
+  m.radius = W.radius;
+  return m;
+}
+
+typedef hipcub::TransformInputIterator<long, WindBoxCell, hipcub::CountingInputIterator<long>> WindBoxIter;
+
+// BC_assign_STWIND_add_cells2src for a moving source at W.pos: the cells of its box within the radius, in cell-id
+// order, compacted into its slot of the lists with the count left in W.dn; then dist, offsets and the flags
+// (stellar_wind::add_cell, stellar_wind_BC.cpp:255-283).  Asynchronous, no allocation.
+static int wind_add_cells_box(Handle *h, const WindSource &W)
+{
+  const WindMember m = wind_member(h, W);
+  WindBoxCell bc;
+  bc.g = h->g;
+  bc.b = wind_box(h, W, W.pos);
+  WindBoxMember pred;
+  pred.m = m;
+  WindBoxIter cells(hipcub::CountingInputIterator<long>(0), bc);
+  size_t bytes = W.scan_bytes;
+  HCHECK(h, hipcub::DeviceSelect::If(W.dscan, bytes, cells, h->dws_idx + W.off, W.dn, (int)W.n, pred, h->stream));
+  hipLaunchKernelGGL(k_wind_cells_dn, dim3((unsigned)((W.n + 255) / 256)), dim3(256), 0, h->stream, m,
+                     h->dws_idx + W.off, W.dn, h->dws_dist + W.off, h->dws_off + W.off, h->nws, h->dflags);
+  return 0;
+}
+
+// pion_gpu_add_wind_source for a source with orbit_period != 0 (2-D / 3-D Cartesian): its slot in the lists, the
+// count and the compaction scratch are sized once, to the box.  The cells at dpos_init join it now, as for a fixed
+// source.
+static int add_moving_wind_source(Handle *h, WindSource &W, int *id)
+{
+  const GridDesc &g = h->g;
+  long cap = 1;
+  for (int a = 0; a < 3; a++) {
+    W.box_w[a] = 1;
+    if (a < g.ndim) {
+      // the sphere spans at most floor(2 radius / dx) + 1 cell centres per axis; plus the margin, plus rounding
+      const double w = floor(2.0 * W.radius / g.dx) + 5.0;
+      W.box_w[a] = (w >= (double)g.nga[a]) ? g.nga[a] : (int)w;
+    }
+    cap *= W.box_w[a];
+  }
+  if (cap > 0x7fffffffL) {
+    h->err = "wind source: the orbit box is too large";
+    return PION_GPU_EINVAL;
+  }
+  if (int rc = wind_lists_grow(h, cap)) return rc;
+  W.off = h->nws - cap;
+  W.n = cap;
+  HCHECK(h, hipMalloc(&W.dn, sizeof(long)));
+  HCHECK(h, hipMemsetAsync(W.dn, 0, sizeof(long), h->stream));
+  {
+    WindBoxCell bc;
+    bc.g = g;
+    bc.b = wind_box(h, W, W.pos);
+    WindBoxMember pred;
+    pred.m = wind_member(h, W);
+    WindBoxIter cells(hipcub::CountingInputIterator<long>(0), bc);
+    W.scan_bytes = 0;
+    HCHECK(h, hipcub::DeviceSelect::If(nullptr, W.scan_bytes, cells, h->dws_idx + W.off, W.dn, (int)cap, pred,
+                                       h->stream));
+    HCHECK(h, hipMalloc(&W.dscan, W.scan_bytes > 0 ? W.scan_bytes : 1));
+  }
+  h->wsrc.push_back(W);
+  if (int rc = wind_add_cells_box(h, h->wsrc.back())) return rc;
+  HCHECK(h, hipGetLastError());
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  h->dt_cached = false;   // the ISBD flags decide which cells enter the time-step reduction
+  if (id) *id = (int)h->wsrc.size() - 1;
+  return 0;
+}
+
+// BC_update_STWIND (stellar_wind_boundaries.cpp:270-322) for every moving source, in id order: remove_cells on the
+// cells within the radius of the current position, the new position from simtime, then the cells within the radius
+// of that position join the source.  Launches only, over the two boxes; nothing waits for the device.
+static int wind_sources_move(Handle *h, const double simtime)
+{
+  bool moved = false;
+  for (size_t s = 0; s < h->wsrc.size(); s++) {
+    WindSource &W = h->wsrc[s];
+    if (!W.moving) continue;
+    const WindBox ob = wind_box(h, W, W.pos);
+    hipLaunchKernelGGL(k_wind_unflag, dim3((unsigned)((ob.n + 255) / 256)), dim3(256), 0, h->stream,
+                       wind_member(h, W), ob, h->dflags);
+    double np[3];
+    wind_orbit_position(W.orbit, h->cfg.ndim, simtime, np);
+    for (int a = 0; a < 3; a++) {
+      moved = moved || !(np[a] == W.pos[a]);
+      W.pos[a] = np[a];
+    }
+    if (int rc = wind_add_cells_box(h, W)) return rc;
+  }
+  // An unchanged position leaves the flags as they were: every cell an unflag touches lies in the sphere of that
+  // moving source, which re-adds it at once.  A move changes them, and with them the cached time step.
+  if (moved) h->dt_cached = false;
+  return 0;
+}
+
 // stellar_wind_evolution::set_cell_values (stellar_wind_BC.cpp:1334-1372) and update_source (:1250-1330) for every
 // source, then one launch per active source, in id order, that writes the reference states of its cells (no host
 // synchronisation: the parameters are scalars of the host, the launch carries them)
 int wind_sources_update(Handle *h, const double simtime)
 {
+  if (int rc = wind_sources_move(h, simtime)) return rc;
   WindStateArgs a;
   memset(&a, 0, sizeof a);
   for (size_t s = 0; s < h->wsrc.size(); s++) {
@@ -654,6 +845,7 @@ int wind_sources_update(Handle *h, const double simtime)
     for (int v = 0; v < PION_MAX_NTR; v++) d.tr[v] = (v < h->cfg.ntracer) ? W.tr[v] : 0.0;
     d.off = W.off;
     d.n = W.n;
+    d.dn = W.moving ? W.dn : nullptr;
     d.active = W.active ? 1 : 0;
   }
   a.P = h->dP;
@@ -934,6 +1126,10 @@ void pion_gpu_destroy(void *handle)
   hipFree(h->dws_dist);
   hipFree(h->dws_off);
   hipFree(h->dws_state);
+  for (WindSource &W : h->wsrc) {
+    hipFree(W.dn);
+    hipFree(W.dscan);
+  }
   hipFree(h->djet_idx);
   hipFree(h->djet_state);
   hipFree(h->dcoolT);
@@ -1039,16 +1235,22 @@ int pion_gpu_set_wind_cells(void *handle, long n, const long *idx, const double 
   h->dwind_state = nullptr;
   h->nwind = n;
   if (n > 0) {
+    for (long k = 0; k < n; k++) {
+      if (idx[k] < 0 || idx[k] >= h->g.ncell) {
+        h->nwind = 0;
+        return PION_GPU_EINVAL;
+      }
+    }
     HCHECK(h, hipMalloc(&h->dwind_idx, sizeof(long) * n));
     HCHECK(h, hipMalloc(&h->dwind_state, sizeof(double) * n * h->cfg.nvar));
     HCHECK(h, hipMemcpy(h->dwind_idx, idx, sizeof(long) * n, hipMemcpyHostToDevice));
     HCHECK(h, hipMemcpy(h->dwind_state, states, sizeof(double) * n * h->cfg.nvar, hipMemcpyHostToDevice));
-    for (long k = 0; k < n; k++) {
-      if (idx[k] < 0 || idx[k] >= h->g.ncell) return PION_GPU_EINVAL;
-      h->hflags[idx[k]] |= PION_CELL_ISBD;  // stellar_wind_BC.cpp:277-278
-      h->hflags[idx[k]] &= ~PION_CELL_ISDOMAIN;
-    }
-    HCHECK(h, hipMemcpy(h->dflags, h->hflags.data(), h->g.ncell, hipMemcpyHostToDevice));
+    // isbd = true, isdomain = false (stellar_wind_BC.cpp:277-278), on the device: the flags there are the only
+    // current ones once a wind source has moved
+    hipLaunchKernelGGL(k_flag_wind_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->dwind_idx, n,
+                       h->dflags);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipStreamSynchronize(h->stream));
   }
   return 0;
 }
@@ -1072,6 +1274,9 @@ int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int 
   if (cfg.coord_sys == 2 && cfg.ndim == 2 && !equalD(src->pos[1], 0.0))
     return fail("Axisymmetry but source not at R=0!");
   if (cfg.ndim == 1 && cfg.eqntype != PION_EQEUL) return fail("1D spherical but MHD?");
+  // a divergence: the reference would move a source on the axis (cylindrical) or at the origin (spherical) off it
+  if (src->orbit_period != 0 && (cfg.ndim < 2 || cfg.coord_sys != 1))
+    return fail("wind source: orbital motion needs a 2-D or 3-D Cartesian grid");
   if (src->type == 1) {
     if (src->npt < 2) return fail("evolving wind source: the table needs at least 2 rows");
     if (!src->evo_time || !src->evo_Teff || !src->evo_Mdot || !src->evo_vrot || !src->evo_vinf || !src->evo_R)
@@ -1136,6 +1341,13 @@ int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int 
   W.Tw_c = Tw;
   W.Rstar_c = Rstar;
 
+  if (src->orbit_period != 0) {
+    W.moving = true;
+    W.orbit = *src;
+    for (int a = 0; a < 3; a++) W.orbit.pos[a] = W.pos[a];   // dpos_init
+    return add_moving_wind_source(h, W, id);
+  }
+
   // membership: every cell, ghosts included, in cell-id order (a scan: hipcub::DeviceSelect keeps the input order)
   WindMember m;
   m.g = g;
@@ -1148,35 +1360,19 @@ int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int 
   unsigned long long cnt = 0;
   HCHECK(h, hipMemcpyAsync(&cnt, dcount, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
   HCHECK(h, hipStreamSynchronize(h->stream));
-  const long n = (long)cnt, ntot = h->nws + n;
-  long *nidx = nullptr;
-  double *ndist = nullptr, *noff = nullptr, *nstate = nullptr;
-  if (ntot > 0) {
-    HCHECK(h, hipMalloc(&nidx, sizeof(long) * ntot));
-    HCHECK(h, hipMalloc(&ndist, sizeof(double) * ntot));
-    HCHECK(h, hipMalloc(&noff, sizeof(double) * 3 * ntot));
-    HCHECK(h, hipMalloc(&nstate, sizeof(double) * ntot * cfg.nvar));
-    HCHECK(h, hipMemsetAsync(nstate, 0, sizeof(double) * ntot * cfg.nvar, h->stream));
-  }
-  if (h->nws > 0) {
-    // the earlier sources' cells keep their place at the front
-    const long o = h->nws;
-    HCHECK(h, hipMemcpyAsync(nidx, h->dws_idx, sizeof(long) * o, hipMemcpyDeviceToDevice, h->stream));
-    HCHECK(h, hipMemcpyAsync(ndist, h->dws_dist, sizeof(double) * o, hipMemcpyDeviceToDevice, h->stream));
-    for (int a = 0; a < 3; a++)
-      HCHECK(h, hipMemcpyAsync(noff + a * ntot, h->dws_off + a * o, sizeof(double) * o, hipMemcpyDeviceToDevice,
-                               h->stream));
-    HCHECK(h, hipMemcpyAsync(nstate, h->dws_state, sizeof(double) * o * cfg.nvar, hipMemcpyDeviceToDevice, h->stream));
-  }
+  hipFree(dcount);
+  const long n = (long)cnt;
+  if (int rc = wind_lists_grow(h, n)) return rc;
+  const long o = h->nws - n, ntot = h->nws;
   if (n > 0) {
     hipcub::CountingInputIterator<long> cells(0);
     long *dsel = nullptr;
     HCHECK(h, hipMalloc(&dsel, sizeof(long)));
     size_t tmp_bytes = 0;
-    HCHECK(h, hipcub::DeviceSelect::If(nullptr, tmp_bytes, cells, nidx + h->nws, dsel, g.ncell, m, h->stream));
+    HCHECK(h, hipcub::DeviceSelect::If(nullptr, tmp_bytes, cells, h->dws_idx + o, dsel, g.ncell, m, h->stream));
     void *tmp = nullptr;
     HCHECK(h, hipMalloc(&tmp, tmp_bytes));
-    HCHECK(h, hipcub::DeviceSelect::If(tmp, tmp_bytes, cells, nidx + h->nws, dsel, g.ncell, m, h->stream));
+    HCHECK(h, hipcub::DeviceSelect::If(tmp, tmp_bytes, cells, h->dws_idx + o, dsel, g.ncell, m, h->stream));
     long nsel = 0;
     HCHECK(h, hipMemcpyAsync(&nsel, dsel, sizeof nsel, hipMemcpyDeviceToHost, h->stream));
     HCHECK(h, hipStreamSynchronize(h->stream));
@@ -1186,34 +1382,42 @@ int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int 
       h->err = "wind source: membership count and compaction disagree";
       return PION_GPU_EDEVICE;
     }
-    hipLaunchKernelGGL(k_wind_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, m, nidx + h->nws, n,
-                       ndist + h->nws, noff + h->nws, ntot, h->dflags);
-    // keep the host mirror of the flags in step (set_wind_cells uploads it whole)
-    std::vector<long> hidx(n);
-    HCHECK(h, hipMemcpyAsync(hidx.data(), nidx + h->nws, sizeof(long) * n, hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    for (long k = 0; k < n; k++) {
-      h->hflags[hidx[k]] |= PION_CELL_ISBD;
-      h->hflags[hidx[k]] &= ~PION_CELL_ISDOMAIN;
-    }
+    hipLaunchKernelGGL(k_wind_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, m, h->dws_idx + o,
+                       n, h->dws_dist + o, h->dws_off + o, ntot, h->dflags);
   }
   HCHECK(h, hipGetLastError());
   HCHECK(h, hipStreamSynchronize(h->stream));
-  hipFree(dcount);
-  hipFree(h->dws_idx);
-  hipFree(h->dws_dist);
-  hipFree(h->dws_off);
-  hipFree(h->dws_state);
-  h->dws_idx = nidx;
-  h->dws_dist = ndist;
-  h->dws_off = noff;
-  h->dws_state = nstate;
-  W.off = h->nws;
+  W.off = o;
   W.n = n;
-  h->nws = ntot;
   h->wsrc.push_back(W);
   h->dt_cached = false;   // the ISBD flags decide which cells enter the time-step reduction
   if (id) *id = (int)h->wsrc.size() - 1;
+  return 0;
+}
+
+int pion_gpu_get_wind_source_pos(void *handle, int id, double *pos)
+{
+  Handle *h = use(handle);
+  if (!h || !pos || id < 0 || id >= (int)h->wsrc.size()) return PION_GPU_EINVAL;
+  for (int a = 0; a < PION_MAX_DIM; a++) pos[a] = (a < 3) ? h->wsrc[id].pos[a] : 0.0;
+  return 0;
+}
+
+int pion_gpu_get_flags(void *handle, unsigned char *out)
+{
+  Handle *h = use(handle);
+  if (!h || !out) return PION_GPU_EINVAL;
+  HCHECK(h, hipMemcpyAsync(out, h->dflags, h->g.ncell, hipMemcpyDeviceToHost, h->stream));
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int pion_gpu_wind_orbit_position(const pion_gpu_wind_source *src, int ndim, double simtime, double *pos)
+{
+  if (!src || !pos || ndim < 2 || ndim > 3) return PION_GPU_EINVAL;
+  double p[3];
+  wind_orbit_position(*src, ndim, simtime, p);
+  for (int a = 0; a < PION_MAX_DIM; a++) pos[a] = (a < 3) ? p[a] : 0.0;
   return 0;
 }
 
@@ -1222,11 +1426,21 @@ int pion_gpu_get_wind_cells(void *handle, int id, long *n, long *idx, double *st
   Handle *h = use(handle);
   if (!h || !n || id < 0 || id >= (int)h->wsrc.size()) return PION_GPU_EINVAL;
   const WindSource &W = h->wsrc[id];
-  *n = W.n;
-  if (!idx || W.n == 0) return 0;
-  HCHECK(h, hipMemcpyAsync(idx, h->dws_idx + W.off, sizeof(long) * W.n, hipMemcpyDeviceToHost, h->stream));
+  long cnt = W.n;
+  if (W.moving) {
+    // the count the last move left on the device
+    HCHECK(h, hipMemcpyAsync(&cnt, W.dn, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    if (cnt < 0 || cnt > W.n) {
+      h->err = "wind source: device cell count out of range";
+      return PION_GPU_EDEVICE;
+    }
+  }
+  *n = cnt;
+  if (!idx || cnt == 0) return 0;
+  HCHECK(h, hipMemcpyAsync(idx, h->dws_idx + W.off, sizeof(long) * cnt, hipMemcpyDeviceToHost, h->stream));
   if (states)
-    HCHECK(h, hipMemcpyAsync(states, h->dws_state + W.off * h->cfg.nvar, sizeof(double) * W.n * h->cfg.nvar,
+    HCHECK(h, hipMemcpyAsync(states, h->dws_state + W.off * h->cfg.nvar, sizeof(double) * cnt * h->cfg.nvar,
                              hipMemcpyDeviceToHost, h->stream));
   HCHECK(h, hipStreamSynchronize(h->stream));
   return 0;

@@ -96,11 +96,15 @@ pion_gpu_bridge::pion_gpu_bridge(class SimParams &par, class GridBaseClass *grid
   // stellar wind: the reference writes a precomputed state into every cell of the boundary's list on each
   // internal-boundary update (stellar_wind_BC.cpp:642-677).  For winds that are constant in time that state
   // is what the cells hold after sim_init's first update, i.e. cell::P at gather time; it is captured there
-  // (gather_and_upload).  Evolving winds change it from step to step on the host: refuse them.
+  // (gather_and_upload).  Evolving winds change it from step to step on the host, and sources on an orbit
+  // (BC_update_STWIND, stellar_wind_boundaries.cpp:253-352) change their cells: refuse both.
   for (size_t i = 0; i < wind_bds.size(); i++) {
-    for (int s = 0; s < SWP.Nsources; s++)
+    for (int s = 0; s < SWP.Nsources; s++) {
       if (SWP.params[s]->type != 0)   // WINDTYPE_CONSTANT (grid/stellar_wind_BC.h)
         throw std::runtime_error("pion_gpu_bridge: evolving / latitude-dependent stellar winds are not translated");
+      if (SWP.params[s]->OrbPeriod != 0)
+        throw std::runtime_error("pion_gpu_bridge: stellar-wind sources on an orbit are not translated");
+    }
     for (std::list<cell *>::const_iterator it = wind_bds[i]->data.begin(); it != wind_bds[i]->data.end(); ++it)
       wind_cells_.push_back(*it);
   }

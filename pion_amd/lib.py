@@ -52,6 +52,9 @@ def load_library():
     lib.pion_gpu_set_wind_cells.argtypes = [C.c_void_p, C.c_long, C.POINTER(C.c_long), _dp]
     lib.pion_gpu_add_wind_source.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     lib.pion_gpu_get_wind_cells.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long), _dp]
+    lib.pion_gpu_get_wind_source_pos.argtypes = [C.c_void_p, C.c_int, _dp]
+    lib.pion_gpu_wind_orbit_position.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp]
+    lib.pion_gpu_get_flags.argtypes = [C.c_void_p, C.c_void_p]
     lib.pion_gpu_set_cooling_tables.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     lib.pion_gpu_update_bcs.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int]
     lib.pion_gpu_calc_dt.argtypes = [C.c_void_p, _dp, _dp]
@@ -84,7 +87,8 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_calc_dt_device", "pion_gpu_read_dt", "pion_gpu_get_stream", "pion_gpu_dt_request", "pion_gpu_dt_wait",
     "pion_gpu_halo_spans", "pion_gpu_halo_begin", "pion_gpu_halo_end",
     "pion_gpu_get_timing", "pion_gpu_stage_part", "pion_gpu_set_comm_stream", "pion_gpu_set_jet",
-    "pion_gpu_add_wind_source", "pion_gpu_get_wind_cells",
+    "pion_gpu_add_wind_source", "pion_gpu_get_wind_cells", "pion_gpu_get_wind_source_pos",
+    "pion_gpu_wind_orbit_position", "pion_gpu_get_flags",
 ]
 
 
@@ -192,6 +196,18 @@ class GpuSim:
         self._chk(self.lib.pion_gpu_get_wind_cells(self.h, sid, C.byref(n), idx.ctypes.data_as(C.POINTER(C.c_long)),
                                                    _p(st)), "get_wind_cells")
         return idx, st
+
+    def get_wind_source_pos(self, sid):
+        """pion_gpu_get_wind_source_pos: the current position of source `sid` (3 floats)"""
+        out = np.zeros(3)
+        self._chk(self.lib.pion_gpu_get_wind_source_pos(self.h, sid, _p(out)), "get_wind_source_pos")
+        return tuple(out)
+
+    def get_flags(self):
+        """pion_gpu_get_flags: the device's cell flags (uint8, ncell_all, cell-id order)"""
+        out = np.zeros(self.ncell, dtype=np.uint8)
+        self._chk(self.lib.pion_gpu_get_flags(self.h, out.ctypes.data), "get_flags")
+        return out
 
     def set_jet(self, jetradius, jetstate):
         st = np.ascontiguousarray(jetstate, dtype=np.float64)

@@ -490,3 +490,67 @@ def etacar2d_evolving(n, wnd_path, time_offset=0.0, t_scalefac=1.0, t_now=5.0e10
     src = wind.WindSource(pos=(0.0, 0.0), radius=max(13.2e15, 6.0 * cfg.dx), vinf=450.0, tracers=[1.0],
                           type=wind.EVOLVING, evolution=ev, elements=[None], t_now=t_now, update_freq=1.0 / t_scalefac)
     return cfg, P, [src]
+
+
+def binary_orbit(x, period, ecc_fac=1.2):
+    """WindSource orbit of a star set up at (x, 0) in a binary about the origin: BC_update_STWIND's ellipse is centred
+    at pos + ecc_fac * periastron, so periastron = -pos / ecc_fac (and a small y part, which the reference needs
+    non-zero) centres it at the origin with semi-major axis |x|.  The stars at +x and -x stay opposite each other,
+    at least 2 b = 2 |x| sqrt(1 - ((f - 1) / f)^2) apart."""
+    return (ecc_fac, -x / ecc_fac, -0.01 * x, period)
+
+
+def cwb2d_orbit(n, strict_fp=0, orbits=(True, True), period=10.0):
+    """test_problems/CollidingWinds2D/param_CWB2DCRT_d2l5n128.txt on one level of n x n cells: 2-D Cartesian (slab
+    symmetry), Euler + 1 tracer, Roe, CFL 0.2, FKJ98 eta 0.15, no cooling, T in [1e-20, 1e25], one-way outflow, two
+    constant winds (0.5e-18 and 1e-18 Msun/yr, 200 and 100 km/s, 1e5 K) at x = +-2.56e15 cm.  The wind radius
+    (8e14 cm, 10-20 cells of the finest of 5 levels) is kept at least 3 cells.  orbits[i]: source i moves on an
+    ellipse of `period` years (binary_orbit); the default period makes the members change every step or two at any
+    n.  Returns (cfg, P, [WindSource, WindSource])."""
+    from . import wind
+    L = 2.048e16
+    cfg = abi.make_config(2, [n, n], abi.EQEUL, abi.FLUX_RSroe, ntracer=1, artvisc=abi.AV_FKJ98_1D, etav=0.15,
+                          gamma=1.6666666666666667, cfl=0.2, xmin=(-L, -L, 0.0), xmax=(L, L, 0.0),
+                          bcs=["one-way-outflow"] * 4, refvec=[1.0e-24, 1.0e-13, 1.0e6, 1.0e6, 1.0e6, 1.0],
+                          min_temp=1.0e-20, max_temp=1.0e25, strict_fp=strict_fp)
+    P = alloc(cfg)
+    P[abi.RO] = 2.124229813e-20
+    P[abi.PG] = 2.209037632e-08
+    r = max(8.0e14, 3.0 * cfg.dx)
+    srcs = []
+    for i, (x, mdot, vinf) in enumerate(((2.56e15, 0.5e-18, 200.0), (-2.56e15, 1.0e-18, 100.0))):
+        orbit = binary_orbit(x, period) if orbits[i] else None
+        srcs.append(wind.WindSource(pos=(x, 0.0), radius=r, mdot=mdot, vinf=vinf, vrot=0.0, Tw=1.0e5, Rstar=6.96e10,
+                                    Bstar=1.0, tracers=[1.0], orbit=orbit))
+    return cfg, P, srcs
+
+
+def cwb3d_orbit(n, strict_fp=0, eqntype=abi.EQGLM, orbits=(True, True), period=3.0):
+    """test_problems/CollidingWinds2D/param_CWB_d3l3n128.txt on one level of n^3 cells: 3-D Cartesian, GLM-MHD (or
+    Euler / MHD) + 1 tracer, HLL, CFL 0.3, no artificial viscosity, no cooling, T in [5e3, 1e9], one-way outflow, two
+    rotating magnetised constant winds (1e-5 and 2e-5 Msun/yr, 2500 and 1250 km/s, vrot 100 km/s, Bsrf 0.01 G) at
+    x = +-4.84e15 cm.  The wind radius (1.2e15 cm, 15 cells of the finest of 3 levels) is kept at least 4 cells.
+    orbits[i]: source i moves on an ellipse of `period` years (binary_orbit); the default makes the members change
+    every step or two at any n.
+    Returns (cfg, P, [WindSource, WindSource])."""
+    from . import wind
+    L = 2.048e16
+    nvb = {abi.EQEUL: 5, abi.EQMHD: 8, abi.EQGLM: 9}[eqntype]
+    ref = [1.0e-24, 1.0e-13, 1.0e6, 1.0e6, 1.0e6] + ([1.0e-6] * 3 if nvb >= 8 else []) \
+        + ([1.0] if nvb == 9 else []) + [1.0]
+    cfg = abi.make_config(3, [n, n, n], eqntype, abi.FLUX_RS_HLL, ntracer=1, artvisc=abi.AV_NONE, etav=0.15,
+                          gamma=1.6666666666666667, cfl=0.3, xmin=(-L, -L, -L), xmax=(L, L, L),
+                          bcs=["one-way-outflow"] * 6, refvec=ref, min_temp=5.0e3, max_temp=1.0e9,
+                          strict_fp=strict_fp)
+    P = alloc(cfg)
+    P[abi.RO] = 2.124229813e-20
+    P[abi.PG] = 2.209037632e-08
+    if nvb >= 8:
+        P[abi.BX] = P[abi.BY] = P[abi.BZ] = 1.0e-5
+    r = max(1.2e15, 4.0 * cfg.dx)
+    srcs = []
+    for i, (x, mdot, vinf) in enumerate(((4.84e15, 1.0e-5, 2500.0), (-4.84e15, 2.0e-5, 1250.0))):
+        orbit = binary_orbit(x, period) if orbits[i] else None
+        srcs.append(wind.WindSource(pos=(x, 0.0, 0.0), radius=r, mdot=mdot, vinf=vinf, vrot=100.0, Tw=1.0e5,
+                                    Rstar=6.96e10, Bstar=0.01, tracers=[1.0], orbit=orbit))
+    return cfg, P, srcs

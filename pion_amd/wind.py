@@ -36,6 +36,7 @@ class PionGpuWindSource(C.Structure):
         ("evo_R", _dp), ("evo_X", _dp * 7),
         ("evo_tracer_elem", C.c_int * abi.PION_MAX_NVAR),
         ("t_now", C.c_double), ("update_freq", C.c_double),
+        ("orbit_ecc_fac", C.c_double), ("orbit_periastron", C.c_double * 2), ("orbit_period", C.c_double),
     ]
 
 
@@ -79,10 +80,13 @@ class WindSource:
     """One SWP wind source.  Constant: mdot [Msun/yr], vinf, vrot [km/s], Tw [K], Rstar [cm], Bstar [G].
     Evolving: `evolution` (a WindEvolution), `elements` = per tracer an element name of ELEMENTS or None (the
     constant tracer value), `t_now` = simulation time at set-up, `update_freq` (already scaled).  `vinf` of an
-    evolving source is only the parameter-file value the first-step limit uses (0: none)."""
+    evolving source is only the parameter-file value the first-step limit uses (0: none).
+    `orbit` = (ecentricity_fac, periastron_x [cm], periastron_y [cm], period [yr]) moves the source on the
+    reference's ellipse around `pos` at every boundary update (2-D and 3-D Cartesian grids); None or a zero period:
+    the source stays at `pos`."""
 
     def __init__(self, pos, radius, mdot=0.0, vinf=0.0, vrot=0.0, Tw=0.0, Rstar=0.0, Bstar=0.0, tracers=(),
-                 type=CONSTANT, evolution=None, elements=None, t_now=0.0, update_freq=0.0):
+                 type=CONSTANT, evolution=None, elements=None, t_now=0.0, update_freq=0.0, orbit=None):
         self.pos = tuple(pos) + (0.0,) * (3 - len(pos))
         self.radius = radius
         self.mdot, self.vinf, self.vrot = mdot, vinf, vrot
@@ -92,6 +96,9 @@ class WindSource:
         self.evolution = evolution
         self.elements = list(elements) if elements is not None else [None] * len(self.tracers)
         self.t_now, self.update_freq = t_now, update_freq
+        self.orbit = tuple(float(v) for v in orbit) if orbit is not None else (0.0, 0.0, 0.0, 0.0)
+        if len(self.orbit) != 4:
+            raise ValueError("orbit = (ecentricity_fac, periastron_x, periastron_y, period_years)")
 
     def to_c(self):
         """(PionGpuWindSource, arrays to keep alive while the struct is used)"""
@@ -121,6 +128,7 @@ class WindSource:
             for v, name in enumerate(self.elements):
                 s.evo_tracer_elem[v] = -1 if name is None else ELEMENTS.index(name)
         s.t_now, s.update_freq = self.t_now, self.update_freq
+        s.orbit_ecc_fac, s.orbit_periastron[0], s.orbit_periastron[1], s.orbit_period = self.orbit
         return s, keep
 
 
@@ -131,3 +139,17 @@ def first_step_dt_limit(cfg, sources, limit=None):
         lim = 0.1 * cfg.cfl * cfg.dx / (s.vinf * 1.0e5) if s.vinf != 0.0 else float("inf")
         limit = lim if limit is None else min(limit, lim)
     return limit
+
+
+def orbit_position(src, ndim, simtime):
+    """pion_gpu_wind_orbit_position (host code of libpion_gpu.so, no device needed): the position of WindSource
+    `src` on its orbit at `simtime` on a grid of `ndim` (2 or 3) dimensions, as a tuple of 3 floats."""
+    from . import lib
+    L = lib.load_library()
+    st, keep = src.to_c()
+    out = (C.c_double * 3)()   # PION_MAX_DIM
+    rc = L.pion_gpu_wind_orbit_position(C.byref(st), int(ndim), float(simtime), out)
+    del keep
+    if rc != 0:
+        raise ValueError("pion_gpu_wind_orbit_position: rc %d" % rc)
+    return tuple(out[:3])
