@@ -10,12 +10,11 @@
 #include <stdint.h>
 
 #include "dev_riemann.h"
+#include "rows_tiling.h"
 
 namespace pion {
 
 #define PION_MAX_NTR 2
-// LDS a workgroup of k_stage_rows2 may use so that two fit a CU (160 KiB)
-#define PION_ROWS2_LDS_BYTES (80 * 1024)
 #define PION_COOL_NT_MAX 256
 
 struct GridDesc {
@@ -41,28 +40,6 @@ struct CoolDev {
   float lg0, inv_dlg;
 };
 
-// Uneven plane chunks of a strip of np planes: chunk number cz covers [*k0, *k1) (relative to the strip); returns the
-// number of chunks.  A rule instead of a table in the kernel arguments: indexing an argument array with a run-time
-// index makes the compiler copy the whole argument struct to scratch memory (measured: the stage kernel 2x slower).
-__host__ __device__ inline int zchunk_bounds(const int np, const int cmax, const int cz, int *k0, int *k1)
-{
-  int n = 0, pos = 0;
-  *k0 = *k1 = np;
-  while (pos < np) {
-    const int rem = np - pos;
-    const int cmin = (np <= 128) ? 2 : 4;   // (a slab of a few dozen planes: its tail is a larger share of the launch)
-    int c = (rem > 2 * cmax) ? cmax : ((rem / 2 > cmin) ? rem / 2 : cmin);
-    if (c > cmax) c = cmax;
-    if (c > rem || rem - c < cmin) c = rem;
-    if (n == cz) {
-      *k0 = pos;
-      *k1 = pos + c;
-    }
-    pos += c;
-    n++;
-  }
-  return n;
-}
 struct StageArgs {
   GridDesc g;
   const double *S;    // stencil state ("Ph")      [nvar][ncell]
@@ -84,7 +61,7 @@ struct StageArgs {
   int zslope_lds;     // k_stage_rows2: carry the z slope in LDS (else rebuild it from plane k-1)
   double *dE;         // k_stage_rows2: cooling source PtoU(p_new)[ERG]-PtoU(P)[ERG] per cell from k_cooling_dE (or null)
   int zchunk;         // planes per wavefront in the marching kernels
-  // k_stage_rows2, first strip [kz0,kz1): nzb > 0 = uneven chunks (zchunk_bounds below: chunks of `zcmax` planes,
+  // k_stage_rows2, first strip [kz0,kz1): nzb > 0 = uneven chunks (zchunk_bounds, rows_tiling.h: chunks of `zcmax` planes,
   // then halving down to 4 -- long chunks first, short ones last: the launch's last wavefronts are short, so its
   // tail is), nzb of them
   int nzb, zcmax;
@@ -148,7 +125,6 @@ struct CoolTestArgs {
   namespace NS {                                                   \
   int launch_stage(const StageArgs &a, hipStream_t s);             \
   int launch_cooling_dE(const StageArgs &a, hipStream_t s);        \
-  int stage_rows2_rows(int eq, int ntr, int zslope_lds, int want); \
   int launch_prepass(const PrepassArgs &a, hipStream_t s);         \
   int launch_dt(const DtArgs &a, hipStream_t s);                   \
   int launch_dt_mp(const DtArgs &a, hipStream_t s);                \

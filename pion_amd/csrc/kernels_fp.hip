@@ -84,15 +84,6 @@ PDEV double sph_Rcom(const double R, const double dR)
   return R * (1.0 + 0.25 * delta2) / (1.0 + delta2 / 12.0);
 }
 
-// XCD-aware tile decode: workgroups are dealt round-robin to the 8 XCDs (b % 8 share an XCD);
-// give each XCD a contiguous range of tiles so that the halo re-reads of neighbouring tiles hit
-// the same L2.  Placement only changes speed, never results.
-PDEV long xcd_tile(const long b, const long ntiles)
-{
-  const long chunk = (ntiles + 7) / 8;
-  return (b % 8) * chunk + (b / 8);
-}
-
 // rotate the three vector components between the lab frame and the sweep frame
 template <int NV, bool MHD>
 PDEV void to_sweep(const int ax, const double *lab, double *sw)
@@ -589,7 +580,6 @@ __global__ __launch_bounds__(256) void k_flux_test(const FluxTestArgs a)
 }
 
 #include "stage_helpers.h"
-#include "rows_tiling.h"
 #include "stage_rows2.h"
 
 // ---------------------------------------------------------------------------
@@ -782,27 +772,6 @@ int launch_cooling_dE(const StageArgs &a, hipStream_t s)
   if (a.eqntype == EQMHD) return launch_cooling_dE_mhd(a, s);
   if (a.eqntype == EQGLM) return launch_cooling_dE_glm(a, s);
   return -1;
-}
-// rows per wavefront k_stage_rows2 will use (LDS budget), for the host's launch cost model
-int stage_rows2_rows(int eq, int ntr, int zslope_lds, int want)
-{
-  const int nv = ((eq == EQEUL) ? 5 : ((eq == EQMHD) ? 8 : 9)) + ntr;
-  const int nz = zslope_lds ? 2 * nv : nv;
-  int r = (int)(PION_ROWS2_LDS_BYTES / (sizeof(double) * 4 * nz * 64));
-  if (r > 8) r = 8;
-  if (want <= 0) {
-    // automatic.  The MHD instances need the whole register file of two wavefronts per SIMD: as many rows as two
-    // workgroups' LDS allows (fewer Riemann solves per cell).  The Euler instances take ~160 registers, so a
-    // THIRD wavefront per SIMD fits if three workgroups' LDS does: rows for 160 KiB / 3 (measured at 512^3,
-    // second-order stage with 2 rows instead of 4: Roe-CV 13.8 -> 12.8 ms/step, FVS + tracer + cooling 25.9 -> 23.6)
-    if (eq == EQEUL) {
-      int r3 = (int)((160 * 1024 / 3) / (sizeof(double) * 4 * nz * 64));
-      if (r3 < 1) r3 = 1;
-      if (r3 < r) r = r3;
-    }
-  }
-  else if (want < r) r = want;
-  return r < 1 ? 1 : r;
 }
 int launch_flux_test(const FluxTestArgs &a, hipStream_t s)
 {

@@ -496,7 +496,7 @@ struct Handle {
   bool timing = false;
   std::vector<hipEvent_t> ev[4];
   double Mu_tot_over_kB = 0.0;
-  int use_march = 3, zchunk = 0, rows = 0;  // zchunk 0: chosen per launch; rows 0: chosen per instance (stage_rows2_rows)
+  int use_march = 3, zchunk = 0, rows = 0;  // zchunk 0: chosen per launch; rows 0: chosen per instance (rows2_plan, rows_tiling.h)
   int rows1 = 0;                            // rows of the first-order stage (PION_ROWS1)
   const double *xghost_fresh = nullptr;   // array whose x ghosts (periodic x) the last stage kernel wrote itself
   int zslope_lds = 1;     // k_stage_rows2: carry the z slope in LDS (default; PION_ZSLOPE_LDS=0: rebuild it from plane k-1, R = 4)
@@ -1913,8 +1913,6 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
   a.max_temp = cfg.max_temp;
   a.cool = h->cool;
   a.use_march = h->use_march;
-  a.rows = h->rows;
-  a.zchunk = h->zchunk;
   a.kz0 = kz0;
   a.kz1 = kz1;
   a.kz2 = kz2;
@@ -1925,80 +1923,31 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
   // periodic x: k_stage_rows2 writes the x ghost images of its rows (the boundary launch then skips them)
   a.xwrap = (a.use_march != 0 && h->fuse_bc && cfg.bc_type[0] == PION_BC_PERIODIC
              && cfg.bc_type[1] == PION_BC_PERIODIC && h->g.ng[0] >= 2 * h->g.nbc[0]) ? 1 : 0;
-  a.rows_auto = 0;
   a.ncu = h->ncu;
-  if (a.use_march != 0 && h->g.ndim == 2) {
-    // 2-D: rows per wavefront marched along y (nothing in LDS): 2 + 1/R solves per cell against the number of
-    // wavefronts (measured, 4096 x 1260 Euler Roe-CV / 4096 x 6144 GLM-MHD HLLD, Mcell-updates/s: R = 4 7694 / 5940,
-    // 8 11360 / 7711, 16 12686 / 8034, 32 13076 / 7371; the cell-per-thread kernel 4680 / 2176); fewer rows on
-    // small grids so that every slot still gets a wavefront (PION_ROWS overrides)
-    int r2 = 16;
-    {
-      const long ntx = (h->g.ng[0] + 61) / 62;
-      while (r2 > 2 && ntx * ((h->g.ng[1] + r2 - 1) / r2) < 8L * (h->ncu > 0 ? h->ncu : 256)) r2 /= 2;
-    }
-    a.rows = (h->rows > 0) ? h->rows : r2;
-    if (a.rows > 64) a.rows = 64;
-    // (without PION_ROWS the launcher refines the choice for the instance it launches: its occupancy decides how
-    // many wavefronts a "round" holds, stage_rows2.h rows2_pick_rows_2d)
-    a.rows_auto = (h->rows > 0) ? 0 : 1;
-  }
-  else if (a.use_march != 0)
-    a.rows = cfg.strict_fp ? fp_strict::stage_rows2_rows(cfg.eqntype, cfg.ntracer, a.zslope_lds && space_ooa == 2, space_ooa == 2 ? h->rows : h->rows1)
-                           : fp_fast::stage_rows2_rows(cfg.eqntype, cfg.ntracer, a.zslope_lds && space_ooa == 2, space_ooa == 2 ? h->rows : h->rows1);
-  if (a.zchunk <= 0) {
-    // Planes per wavefront.  Every wavefront takes (zchunk + 1 priming plane) plane visits and a CU holds 8
-    // wavefronts at a time; pick the chunk that minimises the launch cost model below.
-    int rows = a.rows;
-    if (rows < 1) rows = 1;
-    const int nyg = (h->g.ng[1] + rows - 1) / rows;
-    const int ntx_full = h->g.ng[0] / 62, rem = h->g.ng[0] - ntx_full * 62;
-    const int spw = (rem > 0) ? 64 / (rem + 2) : 0;
-    const long per_chunk = (long)ntx_full * nyg + ((rem > 0) ? (nyg + spw - 1) / spw : 0);
-    const long slots = 8L * (h->ncu > 0 ? h->ncu : 256);   // two workgroups of four wavefronts per CU
-    const int np = kz1 - kz0;
-    // cost in plane visits: wavefronts are dispatched as slots free up, so a launch takes about
-    // (all wave-visits) / slots plus a tail of half a wavefront's length; short chunks balance better, long
-    // chunks prime less (measured at 512^3: 16 and 32 planes 27.3 ms/step, 47: 28.4, 64: 28.0, 128: 31.7)
-    double best_cost = -1.0;
-    a.zchunk = 8;
-    for (int zc = 8; zc <= 128; zc++) {
-      const long nzc = (np + zc - 1) / zc;
-      const int longest = (zc < np ? zc : np) + 1;
-      const int last = np - (int)(nzc - 1) * zc;           // planes of the last chunk
-      if (nzc > 1 && 4 * last < 3 * zc) continue;          // a short last chunk unbalances the tail (22, 26: measured)
-      double cost = (double)per_chunk * (double)(np + nzc) / (double)slots + 0.5 * longest;
-      if (np % zc != 0) cost *= 1.005;                     // equal chunks first (512^3: 32 planes 25.5, 27 planes 25.8 ms/step)
-      if (best_cost < 0 || cost < best_cost) {
-        best_cost = cost;
-        a.zchunk = zc;
-      }
-    }
-  }
-  // Uneven chunks (default; PION_UNEVEN_CHUNKS=0: equal chunks of a.zchunk planes): chunks of the model's length
-  // while more than two of them remain, then halving down to 4 planes.  Wavefronts are dispatched in chunk order, so
-  // the last ones to start are the shortest and the launch ends with (nearly) all slots busy; a priming plane costs
-  // about a third of a plane visit (its z task only).  512 planes: 14 x 32, 32, 16, 8, 4, 4; a 64-plane slab:
-  // 32, 16, 8, 4, 4 (equal chunks: 3.25 ms/step for 512 x 512 x 64, 88 % of the per-cell rate of 512^3).
-  a.nzb = 0;
-  a.zcmax = 32;
-  if (h->zchunk > 0) a.zcmax = h->zchunk;
-  else if (a.use_march != 0) {
-    // longest chunk: at least ~4 wavefronts per slot over the launch (Euler instances run three workgroups per CU,
-    // the MHD ones two), between 8 and 32 planes (256^3 Euler: 11 planes; even chunks of the model 3.05 ms/step,
-    // uneven ones from 32 down 3.28)
-    int rows = a.rows < 1 ? 1 : a.rows;
-    const int nyg = (h->g.ng[1] + rows - 1) / rows;
-    const int ntx_full = h->g.ng[0] / 62, rem = h->g.ng[0] - ntx_full * 62;
-    const int spw = (rem > 0) ? 64 / (rem + 2) : 0;
-    const long per_chunk = (long)ntx_full * nyg + ((rem > 0) ? (nyg + spw - 1) / spw : 0);
-    const long slots = ((cfg.eqntype == PION_EQEUL) ? 12L : 8L) * (h->ncu > 0 ? h->ncu : 256);
-    long c = (long)(kz1 - kz0) * per_chunk / (4 * slots);
-    a.zcmax = (int)(c < 8 ? 8 : (c > 32 ? 32 : c));
-  }
-  if (a.use_march != 0 && h->uneven_chunks && kz1 - kz0 >= 16) {
-    int k0, k1;
-    a.nzb = zchunk_bounds(kz1 - kz0, a.zcmax, 0, &k0, &k1);
+  {
+    // rows per wavefront, plane chunks (rows_tiling.h; PION_ROWS / PION_ROWS1 / PION_ZCHUNK / PION_UNEVEN_CHUNKS
+    // override the choices)
+    Rows2PlanIn p;
+    p.ndim = h->g.ndim;
+    p.nx = h->g.ng[0];
+    p.ny = h->g.ng[1];
+    p.np = kz1 - kz0;
+    p.ncu = h->ncu;
+    p.nv = cfg.nvar;
+    p.euler = (cfg.eqntype == PION_EQEUL);
+    p.march = (a.use_march != 0);
+    p.zslope_lds = (a.zslope_lds != 0);
+    p.second_order = (space_ooa == 2);
+    p.uneven = h->uneven_chunks;
+    p.want_rows = h->rows;
+    p.want_rows1 = h->rows1;
+    p.want_zchunk = h->zchunk;
+    const Rows2Plan pl = rows2_plan(p);
+    a.rows = pl.rows;
+    a.rows_auto = pl.rows_auto;
+    a.zchunk = pl.zchunk;
+    a.zcmax = pl.zcmax;
+    a.nzb = pl.nzb;
   }
   if (cfg.cooling != 0 && a.use_march != 0) {
     // calc_noRT_microphysics_dU as its own launch (thread per cell, full occupancy): dE per cell

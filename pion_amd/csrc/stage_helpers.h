@@ -146,7 +146,4 @@ PDEV double wave_min64(double v)
   return v;
 }
 
-#define PION_MARCH_XT 62  // output cells per wavefront along x
-
-
 #endif

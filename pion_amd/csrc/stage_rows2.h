@@ -22,7 +22,7 @@
 //   * the first-order stage reads the start-of-step state from the stencil array (they are the same
 //     array in that stage), the cooling source arrives as one double per cell from k_cooling;
 //   * the Euler instances need ~160 registers: the host picks their rows per wavefront so that THREE workgroups'
-//     LDS fits a CU (stage_rows2_rows), and three wavefronts per SIMD run.
+//     LDS fits a CU (rows2_rows_3d, rows_tiling.h), and three wavefronts per SIMD run.
 // The arithmetic and its order are the reference's (the strict build stays bit-identical to the oracle).
 #ifndef PION_STAGE_ROWS2_H
 #define PION_STAGE_ROWS2_H
@@ -217,9 +217,6 @@ PDEV void apply_axis_cyl(double *d, const double *q0, const double bnm, const do
 #ifndef PION_ROWS2_PF
 #define PION_ROWS2_PF 1
 #endif
-#ifndef PION_ROWS2_YWG
-#define PION_ROWS2_YWG 1
-#endif
 // PION_ROWS2_COPIES=1: the x, y and z tasks of a row as three straight-line copies of the task body; 0: one body in
 // a uniform task loop (A/B)
 #ifndef PION_ROWS2_COPIES
@@ -254,6 +251,8 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
   const int nzc = nzc1 + (a.kz3 - a.kz2 + a.zchunk - 1) / a.zchunk;   // chunks of both strips
   // the wavefront number is uniform: say so, and the tile / row / plane loops run on the scalar unit
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  // (rows2_decode, rows_tiling.h, restates this decode for the tests' host-side coverage probe: kept inline here, because
+  // the kernel compiled from the shared function is not instruction for instruction the same -- keep the two equal)
   // Workgroup -> (x-y tile group, plane chunk).  Workgroups go to the XCDs round robin (blockIdx % 8): each XCD
   // takes an eighth of the x-y tiles -- y-adjacent row groups, whose halo rows are each other's own rows, share its
   // L2 -- through ALL plane chunks, in chunk order: with uneven chunks (long first) every XCD ends on the short ones.
@@ -906,9 +905,7 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
 template <int NV, bool ZSL>
 __host__ inline int rows2_rmax()
 {
-  constexpr int NZ = ZSL ? 2 * NV : NV;
-  int r = (int)(PION_ROWS2_LDS_BYTES / (sizeof(double) * 4 * NZ * 64));
-  return r > 8 ? 8 : r;
+  return rows2_rmax_lds(NV, ZSL);
 }
 
 // 2-D launches: rows per wavefront for THIS instance.  A 2-D launch is one to a few "rounds" of wavefronts (one
@@ -927,24 +924,7 @@ static int rows2_pick_rows_2d(const StageArgs &a)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, KERNEL, 256, 0) != hipSuccess || n < 1) n = 2;
     wg_per_cu = n;
   }
-  const long slots = 4L * wg_per_cu * (a.ncu > 0 ? a.ncu : 256);
-  int best = a.rows;
-  double best_score = -1.0;
-  StageArgs t = a;
-  // (a launch of many rounds is filled well enough at the caller's rows, and long columns cost it L2 locality:
-  // 4096 x 6144 GLM-MHD HLLD, 12.4 rounds at R = 16: 8340 Mcell-updates/s, R = 50 -- one round fewer -- 7350)
-  if ((rows_tiling(a).per_chunk + slots - 1) / slots > 3) return a.rows;
-  for (int R = 8; R <= 64; R++) {
-    t.rows = R;
-    const long waves = rows_tiling(t).per_chunk;
-    const long rounds = (waves + slots - 1) / slots;
-    const double score = ((double)waves / (double)(rounds * slots)) / (2.0 + 1.0 / R);
-    if (score > best_score * 1.0000001) {
-      best_score = score;
-      best = R;
-    }
-  }
-  return best;
+  return rows2_pick_rows_2d_rule(a.g.ng[0], a.g.ng[1], a.rows, wg_per_cu, a.ncu);
 }
 // one launch of an instance: rows per wavefront (2-D: picked here when the caller leaves the choice), grid, LDS
 template <void (*KERNEL)(const StageArgs)>
@@ -954,9 +934,7 @@ static int rows2_launch(StageArgs a, const int rmax, const size_t lds_bytes_per_
   if (noz && a.rows_auto) a.rows = rows2_pick_rows_2d<KERNEL>(a);
   if (a.rows > rmax) a.rows = rmax;
   if (a.rows < 1) a.rows = 1;
-  const int nzc = ((a.nzb > 0) ? a.nzb : (a.kz1 - a.kz0 + a.zchunk - 1) / a.zchunk) + (a.kz3 - a.kz2 + a.zchunk - 1) / a.zchunk;
-  const int nb4 = (rows_tiling(a).per_chunk + 3) / 4, nb8 = (nb4 + 7) / 8;
-  const long nblocks = 8L * nb8 * nzc;   // (see the kernel: an eighth of the x-y tiles per XCD, through all chunks)
+  const long nblocks = rows2_nblocks(a);   // (rows_tiling.h: an eighth of the x-y tiles per XCD, through all chunks)
   const size_t shmem = noz ? 0 : lds_bytes_per_row * a.rows;
   hipLaunchKernelGGL(KERNEL, dim3((unsigned)nblocks), dim3(256), shmem, s, a);
   return (int)hipGetLastError();
