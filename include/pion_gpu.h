@@ -173,7 +173,8 @@ int pion_gpu_set_wind_cells(void *handle, long n, const long *idx, const double 
 typedef struct pion_gpu_wind_source {
   double pos[PION_MAX_DIM];   /* source position, physical units (unused axes ignored) */
   double radius;              /* radius of the wind region, physical units (> 0) */
-  int type;                   /* 0 = constant, 1 = evolving (2, 3: angle / latitude-dependent: EINVAL) */
+  int type;                   /* 0 = constant, 1 = evolving (here 2, 3: EINVAL; 2 = rotating star, through
+                               * pion_gpu_add_rotating_wind_source; 3 = latitude-dependent: not supported) */
   double mdot;                /* Msun/yr   (constant: converted to g/s as add_source does, stellar_wind_BC.cpp:166-172) */
   double vinf, vrot;          /* km/s      (constant) */
   double Tw, Rstar, Bstar;    /* K, cm, G  (constant; Bstar also for evolving sources) */
@@ -218,6 +219,22 @@ int pion_gpu_get_flags(void *handle, unsigned char *out);
  * BC_update_STWIND computes it (src->pos for orbit_period == 0).  Host only: needs no device or handle.  EINVAL for
  * ndim outside 2..3 or a NULL pointer. */
 int pion_gpu_wind_orbit_position(const pion_gpu_wind_source *src, int ndim, double simtime, double *pos);
+/* WINDTYPE_ANGLE (type 2): the rotating star of Langer, Garcia-Segura & Mac Low (1999), grid/stellar_wind_angle.cpp
+ * (add_evolving_source :700, add_rotating_source :836, update_source :941, set_wind_cell_reference_state :464).
+ * src->type must be 2; the evolving-table fields carry the table as for type 1 (cgs, times offset and scaled) and
+ * evo_vcrit its vcrit column (npt rows); Bstar, tracers, evo_tracer_elem, t_now and update_freq as for type 1.
+ * Membership, flags, id order and pion_gpu_get_wind_cells as for the other sources.  xi = WIND_i_xi, the exponent
+ * of the equatorial enhancement; the LGM99 tables are built for it at the first rotating source of the handle.
+ * EINVAL: a 1-D grid, a source off the axis (cylindrical), orbit_period != 0, npt < 2, radius <= 0, a NULL column,
+ * an xi other than an earlier rotating source's, an evolving (type 1) source on the same handle (either order;
+ * constant sources may sit beside rotating ones), more than PION_MAX_WIND_SOURCES sources, or a member cell whose
+ * polar angle lies outside (0.1 deg, 89.9 deg] -- e.g. a source on a plane of cell centres (theta = 90 deg). */
+int pion_gpu_add_rotating_wind_source(void *handle, const pion_gpu_wind_source *src, const double *evo_vcrit,
+                                      double xi, int *id);
+/* stellar_wind_angle::setup_tables (stellar_wind_angle.cpp:92-212) for `xi`, in plain double: theta[25] (rad),
+ * omega[25], Teff[22] (K), delta[25][22] (omega, Teff) and alpha[25][25][22] (omega, theta, Teff); NULL arrays are
+ * skipped.  Host only: needs no device or handle. */
+int pion_gpu_wind_angle_tables(double xi, double *theta, double *omega, double *Teff, double *delta, double *alpha);
 /* The cells of source `id` in cell-id order and the states (n*nvar doubles, cell-major) the last boundary update
  * wrote (zeros before the first one, or while an evolving source is inactive).  *n = number of cells; idx ==
  * NULL: size query only; states may be NULL.  For a moving source: its current cells (synchronises the stream). */
@@ -244,7 +261,9 @@ int pion_gpu_set_cooling_tables(void *handle, int nT, const double *T,
 /* assign_update_bcs::TimeUpdateInternalBCs + TimeUpdateExternalBCs
  * (boundaries/assign_update_bcs.cpp:134-252): fills ghost cells of Ph, and of
  * P too when cstep==maxstep.  Internal boundaries first: the set_wind_cells list, then the wind sources of
- * pion_gpu_add_wind_source at `simtime` (written to P and Ph), then the external faces.  `assign`!=0 additionally captures the constant
+ * pion_gpu_add_wind_source at `simtime` (written to P and Ph), then the external faces.
+ * EINVAL, with nothing written, when an active rotating source (pion_gpu_add_rotating_wind_source) would write
+ * with omega = min(v_rot/vcrit, 0.999) <= 0 or Tw <= 1000 K at `simtime`: the reference's look-up stops there.  `assign`!=0 additionally captures the constant
  * inflow/fixed reference states from P (BC_assign_*, inflow_boundaries.cpp,
  * fixed_boundaries.cpp) and must be used for the first call after upload. */
 int pion_gpu_update_bcs(void *handle, double simtime, int cstep, int maxstep, int assign);

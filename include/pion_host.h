@@ -41,6 +41,11 @@ int pion_host_sim_set_comm(void *sim, void *comm);            /* before pion_hos
  * km/s, 0 = no limit), combined by min with init's first_step_dt_limit.  EINVAL on a backend other than
  * libpion_gpu.so. */
 int pion_host_sim_add_wind_source(void *sim, const pion_gpu_wind_source *src, int *id);
+/* The same for a rotating star (pion_gpu_add_rotating_wind_source: type 2, the table's vcrit column, xi), with the
+ * same first-step limit.  A boundary update the source cannot evaluate (omega <= 0 or Tw <= 1000 K at that time:
+ * pion_gpu_update_bcs returns EINVAL) stops pion_host_sim_time_int with -1 and the text in pion_host_sim_last_error. */
+int pion_host_sim_add_rotating_wind_source(void *sim, const pion_gpu_wind_source *src, const double *evo_vcrit,
+                                           double xi, int *id);
 int pion_host_sim_last_error(void *sim, char *buf, int len);
 
 /* ---- z-slab communicators (both return a pion_host::slab_comm*) */

@@ -97,9 +97,19 @@ __global__ __launch_bounds__(256) void k_wind_count(const WindMember m, unsigned
   if (threadIdx.x == 0 && n) atomicAdd(count, (unsigned long long)n);
 }
 
-// per member cell: keep dist and the per-axis offsets, mark it boundary data (stellar_wind_BC.cpp:277-278)
+// stellar_wind::add_cell's polar angle (stellar_wind_BC.cpp:286-318) from the offsets: 1-D 0, 2-D atan(|R / z|)
+// (Rcyl = y, Zcyl = x), 3-D atan(|sqrt(x^2 + y^2) / z|)
+__device__ inline double wind_theta(const int ndim, const WindGeo &w)
+{
+#pragma clang fp contract(off)
+  if (ndim == 1) return 0.0;
+  if (ndim == 2) return atan(fabs(w.y / w.x));
+  return atan(fabs(sqrt(w.x * w.x + w.y * w.y) / w.z));
+}
+
+// per member cell: keep dist, the per-axis offsets and theta, mark it boundary data (stellar_wind_BC.cpp:277-278)
 __global__ __launch_bounds__(256) void k_wind_cells(const WindMember m, const long *idx, const long n, double *dist,
-                                                    double *off, const long ntot, uint8_t *flags)
+                                                    double *off, double *theta, const long ntot, uint8_t *flags)
 {
   const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
@@ -109,6 +119,7 @@ __global__ __launch_bounds__(256) void k_wind_cells(const WindMember m, const lo
   off[k] = w.x;
   off[ntot + k] = w.y;
   off[2 * ntot + k] = w.z;
+  theta[k] = wind_theta(m.g.ndim, w);
   flags[c] = (uint8_t)((flags[c] | PION_CELL_ISBD) & ~PION_CELL_ISDOMAIN);
 }
 
@@ -281,6 +292,161 @@ __global__ __launch_bounds__(256) void k_wind_state(const WindStateArgs a, const
   for (int v = 0; v < a.ntracer && v < PION_MAX_NTR; v++) p[ftr + v] = W.tr[v];
   // SET_NEGATIVE_PRESSURE_TO_FIXED_TEMPERATURE (:578-590): mp_only_cooling::Temperature / Set_Temp
   // (mp_only_cooling.cpp:244-280) with a microphysics object, else a neutral-gas floor
+  if (a.cooling) {
+    if (p[1] * a.Mu_tot_over_kB / p[0] < a.Tmin) p[1] = p[0] * a.Tmin / a.Mu_tot_over_kB;
+  }
+  else {
+    const double floor_p = a.Tmin * p[0] * kB * 0.78625 / m_p;
+    p[1] = (p[1] < floor_p) ? floor_p : p[1];
+  }
+  const long c = a.idx[k];
+  for (int v = 0; v < a.nvar; v++) {
+    a.P[v * a.ncell + c] = p[v];
+    a.Ph[v * a.ncell + c] = p[v];
+    a.states[k * a.nvar + v] = p[v];
+  }
+}
+
+// ---- rotating stars, LGM99 (grid/stellar_wind_angle.cpp, WINDTYPE_ANGLE) ---------------------------------------
+// The knots of stellar_wind_angle::setup_tables (:92-212)
+#define PION_ANGLE_NTHETA 25
+#define PION_ANGLE_NOMEGA 25
+#define PION_ANGLE_NTEFF 22
+
+// member cells of a rotating source whose theta lies outside (lo, hi]: root_find_trilinear_vec (tools/interpolate.cpp
+// :385-470) calls rep.error below theta_vec[0] (NaN included) and runs past the vector above theta_vec[24]
+__global__ __launch_bounds__(256) void k_wind_theta_bad(const WindMember m, const double lo, const double hi,
+                                                        unsigned long long *count)
+{
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  int bad = 0;
+  if (c < m.g.ncell) {
+    const WindGeo w = wind_geo(m.g, m.pos, c);
+    if (w.d <= m.radius) {
+      const double t = wind_theta(m.g.ndim, w);
+      bad = !(t > lo && t <= hi);
+    }
+  }
+  const int n = __syncthreads_count(bad);
+  if (threadIdx.x == 0 && n) atomicAdd(count, (unsigned long long)n);
+}
+
+// One rotating source at the time of the update.  Everything that does not depend on the cell comes from the host:
+// omega = min(min(0.9999, v_rot/vcrit), 0.999), delta_interp (root_find_bilinear_vec), the omega and Teff fractions
+// of root_find_trilinear_vec, and its alpha table at the omega and Teff brackets over all theta knots:
+// a[0] = alpha[x0][*][z0], a[1] = alpha[x0][*][z1], a[2] = alpha[x1][*][z0], a[3] = alpha[x1][*][z1].
+struct WindAngleDev {
+  double Mdot, Vinf, v_rot, Tw, Rstar, Bstar, radius;
+  double omega, delta, xi, dx, dz;
+  double theta[PION_ANGLE_NTHETA];
+  double a[4][PION_ANGLE_NTHETA];
+  double tr[PION_MAX_NTR];
+  long off, n;
+};
+
+struct WindAngleArgs {
+  double *P, *Ph, *states;
+  const long *idx;
+  const double *dist, *off, *theta;
+  long ntot, ncell;
+  int nvar, ntracer, ndim, eqntype, cooling;
+  double Tmin, Mu_tot_over_kB;
+  WindAngleDev s;
+};
+
+// stellar_wind_angle::set_wind_cell_reference_state (stellar_wind_angle.cpp:464-691) for one cell of a 2-D or 3-D
+// grid, then set_cell_values: the state goes to P and Ph.  fn_density_interp (:386-455) is evaluated at dist and at
+// Rstar with the same alpha and delta; fn_v_inf (:343-353).  Expression order as in the reference; pow_fast(a, b) =
+// exp(b*log(a)).  One launch per active rotating source, in id order with the k_wind_state launches.
+__global__ __launch_bounds__(256) void k_wind_state_angle(const WindAngleArgs a)
+{
+#pragma clang fp contract(off)
+  const WindAngleDev &W = a.s;
+  const long k0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k0 >= W.n) return;
+  const long k = W.off + k0;
+  const double gamma = 5. / 3., c_gamma = 0.35;
+  const double kB = 1.38064852e-16, m_p = 1.672621898e-24, pi = 3.14159265358979324;
+  const double dist = a.dist[k];
+  const double x = a.off[k], y = a.off[a.ntot + k], z = a.off[2 * a.ntot + k];
+  const double theta = a.theta[k];
+  // root_find_trilinear_vec in theta: while (y > y_vec[j]) j++; set-up keeps theta in (theta_vec[0], theta_vec[24]]
+  int j = 1;
+  while (j < PION_ANGLE_NTHETA - 1 && theta > W.theta[j]) j++;
+  const double dy = (theta - W.theta[j - 1]) / (W.theta[j] - W.theta[j - 1]);
+  const double f000 = W.a[0][j - 1], f001 = W.a[1][j - 1], f010 = W.a[0][j], f100 = W.a[2][j - 1];
+  const double f110 = W.a[2][j], f011 = W.a[1][j], f101 = W.a[3][j - 1], f111 = W.a[3][j];
+  const double c0 = f000;
+  const double c1 = f100 - f000;
+  const double c2 = f010 - f000;
+  const double c3 = f001 - f000;
+  const double c4 = f110 - f010 - f100 + f000;
+  const double c5 = f011 - f001 - f010 + f000;
+  const double c6 = f101 - f001 - f100 + f000;
+  const double c7 = f111 - f011 - f101 - f110 + f100 + f001 + f010 - f000;
+  const double dx = W.dx, dz = W.dz;
+  const double alpha = c0 + c1 * dx + c2 * dy + c3 * dz + c4 * dx * dy + c5 * dy * dz + c6 * dz * dx + c7 * dx * dy * dz;
+  const double sint = sin(theta);
+  const double fxi = exp(W.xi * log(1.0 - W.omega * sint));
+  // fn_v_inf: std::max(0.5e5, v_inf pow_fast(1 - omega sin(theta), c_gamma))
+  double Vinf = W.Vinf * exp(c_gamma * log(1.0 - W.omega * sint));
+  Vinf = (0.5e5 < Vinf) ? Vinf : 0.5e5;
+  double p[PION_MAX_NVAR];
+  bool set_rho = true;
+  if (dist < 0.75 * W.radius && a.ndim > 1) {
+    p[0] = 1.0e-31;
+    p[1] = 1.0e-31;
+    set_rho = false;
+  }
+  if (set_rho) {
+    p[0] = (W.Mdot * alpha * W.delta * fxi);
+    p[0] /= (8.0 * pi * exp(2.0 * log(dist)) * Vinf);
+    double rho_s = (W.Mdot * alpha * W.delta * fxi);
+    rho_s /= (8.0 * pi * exp(2.0 * log(W.Rstar)) * Vinf);
+    p[1] = W.Tw * kB / m_p;
+    p[1] *= exp((1.0 - gamma) * log(rho_s));
+    p[1] *= exp(gamma * log(p[0]));
+  }
+  // velocities (:546-577): no rotation term in 2-D; J along +z in 3-D
+  p[2] = Vinf * x / dist;
+  p[3] = Vinf * y / dist;
+  if (a.ndim == 2) {
+    p[4] = 0.0;
+  }
+  else {
+    p[4] = Vinf * z / dist;
+    p[2] += -W.v_rot * W.Rstar * y / exp(2.0 * log(dist));
+    p[3] += W.v_rot * W.Rstar * x / exp(2.0 * log(dist));
+  }
+  // split monopole + toroidal field (:584-638) with the latitude-dependent Vinf
+  if (a.eqntype != PION_EQEUL) {
+    const double B_s = W.Bstar / sqrt(4.0 * pi);
+    const double D_s = W.Rstar / dist;
+    const double D_2 = D_s * D_s;
+    double beta_B_sint = (W.v_rot / Vinf) * B_s * D_s;
+    if (a.ndim == 2) {
+      p[5] = B_s * D_2 * fabs(x) / dist;
+      p[6] = B_s * D_2 / dist;
+      p[6] = (x > 0.0) ? y * p[6] : -y * p[6];
+      beta_B_sint = beta_B_sint * y / dist;
+      p[7] = (x > 0.0) ? -beta_B_sint : beta_B_sint;
+    }
+    else {
+      p[5] = B_s * D_2 / dist;
+      p[5] = (z > 0.0) ? x * p[5] : -x * p[5];
+      p[6] = B_s * D_2 / dist;
+      p[6] = (z > 0.0) ? y * p[6] : -y * p[6];
+      p[7] = B_s * D_2 * fabs(z) / dist;
+      beta_B_sint *= sqrt(x * x + y * y) / dist;
+      beta_B_sint = (z > 0.0) ? -beta_B_sint : beta_B_sint;
+      p[5] += -beta_B_sint * y / dist;
+      p[6] += beta_B_sint * x / dist;
+    }
+    if (a.eqntype == PION_EQGLM) p[8] = 0.0;
+  }
+  const int ftr = a.nvar - a.ntracer;
+  for (int v = 0; v < a.ntracer && v < PION_MAX_NTR; v++) p[ftr + v] = W.tr[v];
+  // SET_NEGATIVE_PRESSURE_TO_FIXED_TEMPERATURE (:661-675), as in k_wind_state
   if (a.cooling) {
     if (p[1] * a.Mu_tot_over_kB / p[0] < a.Tmin) p[1] = p[0] * a.Tmin / a.Mu_tot_over_kB;
   }

@@ -420,6 +420,14 @@ __global__ void k_halo(double *A, double *buf, const GridDesc g, const int nvar,
   else A[v * g.ncell + c] = buf[t];
 }
 
+// stellar_wind_angle's look-up tables for one xi (setup_tables, grid/stellar_wind_angle.cpp:92-212)
+struct AngleTables {
+  double xi = 0.0;
+  double theta[PION_ANGLE_NTHETA], omega[PION_ANGLE_NOMEGA], Teff[PION_ANGLE_NTEFF];
+  std::vector<double> delta;   // [omega][Teff]
+  std::vector<double> alpha;   // [omega][theta][Teff]
+};
+
 // one pion_gpu_add_wind_source source: its table, the parameters the next boundary update writes with, and the
 // activity bookkeeping of stellar_wind_evolution (evolving_wind_data: tstart, tfinish, t_next_update, is_active)
 struct WindSource {
@@ -427,8 +435,10 @@ struct WindSource {
   double pos[3] = {0.0, 0.0, 0.0};
   double radius = 0.0, Bstar = 0.0;
   std::vector<double> t, Teff, Mdot, vrot, vinf, R, X[7];
+  std::vector<double> vcrit;   // rotating source (type 2): the vcrit column
   int elem[PION_MAX_NVAR];
   double Mdot_c = 0.0, Vinf_c = 0.0, vrot_c = 0.0, Tw_c = 0.0, Rstar_c = 0.0;   // wind_source members, cgs
+  double vcrit_c = 0.0;
   double tr[PION_MAX_NVAR];
   bool active = true;
   double tstart = 0.0, tfinish = 0.0, t_next_update = 1.0e99;
@@ -482,6 +492,10 @@ struct Handle {
   long nws = 0;              // cells of all sources
   long *dws_idx = nullptr;
   double *dws_dist = nullptr, *dws_off = nullptr, *dws_state = nullptr;   // off: [3][nws]; state: [nws][nvar]
+  double *dws_theta = nullptr;   // stellar_wind::add_cell's theta (fixed sources; read by rotating ones)
+  // rotating sources (pion_gpu_add_rotating_wind_source): the LGM99 tables, built at the first one, for its xi
+  bool have_angle = false;
+  AngleTables angle;
   // cooling
   CoolDev cool;
   double *dcoolT = nullptr, *dcooltab = nullptr, *dcoolslope = nullptr;
@@ -637,10 +651,12 @@ static int wind_lists_grow(Handle *h, const long n)
   const long o = h->nws, ntot = o + n;
   const int nvar = h->cfg.nvar;
   long *nidx = nullptr;
-  double *ndist = nullptr, *noff = nullptr, *nstate = nullptr;
+  double *ndist = nullptr, *noff = nullptr, *nstate = nullptr, *ntheta = nullptr;
   if (ntot > 0) {
     HCHECK(h, hipMalloc(&nidx, sizeof(long) * ntot));
     HCHECK(h, hipMalloc(&ndist, sizeof(double) * ntot));
+    HCHECK(h, hipMalloc(&ntheta, sizeof(double) * ntot));
+    HCHECK(h, hipMemsetAsync(ntheta, 0, sizeof(double) * ntot, h->stream));
     HCHECK(h, hipMalloc(&noff, sizeof(double) * 3 * ntot));
     HCHECK(h, hipMalloc(&nstate, sizeof(double) * ntot * nvar));
     HCHECK(h, hipMemsetAsync(nstate, 0, sizeof(double) * ntot * nvar, h->stream));
@@ -648,6 +664,7 @@ static int wind_lists_grow(Handle *h, const long n)
   if (o > 0) {
     HCHECK(h, hipMemcpyAsync(nidx, h->dws_idx, sizeof(long) * o, hipMemcpyDeviceToDevice, h->stream));
     HCHECK(h, hipMemcpyAsync(ndist, h->dws_dist, sizeof(double) * o, hipMemcpyDeviceToDevice, h->stream));
+    HCHECK(h, hipMemcpyAsync(ntheta, h->dws_theta, sizeof(double) * o, hipMemcpyDeviceToDevice, h->stream));
     for (int a = 0; a < 3; a++)
       HCHECK(h, hipMemcpyAsync(noff + a * ntot, h->dws_off + a * o, sizeof(double) * o, hipMemcpyDeviceToDevice,
                                h->stream));
@@ -658,7 +675,9 @@ static int wind_lists_grow(Handle *h, const long n)
   hipFree(h->dws_dist);
   hipFree(h->dws_off);
   hipFree(h->dws_state);
+  hipFree(h->dws_theta);
   h->dws_idx = nidx;
+  h->dws_theta = ntheta;
   h->dws_dist = ndist;
   h->dws_off = noff;
   h->dws_state = nstate;
@@ -687,6 +706,159 @@ static void wind_orbit_position(const pion_gpu_wind_source &s, const int ndim, c
   pos[0] = s.pos[0] - a * cos_a + cos_a * a * cos_t - sin_a * b * sin_t;
   pos[1] = s.pos[1] - a * sin_a + sin_a * a * cos_t + cos_a * b * sin_t;
 }
+
+// ---- rotating stars, LGM99 (grid/stellar_wind_angle.cpp): the tables of setup_tables (:92-212) and the fn_*
+// functions, in plain double, the reference's expressions in their order (no contraction).  pconst.pi(), sqrt2()
+// are constants.h:45,48; pow_fast(a, b) = exp(b*log(a)) (constants.cpp:78-84); ONE_MINUS_EPS = 1 - 1e-12
+// (constants.h:157).  c_gamma = 0.35, c_beta = -1 (unused), c_xi = xi (:58-63).  The tables are AngleTables.
+
+namespace lgm99 {
+const double pi = 3.14159265358979324, sqrt2 = 1.4142135623730950, c_gamma = 0.35;
+
+static double pow_fast(const double a, const double b) { return exp(b * log(a)); }
+
+// stellar_wind::beta (stellar_wind_BC.cpp:820-867)
+static double beta(const double Teff)
+{
+#pragma clang fp contract(off)
+  const double rsg = 0.125;
+  if (Teff <= 3600.0) return rsg;
+  if (Teff >= 22000.0) return 2.6;
+  double b0, b1, T0, T1;
+  if (Teff < 6000.0) {
+    T0 = 3600.0; b0 = rsg; T1 = 6000.0; b1 = 0.5;
+  }
+  else if (Teff < 8000.0) {
+    T0 = 6000.0; b0 = 0.5; T1 = 8000.0; b1 = 0.7;
+  }
+  else if (Teff < 10000.0) {
+    T0 = 8000.0; b0 = 0.7; T1 = 10000.0; b1 = 1.3;
+  }
+  else if (Teff < 20000.0) {
+    T0 = 10000.0; b0 = 1.3; T1 = 20000.0; b1 = 1.3;
+  }
+  else {
+    T0 = 20000.0; b0 = 1.3; T1 = 22000.0; b1 = 2.6;
+  }
+  return b0 + (Teff - T0) * (b1 - b0) / (T1 - T0);
+}
+
+// fn_phi (:286-294)
+static double fn_phi(const double omega, const double theta, const double Teff)
+{
+#pragma clang fp contract(off)
+  const double ans = (omega / (22.0 * sqrt2 * beta(Teff))) * sin(theta) * pow_fast(1.0 - omega * sin(theta), -c_gamma);
+  const double cap = 0.5 * pi * (1.0 - 1.0e-12);
+  return (cap < ans) ? cap : ans;   // std::min(ans, cap)
+}
+
+// fn_alpha (:304-315)
+static double fn_alpha(const double omega, const double theta, const double Teff)
+{
+#pragma clang fp contract(off)
+  return pow_fast(cos(fn_phi(omega, theta, Teff)) + pow_fast(tan(theta), -2.0) *
+                                                        (1.0 + c_gamma * (omega * sin(theta) / (1.0 - omega * sin(theta)))) *
+                                                        fn_phi(omega, theta, Teff) * sin(fn_phi(omega, theta, Teff)),
+                  -1.0);
+}
+
+// integrand (:222-229), integrate_Simpson (:239-276), fn_delta (:325-333)
+static double integrand(const double theta, const double omega, const double Teff, const double xi)
+{
+#pragma clang fp contract(off)
+  return fn_alpha(omega, theta, Teff) * pow_fast(1.0 - omega * sin(theta), xi) * sin(theta);
+}
+
+static double fn_delta(const double omega, const double Teff, const double xi)
+{
+#pragma clang fp contract(off)
+  const double min = 0.001, max = pi / 2.0;
+  const long npt = 230;
+  const double hh = (max - min) / npt;
+  double ans = 0.0;
+  ans += integrand(min, omega, Teff, xi);
+  ans += integrand(max, omega, Teff, xi);
+  int wt = 4;
+  double x = 0.0;
+  for (long i = 1; i < npt; i++) {
+    x = min + i * hh;
+    ans += wt * integrand(x, omega, Teff, xi);
+    wt = 6 - wt;
+  }
+  ans *= hh / 3.0;
+  return 2.0 * pow_fast(ans, -1.0);
+}
+
+// setup_tables (:92-212)
+static void setup_tables(const double xi, AngleTables &T)
+{
+#pragma clang fp contract(off)
+  T.xi = xi;
+  const int nth = PION_ANGLE_NTHETA, nom = PION_ANGLE_NOMEGA, nT = PION_ANGLE_NTEFF;
+  const double theta_min = 0.1, theta_mid = 60.0, theta_max = 89.9;
+  for (int k = 0; k < nth; k++) {
+    if (k <= 4) T.theta[k] = (theta_min + k * ((theta_mid - theta_min) / 4.0)) * (pi / 180.0);
+    else T.theta[k] = (theta_mid + (k - 4) * ((theta_max - theta_mid) / (nth - 5))) * (pi / 180.0);
+  }
+  double log_mu[PION_ANGLE_NOMEGA];
+  for (int i = 0; i < nom; i++) log_mu[nom - i - 1] = -4.0 + i * (4.0 / (nom - 1));
+  for (int j = 0; j < nom; j++) T.omega[j] = 1 - pow_fast(10, log_mu[j]);
+  const double T0 = 1000.0, T1 = 3600.0, T2 = 6000.0, T3 = 8000.0, T4 = 10000.0, T5 = 20000.0, T6 = 22000.0,
+               T7 = 150000.0;
+  for (int i = 0; i < nT; i++) {
+    if (i == 0) T.Teff[i] = T0;
+    if (i == 1) T.Teff[i] = T1;
+    if (2 <= i && i <= 6) T.Teff[i] = T1 + i * ((T2 - T1) / 6);
+    if (i == 7) T.Teff[i] = T2;
+    if (8 <= i && i <= 10) T.Teff[i] = T2 + (i - 6) * ((T3 - T2) / 4);
+    if (i == 11) T.Teff[i] = T3;
+    if (12 <= i && i <= 14) T.Teff[i] = T3 + (i - 10) * ((T4 - T3) / 4);
+    if (i == 15) T.Teff[i] = T4;
+    if (i == 16) T.Teff[i] = T5;
+    if (17 <= i && i <= 19) T.Teff[i] = T5 + (i - 15) * ((T6 - T5) / 4);
+    if (i == 20) T.Teff[i] = T6;
+    if (i == 21) T.Teff[i] = T7;
+  }
+  T.delta.assign((size_t)nom * nT, 0.0);
+  for (int i = 0; i < nom; i++)
+    for (int j = 0; j < nT; j++) T.delta[(size_t)i * nT + j] = fn_delta(T.omega[i], T.Teff[j], xi);
+  T.alpha.assign((size_t)nom * nth * nT, 0.0);
+  for (int i = 0; i < nom; i++)
+    for (int j = 0; j < nth; j++)
+      for (int k = 0; k < nT; k++) T.alpha[((size_t)i * nth + j) * nT + k] = fn_alpha(T.omega[i], T.theta[j], T.Teff[k]);
+}
+
+// interpolate_arrays::root_find_bilinear_vec (tools/interpolate.cpp:300-380) on delta(omega, Teff)
+static double delta_interp(const AngleTables &T, const double xr, const double yr)
+{
+#pragma clang fp contract(off)
+  const double *x = T.omega, *y = T.Teff;
+  size_t ihi = PION_ANGLE_NOMEGA - 1, jhi = PION_ANGLE_NTEFF - 1, ilo = 0, jlo = 0, imid = 0, jmid = 0;
+  do {
+    imid = ilo + (size_t)floor((ihi - ilo) / 2.0);
+    if (x[imid] < xr) ilo = imid;
+    else ihi = imid;
+  } while (ihi - ilo > 1);
+  do {
+    jmid = jlo + (size_t)floor((jhi - jlo) / 2.0);
+    if (y[jmid] < yr) jlo = jmid;
+    else jhi = jmid;
+  } while (jhi - jlo > 1);
+  double xval, yval;
+  if (xr > x[ihi]) xval = x[ihi];
+  else if (xr < x[ilo]) xval = x[ilo];
+  else xval = xr;
+  if (yr > y[jhi]) yval = y[jhi];
+  else if (yr < y[jlo]) yval = y[jlo];
+  else yval = yr;
+  const size_t nT = PION_ANGLE_NTEFF;
+  const std::vector<double> &f = T.delta;
+  double result = (f[ilo * nT + jlo] * (x[ihi] - xval) * (y[jhi] - yval) + f[ihi * nT + jlo] * (xval - x[ilo]) * (y[jhi] - yval) +
+                   f[ilo * nT + jhi] * (x[ihi] - xval) * (yval - y[jlo]) + f[ihi * nT + jhi] * (xval - x[ilo]) * (yval - y[jlo]));
+  result /= ((x[ihi] - x[ilo]) * (y[jhi] - y[jlo]));
+  return result;
+}
+}  // namespace lgm99
 
 // The box of moving source W centred on `pos`: per axis the w cells from one below the first cell whose centre can
 // lie within the radius (the exact test runs in the kernels).  A NaN position gives some box; no cell passes there.
@@ -812,9 +984,111 @@ static int wind_sources_move(Handle *h, const double simtime)
   return 0;
 }
 
-// stellar_wind_evolution::set_cell_values (stellar_wind_BC.cpp:1334-1372) and update_source (:1250-1330) for every
-// source, then one launch per active source, in id order, that writes the reference states of its cells (no host
-// synchronisation: the parameters are scalars of the host, the launch carries them)
+// omega of a rotating source: fn_density_interp's std::min(std::min(0.9999, v_rot/vcrit), 0.999)
+// (stellar_wind_angle.cpp:395, :493); fn_v_inf's clip (:350) gives the same value
+static double angle_omega(const double vrot, const double vcrit)
+{
+  const double r = vrot / vcrit;
+  const double o = (r < 0.9999) ? r : 0.9999;
+  return (0.999 < o) ? 0.999 : o;
+}
+
+// The values a rotating source writes with at simtime (update_source, stellar_wind_angle.cpp:941-1019, when it is
+// due), without changing the source.  false: the source does not write.
+static bool angle_values_at(const Handle *h, const WindSource &W, const double simtime, double *Tw, double *omega)
+{
+  const bool due = simtime >= W.t_next_update;
+  if (!(W.active || due)) return false;
+  double tw = W.Tw_c, vrot = W.vrot_c, vcrit = W.vcrit_c;
+  if (due) {
+    const double T = root_find_linear_vec(W.t, W.Teff, simtime), Tmax = h->angle.Teff[PION_ANGLE_NTEFF - 1];
+    tw = (Tmax < T) ? Tmax : T;
+    vrot = root_find_linear_vec(W.t, W.vrot, simtime);
+    vcrit = root_find_linear_vec(W.t, W.vcrit, simtime);
+  }
+  *Tw = tw;
+  *omega = angle_omega(vrot, vcrit);
+  return true;
+}
+
+// Before any launch of a boundary update: root_find_trilinear_vec calls rep.error for omega <= omega_vec[0] and
+// Teff <= Teff_vec[0] (tools/interpolate.cpp:420-440), so a rotating source that would write with such values
+// makes the update EINVAL, with nothing written.
+static int wind_angle_check(Handle *h, const double simtime)
+{
+  for (size_t s = 0; s < h->wsrc.size(); s++) {
+    const WindSource &W = h->wsrc[s];
+    double Tw, omega;
+    if (W.type != 2 || !angle_values_at(h, W, simtime, &Tw, &omega)) continue;
+    if (!(omega > h->angle.omega[0]) || !(Tw > h->angle.Teff[0])) {
+      h->err = "rotating wind source: omega <= 0 or Tw <= 1000 K (stellar_wind_angle look-up out of range)";
+      return PION_GPU_EINVAL;
+    }
+  }
+  return 0;
+}
+
+// k_wind_state_angle's launch for rotating source W: the parts of fn_density_interp that do not depend on the cell
+static void wind_angle_launch(Handle *h, const WindSource &W, const WindStateArgs &a)
+{
+#pragma clang fp contract(off)
+  const AngleTables &T = h->angle;
+  WindAngleArgs g;
+  memset(&g, 0, sizeof g);
+  g.P = a.P;
+  g.Ph = a.Ph;
+  g.states = a.states;
+  g.idx = a.idx;
+  g.dist = a.dist;
+  g.off = a.off;
+  g.theta = h->dws_theta;
+  g.ntot = a.ntot;
+  g.ncell = a.ncell;
+  g.nvar = a.nvar;
+  g.ntracer = a.ntracer;
+  g.ndim = a.ndim;
+  g.eqntype = a.eqntype;
+  g.cooling = a.cooling;
+  g.Tmin = a.Tmin;
+  g.Mu_tot_over_kB = a.Mu_tot_over_kB;
+  WindAngleDev &d = g.s;
+  d.Mdot = W.Mdot_c;
+  d.Vinf = W.Vinf_c;
+  d.v_rot = W.vrot_c;
+  d.Tw = W.Tw_c;
+  d.Rstar = W.Rstar_c;
+  d.Bstar = W.Bstar;
+  d.radius = W.radius;
+  d.xi = T.xi;
+  const double om = angle_omega(W.vrot_c, W.vcrit_c), Tw = W.Tw_c;
+  d.omega = om;
+  d.delta = lgm99::delta_interp(T, om, Tw);
+  // root_find_trilinear_vec's omega and Teff brackets (while (x > x_vec[i]) i++; wind_angle_check keeps i >= 1)
+  int xi = 0, zi = 0;
+  while (xi < PION_ANGLE_NOMEGA - 1 && om > T.omega[xi]) xi++;
+  while (zi < PION_ANGLE_NTEFF - 1 && Tw > T.Teff[zi]) zi++;
+  xi = std::max(xi, 1);
+  zi = std::max(zi, 1);
+  d.dx = (om - T.omega[xi - 1]) / (T.omega[xi] - T.omega[xi - 1]);
+  d.dz = (Tw - T.Teff[zi - 1]) / (T.Teff[zi] - T.Teff[zi - 1]);
+  const int nth = PION_ANGLE_NTHETA, nT = PION_ANGLE_NTEFF;
+  for (int j = 0; j < nth; j++) {
+    d.theta[j] = T.theta[j];
+    d.a[0][j] = T.alpha[((size_t)(xi - 1) * nth + j) * nT + zi - 1];
+    d.a[1][j] = T.alpha[((size_t)(xi - 1) * nth + j) * nT + zi];
+    d.a[2][j] = T.alpha[((size_t)xi * nth + j) * nT + zi - 1];
+    d.a[3][j] = T.alpha[((size_t)xi * nth + j) * nT + zi];
+  }
+  for (int v = 0; v < PION_MAX_NTR; v++) d.tr[v] = (v < h->cfg.ntracer) ? W.tr[v] : 0.0;
+  d.off = W.off;
+  d.n = W.n;
+  hipLaunchKernelGGL(k_wind_state_angle, dim3((unsigned)((W.n + 255) / 256)), dim3(256), 0, h->stream, g);
+}
+
+// stellar_wind_evolution::set_cell_values (stellar_wind_BC.cpp:1334-1372) and update_source (:1250-1330; rotating
+// sources: stellar_wind_angle::update_source, stellar_wind_angle.cpp:941-1019) for every source, then one launch per
+// active source, in id order, that writes the reference states of its cells (no host synchronisation: the
+// parameters are scalars of the host, the launch carries them)
 int wind_sources_update(Handle *h, const double simtime)
 {
   if (int rc = wind_sources_move(h, simtime)) return rc;
@@ -822,7 +1096,7 @@ int wind_sources_update(Handle *h, const double simtime)
   memset(&a, 0, sizeof a);
   for (size_t s = 0; s < h->wsrc.size(); s++) {
     WindSource &W = h->wsrc[s];
-    if (W.type == 1 && simtime >= W.t_next_update) {
+    if ((W.type == 1 || W.type == 2) && simtime >= W.t_next_update) {
       // update_source: every step from tstart on (:1266), values clamped after tfinish
       W.active = true;
       W.t_next_update = std::min(simtime, W.tfinish);
@@ -833,6 +1107,12 @@ int wind_sources_update(Handle *h, const double simtime)
       W.Rstar_c = root_find_linear_vec(W.t, W.R, simtime);
       for (int v = 0; v < h->cfg.ntracer; v++)
         if (W.elem[v] >= 0) W.tr[v] = root_find_linear_vec(W.t, W.X[W.elem[v]], simtime);
+      if (W.type == 2) {
+        // all in cgs already; Tw = std::min(Twind, Teff_vec.back()) (stellar_wind_angle.cpp:972-984)
+        const double Tmax = h->angle.Teff[PION_ANGLE_NTEFF - 1];
+        W.Tw_c = (Tmax < W.Tw_c) ? Tmax : W.Tw_c;
+        W.vcrit_c = root_find_linear_vec(W.t, W.vcrit, simtime);
+      }
     }
     WindSrcDev &d = a.s[s];
     d.Mdot = W.Mdot_c;
@@ -866,9 +1146,60 @@ int wind_sources_update(Handle *h, const double simtime)
   a.Tmin = h->cfg.min_temp;   // EP.MinTemperature, as handed to the stellar_wind constructor
   a.Mu_tot_over_kB = h->Mu_tot_over_kB;
   // stellar_wind_evolution::set_cell_values: an inactive source keeps its cells flagged but does not write them
-  for (int s = 0; s < a.nsrc; s++)
-    if (a.s[s].active && a.s[s].n > 0)
-      hipLaunchKernelGGL(k_wind_state, dim3((unsigned)((a.s[s].n + 255) / 256)), dim3(256), 0, h->stream, a, s);
+  for (int s = 0; s < a.nsrc; s++) {
+    if (!(a.s[s].active && a.s[s].n > 0)) continue;
+    if (h->wsrc[s].type == 2) wind_angle_launch(h, h->wsrc[s], a);
+    else hipLaunchKernelGGL(k_wind_state, dim3((unsigned)((a.s[s].n + 255) / 256)), dim3(256), 0, h->stream, a, s);
+  }
+  return 0;
+}
+
+// BC_assign_STWIND_add_cells2src for a fixed source (orbit_period == 0): every cell, ghosts included, within the
+// radius joins it in cell-id order; then dist, offsets, theta and the flags.  Synchronises.
+static int add_fixed_wind_source(Handle *h, WindSource &W, int *id)
+{
+  // membership: every cell, ghosts included, in cell-id order (a scan: hipcub::DeviceSelect keeps the input order)
+  const GridDesc &g = h->g;
+  const WindMember m = wind_member(h, W);
+  unsigned long long *dcount = nullptr;
+  HCHECK(h, hipMalloc(&dcount, sizeof(unsigned long long)));
+  HCHECK(h, hipMemsetAsync(dcount, 0, sizeof(unsigned long long), h->stream));
+  hipLaunchKernelGGL(k_wind_count, dim3((unsigned)((g.ncell + 255) / 256)), dim3(256), 0, h->stream, m, dcount);
+  unsigned long long cnt = 0;
+  HCHECK(h, hipMemcpyAsync(&cnt, dcount, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  hipFree(dcount);
+  const long n = (long)cnt;
+  if (int rc = wind_lists_grow(h, n)) return rc;
+  const long o = h->nws - n, ntot = h->nws;
+  if (n > 0) {
+    hipcub::CountingInputIterator<long> cells(0);
+    long *dsel = nullptr;
+    HCHECK(h, hipMalloc(&dsel, sizeof(long)));
+    size_t tmp_bytes = 0;
+    HCHECK(h, hipcub::DeviceSelect::If(nullptr, tmp_bytes, cells, h->dws_idx + o, dsel, g.ncell, m, h->stream));
+    void *tmp = nullptr;
+    HCHECK(h, hipMalloc(&tmp, tmp_bytes));
+    HCHECK(h, hipcub::DeviceSelect::If(tmp, tmp_bytes, cells, h->dws_idx + o, dsel, g.ncell, m, h->stream));
+    long nsel = 0;
+    HCHECK(h, hipMemcpyAsync(&nsel, dsel, sizeof nsel, hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    hipFree(tmp);
+    hipFree(dsel);
+    if (nsel != n) {
+      h->err = "wind source: membership count and compaction disagree";
+      return PION_GPU_EDEVICE;
+    }
+    hipLaunchKernelGGL(k_wind_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, m, h->dws_idx + o,
+                       n, h->dws_dist + o, h->dws_off + o, h->dws_theta + o, ntot, h->dflags);
+  }
+  HCHECK(h, hipGetLastError());
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  W.off = o;
+  W.n = n;
+  h->wsrc.push_back(W);
+  h->dt_cached = false;   // the ISBD flags decide which cells enter the time-step reduction
+  if (id) *id = (int)h->wsrc.size() - 1;
   return 0;
 }
 
@@ -1126,6 +1457,7 @@ void pion_gpu_destroy(void *handle)
   hipFree(h->dws_dist);
   hipFree(h->dws_off);
   hipFree(h->dws_state);
+  hipFree(h->dws_theta);
   for (WindSource &W : h->wsrc) {
     hipFree(W.dn);
     hipFree(W.dscan);
@@ -1269,6 +1601,10 @@ int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int 
   if (h->wsrc.size() >= PION_MAX_WIND_SOURCES) return fail("wind source: at most PION_MAX_WIND_SOURCES sources");
   if (src->type == 2 || src->type == 3) return fail("wind source: angle / latitude-dependent winds are not supported");
   if (src->type != 0 && src->type != 1) return fail("What type of source is this?  add a new type?");
+  // a divergence: in the reference's stellar_wind_angle object an evolving source would get LGM99 updates
+  if (src->type == 1)
+    for (const WindSource &o : h->wsrc)
+      if (o.type == 2) return fail("wind source: evolving and rotating sources cannot share a grid");
   if (!(src->radius > 0.0)) return fail("wind source: radius must be > 0");
   if (cfg.coord_sys == 3 && !equalD(src->pos[0], 0.0)) return fail("Spherical symmetry but source not at origin!");
   if (cfg.coord_sys == 2 && cfg.ndim == 2 && !equalD(src->pos[1], 0.0))
@@ -1348,50 +1684,124 @@ int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int 
     return add_moving_wind_source(h, W, id);
   }
 
-  // membership: every cell, ghosts included, in cell-id order (a scan: hipcub::DeviceSelect keeps the input order)
-  WindMember m;
-  m.g = g;
-  for (int a = 0; a < 3; a++) m.pos[a] = W.pos[a];
-  m.radius = W.radius;
-  unsigned long long *dcount = nullptr;
-  HCHECK(h, hipMalloc(&dcount, sizeof(unsigned long long)));
-  HCHECK(h, hipMemsetAsync(dcount, 0, sizeof(unsigned long long), h->stream));
-  hipLaunchKernelGGL(k_wind_count, dim3((unsigned)((g.ncell + 255) / 256)), dim3(256), 0, h->stream, m, dcount);
-  unsigned long long cnt = 0;
-  HCHECK(h, hipMemcpyAsync(&cnt, dcount, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
-  HCHECK(h, hipStreamSynchronize(h->stream));
-  hipFree(dcount);
-  const long n = (long)cnt;
-  if (int rc = wind_lists_grow(h, n)) return rc;
-  const long o = h->nws - n, ntot = h->nws;
-  if (n > 0) {
-    hipcub::CountingInputIterator<long> cells(0);
-    long *dsel = nullptr;
-    HCHECK(h, hipMalloc(&dsel, sizeof(long)));
-    size_t tmp_bytes = 0;
-    HCHECK(h, hipcub::DeviceSelect::If(nullptr, tmp_bytes, cells, h->dws_idx + o, dsel, g.ncell, m, h->stream));
-    void *tmp = nullptr;
-    HCHECK(h, hipMalloc(&tmp, tmp_bytes));
-    HCHECK(h, hipcub::DeviceSelect::If(tmp, tmp_bytes, cells, h->dws_idx + o, dsel, g.ncell, m, h->stream));
-    long nsel = 0;
-    HCHECK(h, hipMemcpyAsync(&nsel, dsel, sizeof nsel, hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    hipFree(tmp);
-    hipFree(dsel);
-    if (nsel != n) {
-      h->err = "wind source: membership count and compaction disagree";
-      return PION_GPU_EDEVICE;
-    }
-    hipLaunchKernelGGL(k_wind_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, m, h->dws_idx + o,
-                       n, h->dws_dist + o, h->dws_off + o, ntot, h->dflags);
+  return add_fixed_wind_source(h, W, id);
+}
+
+int pion_gpu_add_rotating_wind_source(void *handle, const pion_gpu_wind_source *src, const double *evo_vcrit,
+                                      double xi, int *id)
+{
+  Handle *h = use(handle);
+  if (!h || !src) return PION_GPU_EINVAL;
+  const pion_gpu_config &cfg = h->cfg;
+  auto fail = [&](const char *m) {
+    h->err = m;
+    return PION_GPU_EINVAL;
+  };
+  // the reference's rep.error conditions (stellar_wind_angle.cpp:714-716, :912-923; tools/interpolate.cpp:420-440)
+  // and the limits of this path
+  if (h->wsrc.size() >= PION_MAX_WIND_SOURCES) return fail("wind source: at most PION_MAX_WIND_SOURCES sources");
+  if (src->type != 2) return fail("Bad wind type for evolving stellar wind (rotating star)!");
+  if (cfg.ndim < 2) return fail("rotating wind source: needs a 2-D or 3-D grid (theta = 0 in 1-D)");
+  if (cfg.coord_sys == 2 && !equalD(src->pos[1], 0.0)) return fail("Axisymmetry but source not at R=0!");
+  if (src->orbit_period != 0) return fail("rotating wind source: add_rotating_source takes no orbit");
+  if (!(src->radius > 0.0)) return fail("wind source: radius must be > 0");
+  if (src->npt < 2) return fail("evolving wind source: the table needs at least 2 rows");
+  if (!src->evo_time || !src->evo_Teff || !src->evo_Mdot || !src->evo_vrot || !src->evo_vinf || !src->evo_R ||
+      !evo_vcrit)
+    return fail("evolving wind source: missing table column");
+  for (int v = 0; v < cfg.ntracer; v++) {
+    const int e = src->evo_tracer_elem[v];
+    if (e < -1 || e > 6 || (e >= 0 && !src->evo_X[e])) return fail("evolving wind source: bad tracer selector");
   }
-  HCHECK(h, hipGetLastError());
-  HCHECK(h, hipStreamSynchronize(h->stream));
-  W.off = o;
-  W.n = n;
-  h->wsrc.push_back(W);
-  h->dt_cached = false;   // the ISBD flags decide which cells enter the time-step reduction
-  if (id) *id = (int)h->wsrc.size() - 1;
+  for (const WindSource &o : h->wsrc) {
+    if (o.type == 1) return fail("wind source: evolving and rotating sources cannot share a grid");
+    // stellar_wind_angle holds one c_xi (the reference's errorTest on WIND_i_xi)
+    if (o.type == 2 && !(xi == h->angle.xi)) return fail("rotating wind source: xi differs from an earlier source's");
+  }
+  if (!h->have_angle || !(xi == h->angle.xi)) {
+    lgm99::setup_tables(xi, h->angle);
+    h->have_angle = true;
+  }
+  const AngleTables &T = h->angle;
+  WindSource W;
+  W.type = 2;
+  for (int a = 0; a < 3; a++) W.pos[a] = (a < cfg.ndim) ? src->pos[a] : 0.0;
+  W.radius = src->radius;
+  W.Bstar = src->Bstar;
+  for (int v = 0; v < PION_MAX_NVAR; v++) {
+    W.tr[v] = (v < cfg.ntracer) ? src->tracers[v] : 0.0;
+    W.elem[v] = (v < cfg.ntracer) ? src->evo_tracer_elem[v] : -1;
+  }
+  // theta of every member cell within (theta_vec[0], theta_vec[24]], counted on the device before anything changes
+  {
+    const WindMember m = wind_member(h, W);
+    unsigned long long *dcount = nullptr, cnt = 0;
+    HCHECK(h, hipMalloc(&dcount, sizeof(unsigned long long)));
+    HCHECK(h, hipMemsetAsync(dcount, 0, sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(k_wind_theta_bad, dim3((unsigned)((h->g.ncell + 255) / 256)), dim3(256), 0, h->stream, m,
+                       T.theta[0], T.theta[PION_ANGLE_NTHETA - 1], dcount);
+    HCHECK(h, hipGetLastError());
+    HCHECK(h, hipMemcpyAsync(&cnt, dcount, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HCHECK(h, hipStreamSynchronize(h->stream));
+    hipFree(dcount);
+    if (cnt > 0) return fail("rotating wind source: a member cell's theta lies outside the LGM99 table");
+  }
+  // add_evolving_source (stellar_wind_angle.cpp:700-827) + add_rotating_source (:836-932): all values cgs
+  const int n = src->npt;
+  W.t.assign(src->evo_time, src->evo_time + n);
+  W.Teff.assign(src->evo_Teff, src->evo_Teff + n);
+  W.Mdot.assign(src->evo_Mdot, src->evo_Mdot + n);
+  W.vrot.assign(src->evo_vrot, src->evo_vrot + n);
+  W.vinf.assign(src->evo_vinf, src->evo_vinf + n);
+  W.vcrit.assign(evo_vcrit, evo_vcrit + n);
+  W.R.assign(src->evo_R, src->evo_R + n);
+  for (int e = 0; e < 7; e++)
+    if (src->evo_X[e]) W.X[e].assign(src->evo_X[e], src->evo_X[e] + n);
+  W.tstart = W.t[0];
+  W.tfinish = W.t[n - 1];
+  const double t_now = src->t_now;
+  W.t_next_update = std::max(W.tstart, t_now);
+  double mdot = 0.0, vinf = 0.0, Twind = 0.0, vrot = 0.0, rstar = 0.0, vcrt = 0.0;
+  double x[7] = {0, 0, 0, 0, 0, 0, 0};
+  if (((t_now + src->update_freq) > W.tstart || equalD(W.tstart, t_now)) && t_now < W.tfinish) {
+    W.active = true;
+    Twind = root_find_linear_vec(W.t, W.Teff, t_now);
+    mdot = root_find_linear_vec(W.t, W.Mdot, t_now);
+    vinf = root_find_linear_vec(W.t, W.vinf, t_now);
+    vrot = root_find_linear_vec(W.t, W.vrot, t_now);
+    vcrt = root_find_linear_vec(W.t, W.vcrit, t_now);
+    rstar = root_find_linear_vec(W.t, W.R, t_now);
+    for (int e = 0; e < 7; e++)
+      if (!W.X[e].empty()) x[e] = root_find_linear_vec(W.t, W.X[e], t_now);
+  }
+  else {
+    W.active = false;
+    mdot = -100.0;
+    vinf = -100.0;
+    vrot = -100.0;
+    Twind = -100.0;
+  }
+  for (int v = 0; v < cfg.ntracer; v++)
+    if (W.elem[v] >= 0) W.tr[v] = x[W.elem[v]];
+  const double Tmax = T.Teff[PION_ANGLE_NTEFF - 1];
+  W.Mdot_c = mdot;
+  W.Vinf_c = vinf;
+  W.vrot_c = vrot;
+  W.vcrit_c = vcrt;
+  W.Tw_c = (Tmax < Twind) ? Tmax : Twind;   // std::min(Twind, Teff_vec.back())
+  W.Rstar_c = rstar;
+  return add_fixed_wind_source(h, W, id);
+}
+
+int pion_gpu_wind_angle_tables(double xi, double *theta, double *omega, double *Teff, double *delta, double *alpha)
+{
+  AngleTables T;
+  lgm99::setup_tables(xi, T);
+  if (theta) memcpy(theta, T.theta, sizeof T.theta);
+  if (omega) memcpy(omega, T.omega, sizeof T.omega);
+  if (Teff) memcpy(Teff, T.Teff, sizeof T.Teff);
+  if (delta) memcpy(delta, T.delta.data(), sizeof(double) * T.delta.size());
+  if (alpha) memcpy(alpha, T.alpha.data(), sizeof(double) * T.alpha.size());
   return 0;
 }
 
@@ -1558,6 +1968,10 @@ int pion_gpu_update_bcs(void *handle, double simtime, int cstep, int maxstep, in
   const bool full = (cstep == maxstep);
   // after a partial step only Ph's ghosts are refreshed, after the full step P's (and Ph=P)
   double *T = full ? h->dP : h->dPh;
+  // a rotating source that cannot be evaluated at simtime: EINVAL before anything is written
+  if (h->nws > 0 && h->have_angle) {
+    if (int rc = wind_angle_check(h, simtime)) return rc;
+  }
   time_begin(h, 2);
 
   // TimeUpdateInternalBCs: stellar wind only (assign_update_bcs.cpp:134-183)

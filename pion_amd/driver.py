@@ -25,6 +25,20 @@ class SimControl:
         self.min_timestep = min_timestep
         self.first_step_dt_limit = None  # wind / jet limit of calc_dynamics_dt (calc_timestep.cpp:313-323)
 
+    def add_wind_source(self, src):
+        """stellar_wind_bc::BC_assign_STWIND (stellar_wind_boundaries.cpp:120-190) for one SWP source, before init():
+        a rotating star (wind.ANGLE) through GpuSim.add_rotating_wind_source, any other source through
+        add_wind_source; its first-step limit (calc_timestep.cpp:318-322) joins first_step_dt_limit.  Returns the id.
+        A boundary update that a rotating source cannot evaluate (omega <= 0 or Tw <= 1000 K) raises the backend's
+        EINVAL error (lib.PionGpuError) from update_bcs, with nothing written."""
+        from . import wind
+        if src.type == wind.ANGLE:
+            sid = self.sim.add_rotating_wind_source(src)
+        else:
+            sid = self.sim.add_wind_source(src)
+        self.first_step_dt_limit = wind.first_step_dt_limit(self.cfg, [src], self.first_step_dt_limit)
+        return sid
+
     # sim_init::Init (sim_init.cpp:219-267): read data, Ph=P, assign + update boundaries
     def init(self, P, simtime=0.0):
         self.simtime = simtime

@@ -83,10 +83,12 @@ int sim_control_gpu::Init(const double *P_soa, double simtime)
   return err;
 }
 
-int sim_control_gpu::add_wind_source(const pion_gpu_wind_source &src, int *id)
+int sim_control_gpu::add_wind_source(const pion_gpu_wind_source &src, int *id, const double *evo_vcrit, double xi,
+                                     bool rotating)
 {
   if (be_ != pion_backend_gpu()) return PION_GPU_EINVAL;   // the wind sources live in libpion_gpu.so
-  const int err = pion_gpu_add_wind_source(h_, &src, id);
+  const int err = rotating ? pion_gpu_add_rotating_wind_source(h_, &src, evo_vcrit, xi, id)
+                           : pion_gpu_add_wind_source(h_, &src, id);
   if (err) return err;
   // SWP.params[v]->Vinf is the parameter-file value in km/s (0 for most evolving sources: no limit)
   const double lim = 0.1 * cfg.cfl * cfg.dx / (src.vinf * 1.0e5);
@@ -200,6 +202,12 @@ int pion_host_sim_add_wind_source(void *s, const pion_gpu_wind_source *src, int 
 {
   if (!s || !src) return PION_GPU_EINVAL;
   return static_cast<pion_host::sim_control_gpu *>(s)->add_wind_source(*src, id);
+}
+int pion_host_sim_add_rotating_wind_source(void *s, const pion_gpu_wind_source *src, const double *evo_vcrit,
+                                           double xi, int *id)
+{
+  if (!s || !src) return PION_GPU_EINVAL;
+  return static_cast<pion_host::sim_control_gpu *>(s)->add_wind_source(*src, id, evo_vcrit, xi, true);
 }
 int pion_host_sim_init(void *s, const double *P, double simtime, double finishtime, double first_dt_limit)
 {

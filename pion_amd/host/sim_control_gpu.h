@@ -54,8 +54,9 @@ class sim_control_gpu {
   int set_comm(slab_comm *c);
   // stellar_wind_bc::BC_assign_STWIND (stellar_wind_boundaries.cpp:120-190) for one SWP source: a device-built wind
   // source (pion_gpu_add_wind_source), and its first-step limit 0.1 CFL dx / (Vinf 1e5) (calc_timestep.cpp:318-322).
-  // Before Init.
-  int add_wind_source(const pion_gpu_wind_source &src, int *id);
+  // Before Init.  rotating: a type-2 source (pion_gpu_add_rotating_wind_source with evo_vcrit and xi).
+  int add_wind_source(const pion_gpu_wind_source &src, int *id, const double *evo_vcrit = nullptr, double xi = 0.0,
+                      bool rotating = false);
   int update_boundaries(int cstep, int maxstep, int assign);
   int stage(double dt, int space_ooa, int is_full);
   int finish_halo();

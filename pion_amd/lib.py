@@ -51,6 +51,8 @@ def load_library():
     lib.pion_gpu_synchronize.argtypes = [C.c_void_p]
     lib.pion_gpu_set_wind_cells.argtypes = [C.c_void_p, C.c_long, C.POINTER(C.c_long), _dp]
     lib.pion_gpu_add_wind_source.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    lib.pion_gpu_add_rotating_wind_source.argtypes = [C.c_void_p, C.c_void_p, _dp, C.c_double, C.POINTER(C.c_int)]
+    lib.pion_gpu_wind_angle_tables.argtypes = [C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pion_gpu_get_wind_cells.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long), _dp]
     lib.pion_gpu_get_wind_source_pos.argtypes = [C.c_void_p, C.c_int, _dp]
     lib.pion_gpu_wind_orbit_position.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp]
@@ -88,7 +90,8 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_halo_spans", "pion_gpu_halo_begin", "pion_gpu_halo_end",
     "pion_gpu_get_timing", "pion_gpu_stage_part", "pion_gpu_set_comm_stream", "pion_gpu_set_jet",
     "pion_gpu_add_wind_source", "pion_gpu_get_wind_cells", "pion_gpu_get_wind_source_pos",
-    "pion_gpu_wind_orbit_position", "pion_gpu_get_flags",
+    "pion_gpu_wind_orbit_position", "pion_gpu_get_flags", "pion_gpu_add_rotating_wind_source",
+    "pion_gpu_wind_angle_tables",
 ]
 
 
@@ -184,6 +187,17 @@ class GpuSim:
         st, keep = src.to_c()
         i = C.c_int(-1)
         self._chk(self.lib.pion_gpu_add_wind_source(self.h, C.byref(st), C.byref(i)), "add_wind_source")
+        del keep
+        return i.value
+
+    def add_rotating_wind_source(self, src):
+        """pion_gpu_add_rotating_wind_source: src is a pion_amd.wind.WindSource of type ANGLE with an evolution
+        table (its vcrit column) and xi; returns its id"""
+        st, keep = src.to_c()
+        vcrit = keep[-1].ctypes.data_as(_dp) if src.evolution is not None else None
+        i = C.c_int(-1)
+        self._chk(self.lib.pion_gpu_add_rotating_wind_source(self.h, C.byref(st), vcrit, src.xi, C.byref(i)),
+                  "add_rotating_wind_source")
         del keep
         return i.value
 

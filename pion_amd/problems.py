@@ -554,3 +554,37 @@ def cwb3d_orbit(n, strict_fp=0, eqntype=abi.EQGLM, orbits=(True, True), period=3
         srcs.append(wind.WindSource(pos=(x, 0.0, 0.0), radius=r, mdot=mdot, vinf=vinf, vrot=100.0, Tw=1.0e5,
                                     Rstar=6.96e10, Bstar=0.01, tracers=[1.0], orbit=orbit))
     return cfg, P, srcs
+
+
+def etacar2d_lgm99(n, wnd_path, xi=-0.43, time_offset=0.0, t_scalefac=1.0, t_now=5.0e10, strict_fp=0):
+    """test_problems/EvolvingStar2D/params_EtaCar_LGM99_d2l3n256_xi043.txt as etacar2d_evolving sets it up, with the
+    set-up's real wind: a rotating star (WIND_0_type 2, Langer, Garcia-Segura & Mac Low 1999) with WIND_0_xi = `xi`,
+    whose density and terminal speed depend on latitude through the table's vrot / vcrit.  The source sits on the
+    axis at z = 0, a cell face for even n, so no member cell lies on the equator.  Returns (cfg, P, [WindSource]);
+    add the source with SimControl.add_wind_source or GpuSim.add_rotating_wind_source."""
+    from . import wind
+    cfg, P, srcs = etacar2d_evolving(n, wnd_path, time_offset=time_offset, t_scalefac=t_scalefac, t_now=t_now,
+                                     strict_fp=strict_fp)
+    s = srcs[0]
+    src = wind.WindSource(pos=s.pos, radius=s.radius, vinf=s.vinf, tracers=s.tracers, type=wind.ANGLE,
+                          evolution=s.evolution, elements=s.elements, t_now=s.t_now, update_freq=s.update_freq, xi=xi)
+    return cfg, P, [src]
+
+
+def rotstar3d_lgm99(n, eqntype=abi.EQGLM, xi=-0.43, strict_fp=0, Bstar=0.1, t_now=0.0):
+    """wind3d_rot's grid (n^3 cells, one-way outflow, HLL, FKJ98 eta 0.15, cooling 8 with the cooling-time limit,
+    T in [5e3, 1e10]) with a rotating magnetised star at the origin (a cell corner for even n): an LGM99 wind (type
+    ANGLE, WIND_i_xi = `xi`) from a two-row table, 1e-6 -> 1.2e-6 Msun/yr, 1000 -> 900 km/s, vrot 150 -> 180 km/s
+    of vcrit 300 km/s, Teff 2.5e4 -> 3e4 K from t = -1e12 s to 1e12 s, Rstar 6.96e12 cm, Bsrf `Bstar` G.  The wind radius
+    (6.96e12 cm) is kept at least 6 cells.  Returns (cfg, P, [WindSource])."""
+    from . import wind
+    cfg, P, _ = wind3d_rot(n, strict_fp=strict_fp, eqntype=eqntype, vrot=0.0, Bstar=Bstar)
+    msun_yr = 1.9891e33 / 3.1558150e7
+    cols = {c: np.zeros(2) for c in wind.COLUMNS}
+    cols.update(time=np.array([-1.0e12, 1.0e12]), Teff=np.array([2.5e4, 3.0e4]),
+                Mdot=np.array([1.0e-6, 1.2e-6]) * msun_yr, vrot=np.array([1.5e7, 1.8e7]), vcrit=np.array([3.0e7, 3.0e7]),
+                vinf=np.array([1.0e8, 0.9e8]), R=np.array([6.96e12, 6.96e12]), X_H=np.array([0.7, 0.7]))
+    src = wind.WindSource(pos=(0.0, 0.0, 0.0), radius=max(6.96e12, 6.0 * cfg.dx), vinf=1000.0, Bstar=Bstar,
+                          tracers=[1.0], type=wind.ANGLE, evolution=wind.WindEvolution(cols), elements=[None],
+                          t_now=t_now, update_freq=1.0, xi=xi)
+    return cfg, P, [src]

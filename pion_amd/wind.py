@@ -6,7 +6,9 @@
     idx, states = sim.get_wind_cells(0)
 
 Constant winds take Msun/yr and km/s (stellar_wind::add_source, grid/stellar_wind_BC.cpp:166-172); an evolving wind
-(type EVOLVING) takes a table read by read_wind_evolution, in cgs, with its times already offset and scaled.
+(type EVOLVING) takes a table read by read_wind_evolution, in cgs, with its times already offset and scaled.  A
+rotating star (type ANGLE, the LGM99 wind of grid/stellar_wind_angle.cpp) takes such a table too, its vcrit column
+and `xi`, and is added with GpuSim.add_rotating_wind_source.
 """
 import ctypes as C
 import os
@@ -15,7 +17,7 @@ import numpy as np
 
 from . import abi
 
-CONSTANT, EVOLVING = 0, 1          # WINDTYPE_CONSTANT, WINDTYPE_EVOLVING (grid/stellar_wind_BC.h:41-42)
+CONSTANT, EVOLVING, ANGLE = 0, 1, 2   # WINDTYPE_CONSTANT, _EVOLVING, _ANGLE (grid/stellar_wind_BC.h:41-43)
 ELEMENTS = ("X_H", "X_He", "X_C", "X_N", "X_O", "X_Z", "X_D")   # set_element_indices (:992-1024)
 MAX_SOURCES = 8
 
@@ -83,10 +85,12 @@ class WindSource:
     evolving source is only the parameter-file value the first-step limit uses (0: none).
     `orbit` = (ecentricity_fac, periastron_x [cm], periastron_y [cm], period [yr]) moves the source on the
     reference's ellipse around `pos` at every boundary update (2-D and 3-D Cartesian grids); None or a zero period:
-    the source stays at `pos`."""
+    the source stays at `pos`.
+    Rotating (type ANGLE): as evolving, the table's vcrit column included, and `xi` (WIND_i_xi), the exponent of the
+    equatorial density enhancement."""
 
     def __init__(self, pos, radius, mdot=0.0, vinf=0.0, vrot=0.0, Tw=0.0, Rstar=0.0, Bstar=0.0, tracers=(),
-                 type=CONSTANT, evolution=None, elements=None, t_now=0.0, update_freq=0.0, orbit=None):
+                 type=CONSTANT, evolution=None, elements=None, t_now=0.0, update_freq=0.0, orbit=None, xi=0.0):
         self.pos = tuple(pos) + (0.0,) * (3 - len(pos))
         self.radius = radius
         self.mdot, self.vinf, self.vrot = mdot, vinf, vrot
@@ -96,6 +100,7 @@ class WindSource:
         self.evolution = evolution
         self.elements = list(elements) if elements is not None else [None] * len(self.tracers)
         self.t_now, self.update_freq = t_now, update_freq
+        self.xi = float(xi)
         self.orbit = tuple(float(v) for v in orbit) if orbit is not None else (0.0, 0.0, 0.0, 0.0)
         if len(self.orbit) != 4:
             raise ValueError("orbit = (ecentricity_fac, periastron_x, periastron_y, period_years)")
@@ -127,6 +132,7 @@ class WindSource:
                 s.evo_X[e] = arr(ev.cols[name])
             for v, name in enumerate(self.elements):
                 s.evo_tracer_elem[v] = -1 if name is None else ELEMENTS.index(name)
+            keep.append(np.ascontiguousarray(ev.vcrit, dtype=np.float64))   # keep[-1]: pion_gpu_add_rotating_...
         s.t_now, s.update_freq = self.t_now, self.update_freq
         s.orbit_ecc_fac, s.orbit_periastron[0], s.orbit_periastron[1], s.orbit_period = self.orbit
         return s, keep
@@ -153,3 +159,17 @@ def orbit_position(src, ndim, simtime):
     if rc != 0:
         raise ValueError("pion_gpu_wind_orbit_position: rc %d" % rc)
     return tuple(out[:3])
+
+
+def angle_tables(xi):
+    """pion_gpu_wind_angle_tables (host code of libpion_gpu.so, no device needed): stellar_wind_angle::setup_tables
+    for `xi`.  Returns dict(theta[25], omega[25], Teff[22], delta[25, 22], alpha[25, 25, 22]) of numpy arrays."""
+    from . import lib
+    L = lib.load_library()
+    out = dict(theta=np.zeros(25), omega=np.zeros(25), Teff=np.zeros(22), delta=np.zeros((25, 22)),
+               alpha=np.zeros((25, 25, 22)))
+    rc = L.pion_gpu_wind_angle_tables(float(xi), *(out[k].ctypes.data_as(_dp)
+                                                   for k in ("theta", "omega", "Teff", "delta", "alpha")))
+    if rc != 0:
+        raise ValueError("pion_gpu_wind_angle_tables: rc %d" % rc)
+    return out
