@@ -215,6 +215,13 @@ int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int 
 int pion_gpu_get_wind_source_pos(void *handle, int id, double *pos);
 /* The cell flags (PION_CELL_*, ncell_all bytes, ghosts included) as the device holds them now (synchronises). */
 int pion_gpu_get_flags(void *handle, unsigned char *out);
+/* The HLLD -> HLL switch of every cell (ncell_all bytes, ghosts included) as the prepass of the last stage left it
+ * (synchronises; read-only).  EINVAL for a handle without the switch (not MHD / GLM with HLLD). */
+int pion_gpu_get_hll_switch(void *handle, unsigned char *out);
+/* The screened prepass (3-D MHD / GLM with HLLD; PION_HLL_SCREEN=0 in the environment switches it off): number of
+ * blocks of cells the last stage's prepass evaluated, and number of blocks.  active = -1, total = 0 when that prepass
+ * was the dense one.  Synchronises: call it outside timed regions. */
+int pion_gpu_get_hll_screen_counts(void *handle, int *active, int *total);
 /* The position the orbit of `src` gives at `simtime` on a grid of `ndim` (2 or 3) dimensions, in plain double as
  * BC_update_STWIND computes it (src->pos for orbit_period == 0).  Host only: needs no device or handle.  EINVAL for
  * ndim outside 2..3 or a NULL pointer. */

@@ -11,6 +11,7 @@
 
 #include "dev_riemann.h"
 #include "rows_tiling.h"
+#include "hll_screen.h"
 
 namespace pion {
 
@@ -75,6 +76,11 @@ struct StageArgs {
   int dt_mp;          // also reduce the cooling time (EP.MP_timestep_limit)
   int plain_cells;    // every on-grid cell is an ordinary domain cell (no stellar-wind cells): flags need not be read
   CoolDev cool;
+  // k_stage_rows2, 3-D MHD / GLM with HLLD: pressure-range summary per block of cells (hll_screen.h) for the next
+  // stage's prepass, keys of the maxima [hsum_n] then of the minima [hsum_n], cleared by the caller (or null)
+  unsigned long long *hsum;
+  long hsum_n;
+  int hsum_nbx, hsum_nby, hsum_nbz;
 };
 
 struct PrepassArgs {
@@ -87,6 +93,11 @@ struct PrepassArgs {
   double gamma;
   long c0, c1;            // cell range [c0,c1) (whole planes) this launch covers
   long c2, c3;            // k_prepass_hlld: a second range [c2,c3) in the same launch (empty when c3 <= c2)
+  // screened prepass (hll_screen.h; whole-array launches only): the summary the last stage kernel left of S (or null),
+  // its geometry, the list of active blocks and its counter (both written here)
+  const unsigned long long *hsum;
+  ScrGeom scr;
+  int *scr_list, *scr_count;
 };
 
 struct DtArgs {

@@ -786,6 +786,9 @@ const char *stage_kernel_name(int, int, int) { return "k_stage"; }
 // pre-pass: HLLD switch and H-correction.  One thread per cell INCLUDING ghosts
 // (the reference loops FirstPt_All..NextPt_All, solver_eqn_base.cpp:400-412).
 // ---------------------------------------------------------------------------
+// the switch of one cell i (all-cell indices): shared by k_prepass_hlld and k_prepass_hlld_blocks
+PDEV void prepass_hlld_cell(const PrepassArgs &a, const int *i);
+
 __global__ __launch_bounds__(256) void k_prepass_hlld(const PrepassArgs a)
 {
   // 3-D launch (64 x 4 threads; grid = x tiles, y tiles, planes of [c0,c1)): the cell coordinates come
@@ -806,6 +809,12 @@ __global__ __launch_bounds__(256) void k_prepass_hlld(const PrepassArgs a)
   const unsigned pz = t / (gx * gy);
   i[2] = (pz < npl1) ? (int)(a.c0 / plane) + (int)pz : (int)(a.c2 / plane) + (int)(pz - npl1);
   if (i[0] >= a.g.nga[0] || i[1] >= a.g.nga[1]) return;
+  prepass_hlld_cell(a, i);
+}
+
+PDEV void prepass_hlld_cell(const PrepassArgs &a, const int *i)
+{
+  const long nc = a.g.ncell;
   const long c = (long)i[0] + a.g.sy * i[1] + a.g.sz * i[2];
   const double dx = a.g.dx;
   // The switch is (div v < 0 && grad > 5): the pressure term decides for almost every cell (grad > 5 only
@@ -1012,10 +1021,53 @@ __global__ __launch_bounds__(256) void k_prepass_hcorr(const PrepassArgs a)
   }
 }
 
+// Screened prepass (hll_screen.h).  k_prepass_screen: one thread per block of the summary the last stage kernel left of
+// a.S; a block whose 3 x 3 x 3 neighbourhood is not provably calm goes onto the list of active blocks.
+__global__ __launch_bounds__(256) void k_prepass_screen(const PrepassArgs a)
+{
+  const long nblk = scr_total(a.scr);
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nblk) return;
+  const int bx = (int)(t % a.scr.nb[0]), by = (int)((t / a.scr.nb[0]) % a.scr.nb[1]);
+  const int bz = (int)(t / ((long)a.scr.nb[0] * a.scr.nb[1]));
+  if (!scr_block_quiet(a.scr, a.hsum, a.hsum + nblk, bx, by, bz)) a.scr_list[atomicAdd(a.scr_count, 1)] = (int)t;
+}
+// k_prepass_hlld_blocks: k_prepass_hlld's cell code on the cells of the listed blocks (the flags of all other cells were
+// cleared); a block on a face of the grid also takes the ghost cells beyond it.  A fixed grid strides over the list,
+// whose length stays on the device.  One wavefront per x row of the block.
+__global__ __launch_bounds__(256) void k_prepass_hlld_blocks(const PrepassArgs a)
+{
+  const int n = *a.scr_count;
+  for (int e = (int)blockIdx.x; e < n; e += (int)gridDim.x) {
+    const int t = a.scr_list[e];
+    const int bx = t % a.scr.nb[0], by = (t / a.scr.nb[0]) % a.scr.nb[1], bz = t / (a.scr.nb[0] * a.scr.nb[1]);
+    int lo[3], hi[3];
+    scr_cells_ext(a.scr, 0, bx, &lo[0], &hi[0]);
+    scr_cells_ext(a.scr, 1, by, &lo[1], &hi[1]);
+    scr_cells_ext(a.scr, 2, bz, &lo[2], &hi[2]);
+    const int ny = hi[1] - lo[1], nrow = ny * (hi[2] - lo[2]);
+    for (int r = (int)(threadIdx.x >> 6); r < nrow; r += 4) {
+      int i[3];
+      i[1] = lo[1] + r % ny;
+      i[2] = lo[2] + r / ny;
+      for (i[0] = lo[0] + (int)(threadIdx.x & 63); i[0] < hi[0]; i[0] += 64) prepass_hlld_cell(a, i);
+    }
+  }
+}
+
 int launch_prepass(const PrepassArgs &a, hipStream_t s)
 {
   const unsigned nb = (unsigned)((a.c1 - a.c0 + 255) / 256);
-  if (a.hllflag) {
+  if (a.hllflag && a.hsum) {
+    // (pion_gpu.hip passes a summary only for whole-array launches of a 3-D Cartesian grid without debug outputs)
+    const long nblk = scr_total(a.scr);
+    if (hipMemsetAsync(a.hllflag, 0, (size_t)a.g.ncell, s) != hipSuccess) return -1;
+    if (hipMemsetAsync(a.scr_count, 0, sizeof(int), s) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_prepass_screen, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, s, a);
+    const unsigned ngrid = (nblk < 4096) ? (unsigned)nblk : 4096u;
+    hipLaunchKernelGGL(k_prepass_hlld_blocks, dim3(ngrid), dim3(256), 0, s, a);
+  }
+  else if (a.hllflag) {
     // [c0,c1) is a whole number of planes (pion_gpu.hip)
     const long plane = (long)a.g.nga[0] * a.g.nga[1];
     const unsigned npl = (unsigned)((a.c1 - a.c0) / plane) + ((a.c3 > a.c2) ? (unsigned)((a.c3 - a.c2) / plane) : 0u);

@@ -520,7 +520,28 @@ struct Handle {
   bool dt_mp_pending = false;  // k_dt_mp owed after the two streams of a split stage have joined
   bool split_dt_mp = true;     // PION_SPLIT_DT_MP=0: cooling time inside the stage kernel's fused reduction (A/B)
   bool fuse_bc = true;    // PION_FUSE_BC=0: periodic faces one launch per face (A/B)
+  // Screened HLLD -> HLL switch prepass (hll_screen.h): a whole-stage launch of k_stage_rows2 leaves the pressure range
+  // of every block of the array it writes in dsum; the next stage's prepass evaluates only the blocks that are not
+  // provably calm.  sum_arr: the array dsum describes (null: none), valid for the prepass once sum_bc says that the
+  // boundary update has refilled that array's ghost cells; dropped by everything else that writes the state.
+  bool hll_screen = true;      // PION_HLL_SCREEN=0: always the dense prepass (A/B)
+  bool screen_ok = false;      // grid, boundary types and cell lists admit the screen (screen_admitted)
+  ScrGeom scr;
+  unsigned long long *dsum = nullptr;   // [2][blocks]: keys of the maxima, of the minima
+  int *dscr_list = nullptr, *dscr_count = nullptr;
+  const double *sum_arr = nullptr;
+  bool sum_bc = false;
+  bool last_prepass_screened = false;
 };
+
+// the state arrays, the cell flags or the tables were written from outside the stages: what the last stage left
+// about its result (time-step minima, pressure summary) no longer holds
+static inline void state_changed(Handle *h)
+{
+  h->dt_cached = false;
+  h->sum_arr = nullptr;
+  h->sum_bc = false;
+}
 
 #define HCHECK(h, call)                                                            \
   do {                                                                             \
@@ -953,7 +974,7 @@ static int add_moving_wind_source(Handle *h, WindSource &W, int *id)
   if (int rc = wind_add_cells_box(h, h->wsrc.back())) return rc;
   HCHECK(h, hipGetLastError());
   HCHECK(h, hipStreamSynchronize(h->stream));
-  h->dt_cached = false;   // the ISBD flags decide which cells enter the time-step reduction
+  state_changed(h);   // the ISBD flags decide which cells enter the time-step reduction
   if (id) *id = (int)h->wsrc.size() - 1;
   return 0;
 }
@@ -980,7 +1001,7 @@ static int wind_sources_move(Handle *h, const double simtime)
   }
   // An unchanged position leaves the flags as they were: every cell an unflag touches lies in the sphere of that
   // moving source, which re-adds it at once.  A move changes them, and with them the cached time step.
-  if (moved) h->dt_cached = false;
+  if (moved) state_changed(h);
   return 0;
 }
 
@@ -1198,7 +1219,7 @@ static int add_fixed_wind_source(Handle *h, WindSource &W, int *id)
   W.off = o;
   W.n = n;
   h->wsrc.push_back(W);
-  h->dt_cached = false;   // the ISBD flags decide which cells enter the time-step reduction
+  state_changed(h);   // the ISBD flags decide which cells enter the time-step reduction
   if (id) *id = (int)h->wsrc.size() - 1;
   return 0;
 }
@@ -1250,6 +1271,7 @@ int pion_gpu_create(const pion_gpu_config *cfg, int device, void **handle)
   if (const char *e = getenv("PION_FUSE_DT")) h->fuse_dt = (atoi(e) != 0);
   if (const char *e = getenv("PION_FUSE_BC")) h->fuse_bc = (atoi(e) != 0);
   if (const char *e = getenv("PION_UNEVEN_CHUNKS")) h->uneven_chunks = (atoi(e) != 0);
+  if (const char *e = getenv("PION_HLL_SCREEN")) h->hll_screen = (atoi(e) != 0);
   if (const char *e = getenv("PION_SPLIT_DT_MP")) h->split_dt_mp = (atoi(e) != 0);
   if (const char *e = getenv("PION_ROWS")) h->rows = h->rows1 = (atoi(e) >= 1 && atoi(e) <= 64) ? atoi(e) : 0;
   if (const char *e = getenv("PION_ROWS1")) h->rows1 = (atoi(e) >= 1 && atoi(e) <= 8) ? atoi(e) : 0;
@@ -1440,6 +1462,9 @@ void pion_gpu_destroy(void *handle)
   }
   hipFree(h->dflags);
   hipFree(h->dhll);
+  hipFree(h->dsum);
+  hipFree(h->dscr_list);
+  hipFree(h->dscr_count);
   hipFree(h->ddE);
   if (h->bstream) hipStreamDestroy(h->bstream);
   if (h->ev_pre) hipEventDestroy(h->ev_pre);
@@ -1494,7 +1519,7 @@ int pion_gpu_upload(void *handle, const double *P_soa)
   HCHECK(h, hipMemcpyAsync(h->dPh, h->dP, nb, hipMemcpyDeviceToDevice, h->stream));
   HCHECK(h, hipStreamSynchronize(h->stream));
   h->ph_valid = false;
-  h->dt_cached = false;
+  state_changed(h);
   h->dt_requested = false;   // a read-back requested for the previous state is void
   h->dt_mp_pending = false;
   return 0;
@@ -1525,7 +1550,7 @@ int pion_gpu_bind_device_state(void *handle, void *dP, void *dPh)
   h->dP = (double *)dP;
   h->dPh = (double *)dPh;
   h->ph_valid = false;
-  h->dt_cached = false;
+  state_changed(h);
   h->dt_requested = false;
   return 0;
 }
@@ -1533,7 +1558,7 @@ void *pion_gpu_device_ptr(void *handle, int which)
 {
   Handle *h = use(handle);
   h->xghost_fresh = nullptr;
-  h->dt_cached = false;  // the caller may write through the pointer
+  state_changed(h);  // the caller may write through the pointer
   return which == 0 ? (void *)h->dP : (void *)h->dPh;
 }
 int pion_gpu_set_stream(void *handle, void *stream)
@@ -1560,7 +1585,7 @@ int pion_gpu_synchronize(void *handle)
 int pion_gpu_set_wind_cells(void *handle, long n, const long *idx, const double *states)
 {
   Handle *h = use(handle);
-  h->dt_cached = false;   // the ISBD flags decide which cells enter the time-step reduction
+  state_changed(h);   // the ISBD flags decide which cells enter the time-step reduction
   hipFree(h->dwind_idx);
   hipFree(h->dwind_state);
   h->dwind_idx = nullptr;
@@ -1822,6 +1847,28 @@ int pion_gpu_get_flags(void *handle, unsigned char *out)
   return 0;
 }
 
+int pion_gpu_get_hll_switch(void *handle, unsigned char *out)
+{
+  Handle *h = use(handle);
+  if (!h || !out || !h->dhll) return PION_GPU_EINVAL;
+  HCHECK(h, hipMemcpyAsync(out, h->dhll, h->g.ncell, hipMemcpyDeviceToHost, h->stream));
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int pion_gpu_get_hll_screen_counts(void *handle, int *active, int *total)
+{
+  Handle *h = use(handle);
+  if (!h || !active || !total) return PION_GPU_EINVAL;
+  *active = -1;
+  *total = 0;
+  if (!h->last_prepass_screened) return 0;
+  HCHECK(h, hipMemcpyAsync(active, h->dscr_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  *total = (int)scr_total(h->scr);
+  return 0;
+}
+
 int pion_gpu_wind_orbit_position(const pion_gpu_wind_source *src, int ndim, double simtime, double *pos)
 {
   if (!src || !pos || ndim < 2 || ndim > 3) return PION_GPU_EINVAL;
@@ -1859,7 +1906,7 @@ int pion_gpu_get_wind_cells(void *handle, int id, long *n, long *idx, double *st
 int pion_gpu_set_jet(void *handle, int jetradius, const double *jetstate)
 {
   Handle *h = use(handle);
-  h->dt_cached = false;   // (cell flags change)
+  state_changed(h);   // (cell flags change)
   const pion_gpu_config &cfg = h->cfg;
   const GridDesc &g = h->g;
   const bool cart3d = (cfg.ndim == 3 && cfg.coord_sys == 1 && cfg.eqntype == PION_EQEUL);
@@ -1917,7 +1964,7 @@ int pion_gpu_set_jet(void *handle, int jetradius, const double *jetstate)
 int pion_gpu_set_cooling_tables(void *handle, int nT, const double *T, const double *tabs, const double *slopes)
 {
   Handle *h = use(handle);
-  h->dt_cached = false;   // t_mp depends on the tables
+  state_changed(h);   // t_mp depends on the tables
   if (nT < 2 || nT > PION_COOL_NT_MAX) {
     // (k_cooling_dE keeps the tables in LDS: 11 x PION_COOL_NT_MAX doubles; mp_only_cooling builds 200 points)
     h->err = "cooling tables: 2 <= nT <= 256 required";
@@ -1968,6 +2015,9 @@ int pion_gpu_update_bcs(void *handle, double simtime, int cstep, int maxstep, in
   const bool full = (cstep == maxstep);
   // after a partial step only Ph's ghosts are refreshed, after the full step P's (and Ph=P)
   double *T = full ? h->dP : h->dPh;
+  // the pressure summary of T (if any) describes its on-grid cells: this update makes the ghost cells copies of them
+  if (h->sum_arr == T && h->nwind == 0 && h->nws == 0) h->sum_bc = true;
+  else if (h->sum_arr == T) h->sum_arr = nullptr;
   // a rotating source that cannot be evaluated at simtime: EINVAL before anything is written
   if (h->nws > 0 && h->have_angle) {
     if (int rc = wind_angle_check(h, simtime)) return rc;
@@ -2238,6 +2288,39 @@ static int launch_cooling_time(Handle *h, hipStream_t s)
   return 0;
 }
 
+// Does this handle admit the screened prepass?  3-D Cartesian grid run by k_stage_rows2 with HLLD; every face periodic,
+// outflow, one-way outflow, reflecting or axis-reflecting (k_bc_all / k_bc_face / k_bc_periodic_all leave exact copies
+// of on-grid pressures in the ghost cells of those, and of no other type); no wind, jet or DMR2 cells; blocks at
+// the faces wide enough to hold the copied cells.
+static bool screen_admitted(Handle *h)
+{
+  const pion_gpu_config &cfg = h->cfg;
+  if (!h->hll_screen || !h->dhll || cfg.ndim != 3 || h->g.cyl != 0 || h->use_march == 0 || h->g.nbc[2] < 2) return false;
+  if (any_wind(h) || h->njet > 0 || cfg.bc_dmach2) return false;
+  if (h->g.ncell * 8L >= (1L << 32)) return false;
+  int per[3];
+  for (int d = 0; d < 3; d++) {
+    for (int f = 2 * d; f < 2 * d + 2; f++) {
+      const int t = cfg.bc_type[f];
+      if (!(t == PION_BC_PERIODIC || t == PION_BC_OUTFLOW || t == PION_BC_ONEWAY_OUT || t == PION_BC_REFLECTING
+            || t == PION_BC_AXISYMMETRIC))
+        return false;
+    }
+    if ((cfg.bc_type[2 * d] == PION_BC_PERIODIC) != (cfg.bc_type[2 * d + 1] == PION_BC_PERIODIC)) return false;
+    per[d] = (cfg.bc_type[2 * d] == PION_BC_PERIODIC) ? 1 : 0;
+    if (!scr_axis_ok(h->g.ng[d], h->g.nbc[d])) return false;
+  }
+  h->scr = scr_geom(h->g.ng, h->g.nbc, per);
+  if (!h->dsum) {
+    const size_t n = (size_t)scr_total(h->scr);
+    if (hipMalloc(&h->dsum, 2 * n * sizeof(unsigned long long)) != hipSuccess) return false;
+    if (hipMalloc(&h->dscr_list, n * sizeof(int)) != hipSuccess) return false;
+    if (hipMalloc(&h->dscr_count, sizeof(int)) != hipSuccess) return false;
+    if (hipMemset(h->dscr_count, 0, sizeof(int)) != hipSuccess) return false;
+  }
+  return true;
+}
+
 // planes [kz0,kz1) and, if kz3 > kz2, also [kz2,kz3) (the two z-boundary strips go out as ONE launch)
 static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_step, int kz0, int kz1,
                         bool first, bool last, int kz2 = 0, int kz3 = 0, hipStream_t ls = 0, bool use_ls = false)
@@ -2269,6 +2352,17 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
     p.c0 = 0;
     p.c1 = h->g.ncell;
     p.c2 = p.c3 = 0;
+    // the summary the last stage left of S, if nothing but the boundary update has touched S since
+    p.hsum = nullptr;
+    p.scr_list = p.scr_count = nullptr;
+    h->screen_ok = screen_admitted(h);
+    if (first && last && h->screen_ok && h->sum_arr == S && h->sum_bc) {
+      p.hsum = h->dsum;
+      p.scr = h->scr;
+      p.scr_list = h->dscr_list;
+      p.scr_count = h->dscr_count;
+    }
+    h->last_prepass_screened = (p.hsum != nullptr);
     if (!(first && last)) {
       const int nb = h->g.nbc[2], nz = h->g.ng[2];
       int lo = kz0 - 1, hi = kz1 + 1;        // on-grid plane numbers [lo,hi): the interior part
@@ -2380,6 +2474,24 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
                        && ((h->g.ndim == 3 && h->g.nbc[2] >= 2) || h->g.ndim == 2) && a.out == h->dP;
   a.dtres = nullptr;
   a.cfl = cfg.cfl;
+  // pressure-range summary of the array this launch writes: whole stages of the rows kernel on a grid of ordinary
+  // cells, rows per wavefront dividing the block height
+  a.hsum = nullptr;
+  a.hsum_n = 0;
+  a.hsum_nbx = a.hsum_nby = a.hsum_nbz = 0;
+  h->sum_arr = nullptr;
+  h->sum_bc = false;
+  const bool leave_sum = first && last && h->dhll && h->screen_ok && a.plain_cells && a.rows >= 1 && cfg.cooling == 0
+                         && !h->deta && !a.fc.mp.present
+                         && PION_SCR_BY % a.rows == 0 && !(is_full_step && a.out == h->dPh);
+  if (leave_sum) {
+    a.hsum = h->dsum;
+    a.hsum_n = scr_total(h->scr);
+    a.hsum_nbx = h->scr.nb[0];
+    a.hsum_nby = h->scr.nb[1];
+    a.hsum_nbz = h->scr.nb[2];
+    HCHECK(h, hipMemsetAsync(h->dsum, 0, 2 * (size_t)a.hsum_n * sizeof(unsigned long long), ls));
+  }
   // the cooling time: not in the stage kernel's fused reduction but in its own launch behind the last part of the
   // stage (k_dt_mp, rate tables in LDS; PION_SPLIT_DT_MP=0: fused, A/B)
   const bool split_mp = fuse_dt && mp_dt_limited(cfg) && h->split_dt_mp;
@@ -2419,6 +2531,7 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
   }
   h->ph_valid = !is_full_step;
   h->dt_cached = fuse_dt;
+  if (leave_sum) h->sum_arr = a.out;
   h->xghost_fresh = a.xwrap ? ((is_full_step && a.out == h->dPh) ? h->dP : a.out) : nullptr;
   return 0;
 }

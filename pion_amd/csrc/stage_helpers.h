@@ -145,5 +145,14 @@ PDEV double wave_min64(double v)
   }
   return v;
 }
+PDEV double wave_max64(double v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double w = __shfl_xor(v, o, 64);
+    v = (w > v) ? w : v;
+  }
+  return v;
+}
 
 #endif

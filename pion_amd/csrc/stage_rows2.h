@@ -242,6 +242,11 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
   constexpr bool MHD = E::MHD;
   constexpr int NZ = ZSL ? 2 * NV : NV;   // LDS slots per row: [z slope,] lower z flux
   constexpr bool PF = PION_ROWS2_PF && (OAMODE == 1);
+  // the instances whose result the HLLD -> HLL switch prepass screens (hll_screen.h): 3-D runs of these leave the range
+  // of the pressure they write per block of cells when the host asks for it (a.hsum).  Not the instances with cooling /
+  // H-correction: they have no registers to spare (12 bytes of scratch with the two running values), and a summary
+  // that is asked for but not written reads as "every block active", which is today's result.
+  constexpr bool SCR = MHD && SOLVER == FLUX_RS_HLLD && !CYL && PLAIN;
   extern __shared__ double lds[];
 
   const int R = a.rows;
@@ -288,6 +293,8 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
     writer = (seg < tl.spw && jg < nyg && pos >= 1 && pos <= tl.rem);
     if (jg >= nyg) jg = nyg - 1;   // idle lanes redo the last group, in bounds, and write nothing
   }
+  // (SCR) x block of the wavefront's cells: lane 0 is the halo lane left of the first cell of its x tile
+  const int scr_bx = SCR ? __builtin_amdgcn_readfirstlane(ix + 1) / PION_SCR_BX : 0;
   if (ix > a.g.ng[0]) ix = a.g.ng[0];
   const int j0 = jg * R;
   const int nrows = (jg_first * R + R <= a.g.ng[1]) ? R : a.g.ng[1] - jg_first * R;
@@ -322,6 +329,9 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
   if (PLAIN) fc.mp.present = 0;
   int err = 0;
   double tdyn = 1.e100, tmp = 1.0e99;  // running minima for the fused time-step reduction
+  // (SCR) running range of the pressure this lane has written since the last block boundary; a NaN enters as +inf
+  const bool scr_on = SCR && a.hsum != nullptr && (PION_SCR_BY % R) == 0;   // (a row group lies in one block)
+  double scr_m = __builtin_inf(), scr_M = -__builtin_inf();
 
   const int zbase = wave * R * NZ * 64 + lane;
 #define ZS2(r, s) lds[zbase + ((r) * NZ + (s)) * 64]
@@ -859,6 +869,13 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
         }
 #pragma unroll
         for (int v = 0; v < NV; v++) stu(Ob + v * ncb, off, Pf[v]);
+        if constexpr (SCR) {
+          if (scr_on) {
+            const double p = Pf[qPG], pM = (p == p) ? p : __builtin_inf();
+            scr_m = (p < scr_m) ? p : scr_m;
+            scr_M = (pM > scr_M) ? pM : scr_M;
+          }
+        }
         if (a.xwrap) {
           // periodic x faces: the ghost images of the first / last nbc cells of the row are these same values
           // (periodic_boundaries.cpp:42-50); written here, where the row is in registers, instead of by the
@@ -886,6 +903,26 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
             tmp = (t < tmp) ? t : tmp;
           }
         }
+      }
+    }
+    if constexpr (SCR) {
+      // last plane of a block of PION_SCR_BZ planes, or of the chunk: fold the range into the block's summary.  A full
+      // x tile is one block wide and its row group lies in one block (the host enables this only when the rows per
+      // wavefront divide PION_SCR_BY): one reduction and one pair of atomics per wavefront.  The lanes of a
+      // remainder wavefront belong to several row groups: each writer lane folds its own values.
+      if (scr_on && !prime && (((k + 1) % PION_SCR_BZ) == 0 || k == k1 - 1)) {
+        const long si = ((long)scr_block_of(k, a.hsum_nbz, 2) * a.hsum_nby + scr_block_of(j0, a.hsum_nby, 1)) * a.hsum_nbx
+                        + ((scr_bx < a.hsum_nbx) ? scr_bx : a.hsum_nbx - 1);
+        if (tt < tl.nfull) {
+          scr_m = wave_min64(scr_m);
+          scr_M = wave_max64(scr_M);
+        }
+        if ((tt < tl.nfull) ? (lane == 0) : writer) {
+          atomicMax(&a.hsum[si], scr_key(scr_M));
+          atomicMax(&a.hsum[a.hsum_n + si], ~scr_key(scr_m));
+        }
+        scr_m = __builtin_inf();
+        scr_M = -__builtin_inf();
       }
     }
   }

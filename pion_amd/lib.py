@@ -57,6 +57,9 @@ def load_library():
     lib.pion_gpu_get_wind_source_pos.argtypes = [C.c_void_p, C.c_int, _dp]
     lib.pion_gpu_wind_orbit_position.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp]
     lib.pion_gpu_get_flags.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pion_gpu_get_hll_switch"):   # (a PION_GPU_LIB build for A/B runs may predate these two read-backs)
+        lib.pion_gpu_get_hll_switch.argtypes = [C.c_void_p, C.c_void_p]
+        lib.pion_gpu_get_hll_screen_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.pion_gpu_set_cooling_tables.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     lib.pion_gpu_update_bcs.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int]
     lib.pion_gpu_calc_dt.argtypes = [C.c_void_p, _dp, _dp]
@@ -91,7 +94,7 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_get_timing", "pion_gpu_stage_part", "pion_gpu_set_comm_stream", "pion_gpu_set_jet",
     "pion_gpu_add_wind_source", "pion_gpu_get_wind_cells", "pion_gpu_get_wind_source_pos",
     "pion_gpu_wind_orbit_position", "pion_gpu_get_flags", "pion_gpu_add_rotating_wind_source",
-    "pion_gpu_wind_angle_tables",
+    "pion_gpu_wind_angle_tables", "pion_gpu_get_hll_switch", "pion_gpu_get_hll_screen_counts",
 ]
 
 
@@ -222,6 +225,18 @@ class GpuSim:
         out = np.zeros(self.ncell, dtype=np.uint8)
         self._chk(self.lib.pion_gpu_get_flags(self.h, out.ctypes.data), "get_flags")
         return out
+
+    def get_hll_switch(self):
+        """pion_gpu_get_hll_switch: the HLLD -> HLL switch per cell as the last stage's prepass left it (uint8, ncell_all)"""
+        out = np.zeros(self.ncell, dtype=np.uint8)
+        self._chk(self.lib.pion_gpu_get_hll_switch(self.h, out.ctypes.data), "get_hll_switch")
+        return out
+
+    def get_hll_screen_counts(self):
+        """pion_gpu_get_hll_screen_counts: (active blocks, blocks) of the last prepass; (-1, 0): it was the dense one"""
+        a, t = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.pion_gpu_get_hll_screen_counts(self.h, C.byref(a), C.byref(t)), "get_hll_screen_counts")
+        return a.value, t.value
 
     def set_jet(self, jetradius, jetstate):
         st = np.ascontiguousarray(jetstate, dtype=np.float64)
