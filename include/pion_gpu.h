@@ -68,7 +68,10 @@ extern "C" {
 #define PION_BC_DMACH 7   /* YP boundary of the double Mach reflection test */
 #define PION_BC_DMACH2 8  /* internal: fixed post-shock state in y<0, x<=1/6 */
 #define PION_BC_STWIND 9  /* internal: stellar-wind cells (fixed per-cell state) */
-#define PION_BC_SLAB 10   /* z face owned by a neighbouring GPU (halo exchange) */
+#define PION_BC_SLAB 10   /* face of the slab axis owned by a neighbouring GPU (halo exchange).  The slab axis is the
+                           * last axis: faces 4, 5 (ZN, ZP) of a 3-D grid, faces 2, 3 (YN, YP) of a 2-D grid, Cartesian
+                           * or cylindrical (z,R); on any other face, and on a 1-D grid, pion_gpu_create returns EINVAL.
+                           * A cylindrical slab other than the lowest has SLAB at YN and no axis. */
 #define PION_BC_JET 11    /* internal: jet inflow cells on the XN face (pion_gpu_set_jet) */
 #define PION_BC_JETREFLECT 13   /* reflecting wall behind a jet: v_n and the TANGENTIAL field change sign
                                  * (jetreflect_boundaries.cpp:32-62) */
@@ -151,7 +154,7 @@ void *pion_gpu_device_ptr(void *handle, int which);
 /* HIP stream all subsequent work of this handle is issued on (hipStream_t) */
 int pion_gpu_set_stream(void *handle, void *stream);
 /* Second HIP stream for pion_gpu_pack_halo / pion_gpu_unpack_halo (NULL: the compute stream).
- * The library orders pack after the compute stream's work so far and PION_STAGE_ZBOUNDARY after the
+ * The library orders pack after the compute stream's work so far and PION_STAGE_SLABBOUNDARY after the
  * last unpack; the caller's transfer (RCCL/MPI) must be enqueued on, or ordered with, this stream. */
 int pion_gpu_set_comm_stream(void *handle, void *stream);
 /* the handle's streams (hipStream_t): which = 0 compute, 1 comm */
@@ -310,18 +313,22 @@ int pion_gpu_set_glm_speeds(void *handle, double dt, double dx, double cr);
  * space_ooa: OA1 (first half step) or OA2; is_full_step: step==ooa (P=Ph). */
 int pion_gpu_stage(void *handle, double dt_stage, int space_ooa, int is_full_step);
 
-/* The same stage in two parts, so that a z-slab's halo exchange (MCMD_boundaries.cpp:122-237, which
- * the reference completes before calc_dynamics_dU starts) runs underneath most of the work:
- *   PION_STAGE_INTERIOR   the on-grid planes that read no z ghost plane; may be issued while the
- *                         z halo of the stencil array is still in flight;
- *   PION_STAGE_ZBOUNDARY  the nbc planes next to each z face; ordered after the last
- *                         pion_gpu_unpack_halo (comm stream) inside the library.
- * INTERIOR followed by ZBOUNDARY gives bit for bit the result of PION_STAGE_WHOLE (= pion_gpu_stage).
- * Configurations the split does not cover (1-D/2-D, H-correction, first-order scheme, <= 2*nbc
- * planes) do all the work in the ZBOUNDARY call. */
+/* The same stage in two parts, so that a slab's halo exchange (MCMD_boundaries.cpp:122-237, which
+ * the reference completes before calc_dynamics_dU starts) runs underneath most of the work.  The slab axis is
+ * the last axis of the grid; its "planes" are x-y planes of a 3-D grid and rows (along x) of a 2-D grid:
+ *   PION_STAGE_WHOLE         every on-grid plane of the slab axis, after the last unpacked halo;
+ *   PION_STAGE_INTERIOR      the on-grid planes [nbc, n - nbc) that read no ghost plane of the slab axis; may
+ *                            be issued while the halo of the stencil array is still in flight;
+ *   PION_STAGE_SLABBOUNDARY  the nbc planes next to each face of the slab axis (one launch for both strips);
+ *                            ordered after the last pion_gpu_unpack_halo / pion_gpu_halo_end (comm stream)
+ *                            inside the library.
+ * INTERIOR followed by SLABBOUNDARY gives bit for bit the result of PION_STAGE_WHOLE (= pion_gpu_stage).
+ * Configurations the split does not cover (1-D grids, 2-D grids not run by the rows kernel -- PION_ROWS_2D=0,
+ * nbc < 2 --, H-correction, first-order scheme, <= 2*nbc planes) do all the work in the SLABBOUNDARY call. */
 #define PION_STAGE_WHOLE 0
 #define PION_STAGE_INTERIOR 1
 #define PION_STAGE_ZBOUNDARY 2
+#define PION_STAGE_SLABBOUNDARY PION_STAGE_ZBOUNDARY
 int pion_gpu_stage_part(void *handle, double dt_stage, int space_ooa, int is_full_step, int part);
 
 /* time_integrator::advance_time (time_integrator.cpp:72-142) for OA1/OA1 and
@@ -331,18 +338,20 @@ int pion_gpu_advance_time(void *handle, double dt, double simtime);
 /* ---- slab decomposition (replaces decomposition/MCMD_control.cpp:231-309 and
  * comms/comm_mpi.cpp:287-636 for this path) -------------------------------- */
 
-/* Copy the nbc on-grid z-planes adjacent to face (4=ZN, 5=ZP) of `which`
- * (0=P,1=Ph) into a contiguous device buffer [nvar][nbc][ny_all][nx_all], or
+/* Copy the nbc on-grid planes of the slab axis adjacent to face (3-D: 4=ZN, 5=ZP; 2-D: 2=YN, 3=YP) of `which`
+ * (0=P,1=Ph) into a contiguous device buffer [nvar][nbc][ny_all][nx_all] (2-D: [nvar][nbc][nx_all]), or
  * write such a buffer into the ghost planes of that face. */
 long pion_gpu_halo_count(void *handle); /* doubles per halo buffer */
 /* In-place exchange (no pack / unpack kernels): in the [nvar][nz_all][ny_all][nx_all] layout the nbc planes
- * next to a z face are ONE contiguous run of count_per_var doubles per variable, so a transport can send
+ * next to a face of the slab axis (z planes in 3-D; in 2-D the nbc rows next to a y face, nbc * nx_all doubles)
+ * are ONE contiguous run of count_per_var doubles per variable, so a transport can send
  * from, and receive into, the state array directly (variable v: pointer + v * var_stride doubles):
- *   send_lo / send_hi  the first / last nbc on-grid planes (x/y ghosts included)
- *   recv_lo / recv_hi  the ZN / ZP ghost planes.
+ *   send_lo / send_hi  the first / last nbc on-grid planes (x/y ghosts included; 2-D: rows, x ghosts included)
+ *   recv_lo / recv_hi  the ghost planes of the lower / upper face (ZN / ZP; 2-D: YN / YP).
+ * EINVAL for a 1-D grid.
  * pion_gpu_halo_begin orders the communication stream after the compute stream's work so far (what
  * pion_gpu_pack_halo does first), pion_gpu_halo_end marks the point of the communication stream after
- * which the ghost planes are complete (what pion_gpu_unpack_halo does last): PION_STAGE_ZBOUNDARY and
+ * which the ghost planes are complete (what pion_gpu_unpack_halo does last): PION_STAGE_SLABBOUNDARY and
  * whole stages wait for it inside the library. */
 typedef struct {
   double *send_lo, *send_hi, *recv_lo, *recv_hi;

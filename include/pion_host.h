@@ -48,7 +48,9 @@ int pion_host_sim_add_rotating_wind_source(void *sim, const pion_gpu_wind_source
                                            double xi, int *id);
 int pion_host_sim_last_error(void *sim, char *buf, int len);
 
-/* ---- z-slab communicators (both return a pion_host::slab_comm*) */
+/* ---- slab communicators (both return a pion_host::slab_comm*).  A grid is cut along its slab axis, the last one:
+ * z of a 3-D grid, y of a 2-D grid (Cartesian or cylindrical (z,R)).  periodic_z: the global problem is periodic along the slab
+ * axis (rank 0 <-> world-1 exchange); physical faces of the slab axis apply on the end ranks only. */
 int pion_host_comm_unique_id(void *out128);                   /* ncclGetUniqueId on rank 0 */
 int pion_host_comm_create(int rank, int world, int periodic_z, const void *unique_id, int device, void **comm);   /* RCCL */
 int pion_host_comm_shm_create(int rank, int world, int periodic_z, const char *name, const struct pion_backend *backend,

@@ -32,6 +32,7 @@ RO, PG, VX, VY, VZ, BX, BY, BZ, SI = range(9)
 RHO, ERG, MMX, MMY, MMZ, BBX, BBY, BBZ, PSI = range(9)
 OA1, OA2 = 1, 2
 STAGE_WHOLE, STAGE_INTERIOR, STAGE_ZBOUNDARY = 0, 1, 2
+STAGE_SLABBOUNDARY = STAGE_ZBOUNDARY   # the boundary part of the slab axis: z planes (3-D), y rows (2-D)
 
 E_OK, E_INVAL, E_DEVICE, E_PHYSICS, E_NOMEM = 0, -1, -2, -3, -4
 

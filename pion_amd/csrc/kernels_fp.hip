@@ -620,7 +620,10 @@ __global__ __launch_bounds__(256) void k_cooling_dE(const StageArgs a)
   const int iz = (pz < np1) ? a.kz0 + (int)pz : a.kz2 + (int)(pz - np1);
   if (ix >= a.g.ng[0] || iy >= a.g.ng[1]) return;
   const long nc = a.g.ncell;
-  const long c = (long)(ix + a.g.nbc[0]) + a.g.sy * (iy + a.g.nbc[1]) + a.g.sz * (iz + a.g.nbc[2]);
+  // (a 2-D launch of the rows kernel: a.g.ng[1] rows per range and the "plane" of a strip is the first row of its
+  // range, rows_tiling.h "2-D row ranges")
+  const long c = (a.g.ndim == 2) ? (long)(ix + a.g.nbc[0]) + a.g.sy * (iy + iz + a.g.nbc[1])
+                                 : (long)(ix + a.g.nbc[0]) + a.g.sy * (iy + a.g.nbc[1]) + a.g.sz * (iz + a.g.nbc[2]);
   double dE = 0.0;
   if (a.flags[c] & 4 /*ISDOMAIN*/) {
     const double g = a.fc.gamma;
@@ -809,6 +812,24 @@ __global__ __launch_bounds__(256) void k_prepass_hlld(const PrepassArgs a)
   const unsigned pz = t / (gx * gy);
   i[2] = (pz < npl1) ? (int)(a.c0 / plane) + (int)pz : (int)(a.c2 / plane) + (int)(pz - npl1);
   if (i[0] >= a.g.nga[0] || i[1] >= a.g.nga[1]) return;
+  prepass_hlld_cell(a, i);
+}
+
+// 2-D grids, a part of a split stage: the cells of all-cell rows [c0, c1) / nga[0] and, if c3 > c2, [c2, c3) / nga[0]
+// (whole rows, x ghosts included), 64 x 4 threads per workgroup
+__global__ __launch_bounds__(256) void k_prepass_hlld_rows(const PrepassArgs a)
+{
+  const long row = a.g.nga[0];
+  const unsigned gx = (a.g.nga[0] + 63) / 64;
+  const unsigned nr1 = (unsigned)((a.c1 - a.c0) / row);
+  const unsigned nr = nr1 + ((a.c3 > a.c2) ? (unsigned)((a.c3 - a.c2) / row) : 0u);
+  const unsigned t = blockIdx.x;
+  int i[3];
+  i[0] = (int)((t % gx) * 64 + (threadIdx.x & 63));
+  const unsigned r = (t / gx) * 4 + (threadIdx.x >> 6);
+  if (i[0] >= a.g.nga[0] || r >= nr) return;
+  i[1] = (r < nr1) ? (int)(a.c0 / row) + (int)r : (int)(a.c2 / row) + (int)(r - nr1);
+  i[2] = 0;
   prepass_hlld_cell(a, i);
 }
 
@@ -1072,7 +1093,15 @@ int launch_prepass(const PrepassArgs &a, hipStream_t s)
     const long plane = (long)a.g.nga[0] * a.g.nga[1];
     const unsigned npl = (unsigned)((a.c1 - a.c0) / plane) + ((a.c3 > a.c2) ? (unsigned)((a.c3 - a.c2) / plane) : 0u);
     const unsigned ntile = (unsigned)((a.g.nga[0] + 63) / 64) * ((a.g.nga[1] + 3) / 4) * npl;
-    if (a.g.ndim == 3 && a.g.cyl == 0 && !a.divv && !a.gradp && a.c3 <= a.c2 && npl >= PION_PREPASS_ZC
+    if (a.g.ndim == 2 && (a.c0 != 0 || a.c1 != a.g.ncell)) {
+      // a part of a split 2-D stage (pion_gpu.hip): whole rows
+      const long row = a.g.nga[0];
+      const unsigned nr = (unsigned)((a.c1 - a.c0) / row) + ((a.c3 > a.c2) ? (unsigned)((a.c3 - a.c2) / row) : 0u);
+      if (nr > 0)
+        hipLaunchKernelGGL(k_prepass_hlld_rows, dim3((unsigned)((a.g.nga[0] + 63) / 64) * ((nr + 3) / 4)), dim3(256), 0,
+                           s, a);
+    }
+    else if (a.g.ndim == 3 && a.g.cyl == 0 && !a.divv && !a.gradp && a.c3 <= a.c2 && npl >= PION_PREPASS_ZC
         && a.g.ncell * 8L < (1L << 32)) {
       const unsigned nch = (npl + PION_PREPASS_ZC - 1) / PION_PREPASS_ZC;
       const unsigned nt = (unsigned)((a.g.nga[0] + 61) / 62) * ((a.g.nga[1] + 3) / 4) * nch;   // 62 cells per wavefront along x

@@ -35,7 +35,8 @@ struct BCArgs {
 // periodic copies (periodic_boundaries.cpp:42-50, corner cells through already filled ghosts) ends with
 // every ghost cell holding the on-grid cell at its coordinates wrapped axis by axis, so the wrapped
 // cell can be read directly: the same values, one launch instead of six.  z faces of kind SLAB
-// (neighbour rank) are left alone: then only ghosts on on-grid z planes are filled.
+// (neighbour rank) are left alone: then only ghosts on on-grid z planes are filled.  (A 2-D grid with SLAB y faces
+// goes through k_bc_all.)
 __global__ __launch_bounds__(256) void k_bc_periodic_all(double *T, const GridDesc g, const int nvar, const int zwrap,
                                                          const int skipx)
 {
@@ -93,7 +94,8 @@ __global__ __launch_bounds__(256) void k_bc_periodic_all(double *T, const GridDe
 // the same values as the six launches, without their ordering.  psi of GLM-MHD follows its own chain: outflow
 // and one-way faces take -psi of the MIRROR cell (outflow_boundaries.cpp:140-152), everything else of the copy
 // source.  Then the internal DMR2 boundary, which the reference applies last (double_Mach_ref_boundaries.cpp:98-147).
-// z faces of kind SLAB (neighbour rank) are left alone.
+// Faces of kind SLAB (neighbour rank; the faces of the slab axis, z in 3-D and y in 2-D) are left alone: the x (and, in
+// 3-D, y) ghosts are still filled over the rows / planes the rank owns, so that what it sends carries them.
 struct BCAllArgs {
   GridDesc g;
   double *T;
@@ -401,11 +403,13 @@ __global__ void k_wind(double *T, const long *idx, const double *states, const l
   for (int v = 0; v < nvar; v++) T[v * nc + c] = states[t * nvar + v];
 }
 
-// halo planes: buffer layout [nvar][nbc][ny_all][nx_all]
+// halo planes of the slab axis (the last axis: z planes in 3-D, y rows in 2-D): buffer layout
+// [nvar][nbc][ny_all][nx_all] (2-D: [nvar][nbc][nx_all])
 __global__ void k_halo(double *A, double *buf, const GridDesc g, const int nvar, const int face, const int pack)
 {
-  const long plane = (long)g.nga[0] * g.nga[1];
-  const long per = plane * g.nbc[2];
+  const int sa = g.ndim - 1;
+  const long plane = (sa == 2) ? (long)g.nga[0] * g.nga[1] : (long)g.nga[0];
+  const long per = plane * g.nbc[sa];
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= per * nvar) return;
   const int v = (int)(t / per);
@@ -413,8 +417,8 @@ __global__ void k_halo(double *A, double *buf, const GridDesc g, const int nvar,
   const int k = (int)(r / plane);
   const long xy = r % plane;
   int izall;
-  if (pack) izall = (face == 4) ? g.nbc[2] + k : g.ng[2] + k;              // on-grid planes next to the face
-  else izall = (face == 4) ? k : g.nbc[2] + g.ng[2] + k;                   // ghost planes of the face
+  if (pack) izall = (face == 2 * sa) ? g.nbc[sa] + k : g.ng[sa] + k;       // on-grid planes next to the face
+  else izall = (face == 2 * sa) ? k : g.nbc[sa] + g.ng[sa] + k;            // ghost planes of the face
   const long c = xy + plane * izall;
   if (pack) buf[t] = A[v * g.ncell + c];
   else A[v * g.ncell + c] = buf[t];
@@ -1249,6 +1253,9 @@ int pion_gpu_create(const pion_gpu_config *cfg, int device, void **handle)
     return PION_GPU_EINVAL;
   for (int d = 0; d < 2 * cfg->ndim; d++)
     if (cfg->bc_type[d] == PION_BC_AXISYMMETRIC && !(cfg->coord_sys == 2 && d == 2)) return PION_GPU_EINVAL;
+  // a face owned by a neighbouring GPU: the two faces of the slab axis (the last axis) of a 3-D or 2-D grid only
+  for (int d = 0; d < 2 * cfg->ndim; d++)
+    if (cfg->bc_type[d] == PION_BC_SLAB && !(cfg->ndim >= 2 && d / 2 == cfg->ndim - 1)) return PION_GPU_EINVAL;
   const int base = (cfg->eqntype == PION_EQEUL) ? 5 : (cfg->eqntype == PION_EQMHD ? 8 : (cfg->eqntype == PION_EQGLM ? 9 : -1));
   if (base < 0 || cfg->nvar != base + cfg->ntracer || cfg->ntracer > PION_MAX_NTR) return PION_GPU_EINVAL;
   if (cfg->sp_ooa == 2 && cfg->nbc < 2) return PION_GPU_EINVAL;
@@ -2252,13 +2259,16 @@ int pion_gpu_set_glm_speeds(void *handle, double dt, double dx, double cr)
   return 0;
 }
 
-// One stage, or a part of one (PION_STAGE_WHOLE / _INTERIOR / _ZBOUNDARY).  The split lets the z-halo
-// exchange of a slab run under the interior: the interior part reads no z ghost plane, the z-boundary
-// part (the nbc on-grid planes next to each z face) waits for the unpacked halo.
+// One stage, or a part of one (PION_STAGE_WHOLE / _INTERIOR / _SLABBOUNDARY).  The split lets the halo
+// exchange of a slab run under the interior: the interior part reads no ghost plane of the slab axis (the last
+// axis: z planes in 3-D, y rows in 2-D), the boundary part (the nbc on-grid planes / rows next to each face of
+// that axis) waits for the unpacked halo.
+static inline int slab_axis(const Handle *h) { return h->g.ndim - 1; }
 static bool stage_can_split(const Handle *h)
 {
-  return h->use_march != 0 && !h->deta && h->g.ndim == 3
-         && h->g.ng[2] > 2 * h->g.nbc[2] && !(h->cfg.tm_ooa == 1 && h->cfg.sp_ooa == 1);
+  const int sa = slab_axis(h);
+  return h->use_march != 0 && !h->deta && (h->g.ndim == 3 || h->g.ndim == 2)
+         && h->g.ng[sa] > 2 * h->g.nbc[sa] && !(h->cfg.tm_ooa == 1 && h->cfg.sp_ooa == 1);
 }
 
 // min of the cooling time over the state the full step has just written (P), into ddt[1]: k_dt_mp
@@ -2321,7 +2331,9 @@ static bool screen_admitted(Handle *h)
   return true;
 }
 
-// planes [kz0,kz1) and, if kz3 > kz2, also [kz2,kz3) (the two z-boundary strips go out as ONE launch)
+// planes [kz0,kz1) and, if kz3 > kz2, also [kz2,kz3) (the two z-boundary strips go out as ONE launch).  2-D grids
+// run by the rows kernel: the same with on-grid ROWS (the slab axis is y); other 2-D / 1-D grids: whole stages only,
+// the ranges are not read.
 static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_step, int kz0, int kz1,
                         bool first, bool last, int kz2 = 0, int kz3 = 0, hipStream_t ls = 0, bool use_ls = false)
 {
@@ -2363,8 +2375,10 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
       p.scr_count = h->dscr_count;
     }
     h->last_prepass_screened = (p.hsum != nullptr);
+    const int sa = slab_axis(h);
+    const long sst = (sa == 2) ? h->g.sz : h->g.sy;   // cells per plane (3-D) / row (2-D) of the slab axis
     if (!(first && last)) {
-      const int nb = h->g.nbc[2], nz = h->g.ng[2];
+      const int nb = h->g.nbc[sa], nz = h->g.ng[sa];
       int lo = kz0 - 1, hi = kz1 + 1;        // on-grid plane numbers [lo,hi): the interior part
       if (kz0 == 0) {                        // lower z-boundary part: the interior part did nb-1 ..
         lo = -1;
@@ -2374,14 +2388,14 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
         lo = nz - nb + 1;
         hi = nz + 1;
       }
-      p.c0 = (long)(lo + nb) * h->g.sz;
-      p.c1 = (long)(hi + nb) * h->g.sz;
+      p.c0 = (long)(lo + nb) * sst;
+      p.c1 = (long)(hi + nb) * sst;
     }
     if (kz3 > kz2) {
       // second strip (the upper z boundary): its own plane range of flags, same launch
-      const int nb = h->g.nbc[2], nz = h->g.ng[2];
-      p.c2 = (long)(nz - nb + 1 + nb) * h->g.sz;
-      p.c3 = (long)(nz + 1 + nb) * h->g.sz;
+      const int nb = h->g.nbc[sa], nz = h->g.ng[sa];
+      p.c2 = (long)(nz - nb + 1 + nb) * sst;
+      p.c3 = (long)(nz + 1 + nb) * sst;
     }
     time_begin(h, 1);
     rc = cfg.strict_fp ? fp_strict::launch_prepass(p, ls) : fp_fast::launch_prepass(p, ls);
@@ -2425,6 +2439,25 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
   a.kz1 = kz1;
   a.kz2 = kz2;
   a.kz3 = (kz3 > kz2) ? kz3 : kz2;
+  const bool rows2d = (h->g.ndim == 2 && h->use_march != 0);
+  if (h->g.ndim < 3) {
+    a.kz0 = 0;
+    a.kz1 = 1;
+    a.kz2 = a.kz3 = 0;
+  }
+  if (rows2d) {
+    // 2-D row ranges (rows_tiling.h, "2-D row ranges"): the kernels see a grid of as many rows as a range has, whose
+    // one "plane" per range is numbered by the range's first row
+    if (kz3 > kz2 && kz3 - kz2 != kz1 - kz0) {
+      h->err = "stage: the two row strips of a 2-D launch must have the same number of rows";
+      return PION_GPU_EINVAL;
+    }
+    a.g.ng[1] = kz1 - kz0;
+    a.kz0 = kz0;
+    a.kz1 = kz0 + 1;
+    a.kz2 = kz2;
+    a.kz3 = (kz3 > kz2) ? kz2 + 1 : kz2;
+  }
   a.zslope_lds = h->zslope_lds;
   a.plain_cells = any_wind(h) ? 0 : 1;
   a.dE = nullptr;
@@ -2438,8 +2471,8 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
     Rows2PlanIn p;
     p.ndim = h->g.ndim;
     p.nx = h->g.ng[0];
-    p.ny = h->g.ng[1];
-    p.np = kz1 - kz0;
+    p.ny = a.g.ng[1];                        // (2-D: the rows of the range, which is what the launch tiles)
+    p.np = (h->g.ndim == 3) ? kz1 - kz0 : 1;
     p.ncu = h->ncu;
     p.nv = cfg.nvar;
     p.euler = (cfg.eqntype == PION_EQEUL);
@@ -2539,17 +2572,18 @@ static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_s
 int pion_gpu_stage_part(void *handle, double dt_stage, int space_ooa, int is_full_step, int part)
 {
   Handle *h = use(handle);
-  const int nz = h->g.ng[2], nb = h->g.nbc[2];
+  // planes (3-D) / rows (2-D) of the slab axis; a 1-D grid has neither and never splits
+  const int nz = h->g.ng[slab_axis(h) > 0 ? slab_axis(h) : 2], nb = h->g.nbc[slab_axis(h) > 0 ? slab_axis(h) : 2];
   if (part == PION_STAGE_WHOLE) {
     if (int rc = order_after_unpack(h)) return rc;
     return stage_launch(h, dt_stage, space_ooa, is_full_step, 0, nz, true, true);
   }
   const bool split = stage_can_split(h);
   if (part == PION_STAGE_INTERIOR) {
-    if (!split) return 0;  // everything happens in the z-boundary call
+    if (!split) return 0;  // everything happens in the boundary call
     return stage_launch(h, dt_stage, space_ooa, is_full_step, nb, nz - nb, true, false);
   }
-  if (part != PION_STAGE_ZBOUNDARY) return PION_GPU_EINVAL;
+  if (part != PION_STAGE_SLABBOUNDARY) return PION_GPU_EINVAL;
   if (split && h->ev_pre_valid && h->ev_unpacked_valid) {
     // Two-stream mode: the strips (4 of the slab's planes: a launch of ~2100 short wavefronts on 2048 slots)
     // go to a third stream that waits for the halo and for the point of the compute stream just before the
@@ -2603,11 +2637,13 @@ int pion_gpu_advance_time(void *handle, double dt, double simtime)
 long pion_gpu_halo_count(void *handle)
 {
   Handle *h = use(handle);
-  return (long)h->cfg.nvar * h->g.nbc[2] * h->g.nga[0] * h->g.nga[1];
+  if (h->g.ndim == 2) return (long)h->cfg.nvar * h->g.nbc[1] * h->g.nga[0];   // rows of the slab axis y
+  return (long)h->cfg.nvar * h->g.nbc[2] * h->g.nga[0] * h->g.nga[1];         // (0 for a 1-D grid)
 }
 static int halo_go(Handle *h, int which, int face, void *dbuf, int pack)
 {
-  if (h->cfg.ndim != 3 || (face != 4 && face != 5)) return PION_GPU_EINVAL;
+  const int sa = slab_axis(h);
+  if (sa < 1 || (face != 2 * sa && face != 2 * sa + 1)) return PION_GPU_EINVAL;
   double *A = (which == 0) ? h->dP : h->dPh;
   const long n = pion_gpu_halo_count(h);
   hipStream_t cs = h->comm_stream ? h->comm_stream : h->stream;
@@ -2630,9 +2666,11 @@ static int halo_go(Handle *h, int which, int face, void *dbuf, int pack)
 int pion_gpu_halo_spans(void *handle, int which, pion_gpu_halo_spans_t *out)
 {
   Handle *h = use(handle);
-  if (h->cfg.ndim != 3 || !out) return PION_GPU_EINVAL;
+  const int sa = slab_axis(h);
+  if (sa < 1 || !out) return PION_GPU_EINVAL;
   double *A = (which == 0) ? h->dP : h->dPh;
-  const long nb = h->g.nbc[2], nz = h->g.ng[2], sz = h->g.sz;
+  // (sz: cells per plane of the slab axis -- an x-y plane in 3-D, a row with its x ghosts in 2-D)
+  const long nb = h->g.nbc[sa], nz = h->g.ng[sa], sz = (sa == 2) ? h->g.sz : h->g.sy;
   out->recv_lo = A;                       // ghost planes 0 .. nb-1
   out->send_lo = A + nb * sz;             // first on-grid planes
   out->send_hi = A + nz * sz;             // last on-grid planes (all-cell planes nz .. nz+nb-1)

@@ -10,6 +10,18 @@
 // of a wavefront idle, so a "remainder" wavefront packs the remainders of `spw` consecutive row groups side by
 // side, each in a segment of rem + 2 lanes with its own two halo lanes (the x shuffles only ever cross a segment
 // boundary into a halo lane).  y: groups of a.rows consecutive rows per wavefront.
+//
+// 2-D row ranges.  A 2-D launch has one "plane" and no z part; it updates a RANGE of on-grid rows [ky0, ky1) and, for
+// the two boundary strips of a slab cut along y, a second range [ky2, ky3) of the same length.  The launcher
+// (stage_launch, pion_gpu.hip) encodes a range in the members the geometry already reads, so nothing here changes:
+//   a.g.ng[1] = ky1 - ky0            the rows that are tiled: rows_tiling, rows2_nblocks and rows2_pick_rows_2d_rule
+//                                    are sized from the range, row groups start at its first row;
+//   a.kz0 = ky0, a.kz1 = ky0 + 1     one chunk (zchunk >= 1, nzb = 0) whose "plane" number k0 is the range's first row;
+//   a.kz2 = ky2, a.kz3 = ky2 + 1     the second range as a second chunk (empty when kz3 <= kz2).
+// A whole stage is the range [0, ny): ng[1] = ny, kz0 = 0, kz1 = 1, which is what 2-D launches always passed.
+// rows2_decode returns j0 = jg * R RELATIVE to the range and k0 = the range's first row; the kernels (k_stage_rows2,
+// k_cooling_dE) add k0 to the row and use plane 0 when a.g.ndim == 2 -- that one step is theirs alone (the argument
+// structs of the host-side probe carry no ndim), so the probe pins the tiling of a range, not its placement.
 #ifndef PION_ROWS_TILING_H
 #define PION_ROWS_TILING_H
 

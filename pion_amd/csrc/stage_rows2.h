@@ -250,6 +250,13 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
   extern __shared__ double lds[];
 
   const int R = a.rows;
+  // 2-D grids run the same kernel without its z part: one "plane", a group of R rows per wavefront marched along y with
+  // the flux and the slope carried in registers (2 + 1/R Riemann solves per cell), no LDS.  A 2-D launch updates a RANGE
+  // of on-grid rows (rows_tiling.h, "2-D row ranges"): a.g.ng[1] is the number of rows of a range, and the "plane" of a
+  // chunk is the first row of its range -- [0, ny) for a whole stage, the nbc rows next to each y face for the two
+  // boundary strips of a slab.  Row groups start at the first row of the range; the lower y face of a group's first row
+  // comes from the lower mode of the y task whatever lies below it.
+  const bool noz = (a.g.ndim == 2);
   const RowsTiling tl = rows_tiling(a);
   const int nyg = tl.nyg;
   const int nzc1 = (a.nzb > 0) ? a.nzb : (a.kz1 - a.kz0 + a.zchunk - 1) / a.zchunk;
@@ -257,7 +264,9 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
   // the wavefront number is uniform: say so, and the tile / row / plane loops run on the scalar unit
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   // (rows2_decode, rows_tiling.h, restates this decode for the tests' host-side coverage probe: kept inline here, because
-  // the kernel compiled from the shared function is not instruction for instruction the same -- keep the two equal)
+  // the kernel compiled from the shared function is not instruction for instruction the same -- keep the two equal.
+  // One step is the kernel's alone: on a 2-D grid it adds the chunk's k0, the first row of its range, to j0 and then
+  // uses plane 0; rows2_decode returns j0 relative to the range and k0 as it is -- rows_tiling.h, "2-D row ranges")
   // Workgroup -> (x-y tile group, plane chunk).  Workgroups go to the XCDs round robin (blockIdx % 8): each XCD
   // takes an eighth of the x-y tiles -- y-adjacent row groups, whose halo rows are each other's own rows, share its
   // L2 -- through ALL plane chunks, in chunk order: with uneven chunks (long first) every XCD ends on the short ones.
@@ -296,9 +305,8 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
   // (SCR) x block of the wavefront's cells: lane 0 is the halo lane left of the first cell of its x tile
   const int scr_bx = SCR ? __builtin_amdgcn_readfirstlane(ix + 1) / PION_SCR_BX : 0;
   if (ix > a.g.ng[0]) ix = a.g.ng[0];
-  const int j0 = jg * R;
   const int nrows = (jg_first * R + R <= a.g.ng[1]) ? R : a.g.ng[1] - jg_first * R;
-  const int nrows_l = (j0 + R <= a.g.ng[1]) ? R : a.g.ng[1] - j0;
+  const int nrows_l = (jg * R + R <= a.g.ng[1]) ? R : a.g.ng[1] - jg * R;
   int k0, k1;
   if (a.nzb > 0 && cz < nzc1) {
     zchunk_bounds(a.kz1 - a.kz0, a.zcmax, cz, &k0, &k1);   // (scalar unit: cz is uniform)
@@ -310,6 +318,12 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
     const int kend = (cz < nzc1) ? a.kz1 : a.kz3;
     k1 = (k0 + a.zchunk < kend) ? k0 + a.zchunk : kend;
   }
+  // the lane's first row: in 2-D counted from the first row of the chunk's range (uniform), and the one plane is plane 0
+  const int j0 = jg * R + (noz ? k0 : 0);
+  if (noz) {
+    k0 = 0;
+    k1 = 1;
+  }
 
   const long nc = a.g.ncell, sy = a.g.sy, sz = a.g.sz;
   const long ncb = nc * 8, syb = sy * 8, szb = sz * 8;   // byte strides (uniform)
@@ -317,9 +331,6 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
   const char *const Hb = reinterpret_cast<const char *>(a.hllflag);
   const double g = a.fc.gamma, dx = a.g.dx, dt = a.dt;
   const bool oa2 = (OAMODE == 0) ? (a.space_ooa == 2) : (OAMODE == 2);
-  // 2-D Cartesian grids run the same kernel without its z part: one "plane", a group of R rows per wavefront marched
-  // along y with the flux and the slope carried in registers (2 + 1/R Riemann solves per cell), no LDS
-  const bool noz = (a.g.ndim == 2);
   const double thr = PION_VERY_TINY_VALUE * dx * dx;   // AvgFalle's zero test on raw differences (fast build)
   const bool hcorr = PLAIN ? false : (a.fc.artvisc == AV_HCORRECTION || a.fc.artvisc == AV_HCORR_FKJ98);
   // first-order stages read their stencil from the start-of-step array (time_integrator.cpp:151-250:

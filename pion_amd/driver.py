@@ -3,8 +3,9 @@ time_integrator (source/sim_control/sim_control.cpp:202-281, calc_timestep.cpp:6
 time_integrator.cpp:72-142), driving a stage-granular backend.
 
 The backend is anything with the pion_gpu call shapes (pion_amd.lib.GpuSim on the
-product path).  With `comm` set (a pion_amd.slab.SlabComm) the grid is a z-slab of
-a larger domain: the ghost planes of the two z faces are exchanged with the
+product path).  With `comm` set (a pion_amd.slab.SlabComm) the grid is a slab of
+a larger domain, cut along its last axis (z in 3-D, y in 2-D; the text says z): the
+ghost planes of the two z faces are exchanged with the
 neighbouring ranks after every stage and the time step is min-reduced over ranks,
 replacing source/decomposition/MCMD_control.cpp:231-309, comms/comm_mpi.cpp:287-636
 and sim_control_MPI.cpp:482-583 for this path.
@@ -16,6 +17,12 @@ class SimControl:
     def __init__(self, sim, cfg, comm=None, finishtime=1e300, min_timestep=0.0):
         self.sim = sim
         self.cfg = cfg
+        if comm is not None:
+            from . import slab
+            if isinstance(comm, slab.SlabComm) and cfg.ndim != 3:
+                raise NotImplementedError("slab.SlabComm (the torch.distributed transport) exchanges the z faces of a "
+                                          "3-D grid only; run a %d-D slab through host_rccl.HostSim (the C++ loop)"
+                                          % cfg.ndim)
         self.comm = comm
         self.simtime = 0.0
         self.timestep = 0
@@ -59,7 +66,7 @@ class SimControl:
             return
         self.sim.stage_part(dt, space_ooa, is_full, abi.STAGE_INTERIOR)
         self.comm.finish(self.sim)
-        self.sim.stage_part(dt, space_ooa, is_full, abi.STAGE_ZBOUNDARY)
+        self.sim.stage_part(dt, space_ooa, is_full, abi.STAGE_SLABBOUNDARY)
 
     def finish_halo(self):
         """Complete a halo exchange still in flight (before the state is read back)."""

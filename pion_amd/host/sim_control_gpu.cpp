@@ -52,7 +52,7 @@ int sim_control_gpu::stage(double dt, int space_ooa, int is_full)
   if (!comm_) return be_->stage(h_, dt, space_ooa, is_full);
   int err = be_->stage_part(h_, dt, space_ooa, is_full, PION_STAGE_INTERIOR);
   err += comm_->finish();
-  err += be_->stage_part(h_, dt, space_ooa, is_full, PION_STAGE_ZBOUNDARY);
+  err += be_->stage_part(h_, dt, space_ooa, is_full, PION_STAGE_SLABBOUNDARY);
   return err;
 }
 

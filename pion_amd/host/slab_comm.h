@@ -1,6 +1,7 @@
-// slab_comm.h -- what sim_control_gpu needs from a z-slab communicator (one process per GPU): the halo
+// slab_comm.h -- what sim_control_gpu needs from a slab communicator (one process per GPU): the halo
 // exchange of BC_update_BCMPI (boundaries/MCMD_boundaries.cpp:122-237) split into a start and a finish around the
 // interior part of a stage, and the global minimum of the time step (sim_control_MPI.cpp:503-504).
+// The slab axis is the grid's last axis: z in 3-D, y in 2-D, where the "planes" below are rows.
 //
 // Two implementations:
 //   slab_comm_rccl  (slab_comm_rccl.h)  device-resident transfers over RCCL / xGMI -- the production transport;
@@ -20,10 +21,10 @@ class slab_comm {
   virtual ~slab_comm() {}
   // bind to the backend handle whose state is exchanged; must precede start()
   virtual int attach(void *handle) = 0;
-  // first half: the on-grid planes next to the internal z faces of array `which` (0 = P, 1 = Ph) leave.
+  // first half: the on-grid planes next to the internal slab-axis faces of array `which` (0 = P, 1 = Ph) leave.
   // Returns at once.
   virtual int start(int which) = 0;
-  // second half: the ghost planes are (ordered to be) filled before the z-boundary part of the next stage
+  // second half: the ghost planes are (ordered to be) filled before the slab-boundary part of the next stage
   virtual int finish() = 0;
   // global minimum of the device-resident {t_dyn, t_mp}: request_min() starts it (right after the full-step
   // stage), allreduce_min() waits for it -- the single host synchronisation of a step

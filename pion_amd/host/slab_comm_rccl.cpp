@@ -40,7 +40,8 @@ slab_comm_rccl::slab_comm_rccl(int rank, int world, bool periodic_z, const void 
     : rank_(rank), world_(world), device_(device), up_(-1), down_(-1), comm_(nullptr), cstream_(nullptr), h_(nullptr),
       pending_(-1), requested_(false)
 {
-  // decomposeDomain along z (MCMD_control.cpp:231-309): rank r is below r+1; periodic wrap 0 <-> world-1
+  // decomposeDomain along the slab axis (the grid's last: z in 3-D, y in 2-D; MCMD_control.cpp:231-309): rank r is
+  // below r+1; periodic_z = periodic along that axis: wrap 0 <-> world-1
   if (periodic_z || rank < world - 1) up_ = (rank + 1) % world;
   if (periodic_z || rank > 0) down_ = (rank - 1 + world) % world;
   if (world == 1 && !periodic_z) up_ = down_ = -1;
@@ -78,7 +79,8 @@ int slab_comm_rccl::attach(void *gpu_handle)
   return pion_gpu_set_comm_stream(h_, cstream_);
 }
 
-// The nbc planes next to a z face are one contiguous run per variable of the SoA state, so they are sent
+// The nbc planes next to a face of the slab axis (3-D: z planes; 2-D: y rows with their x ghosts) are one
+// contiguous run per variable of the SoA state, so they are sent
 // from and received into the state array itself: no pack / unpack kernels, no staging buffers.  While the
 // transfer is in flight the compute stream runs the INTERIOR part of the next stage, which reads no z ghost
 // plane and writes the other array.

@@ -1,4 +1,5 @@
-// slab_comm_rccl.h -- z-slab halo exchange and time-step reduction over RCCL, driven from C++.
+// slab_comm_rccl.h -- slab halo exchange and time-step reduction over RCCL, driven from C++.  The slab axis is the
+// grid's last axis: z in 3-D, y in 2-D.
 //
 // Replaces, for the flux-update path on one node (one process per GPU), the reference's
 //   comm_mpi::send_cell_data / receive_cell_data        source/comms/comm_mpi.cpp:287-425
@@ -27,7 +28,7 @@ namespace pion_host {
 class slab_comm_rccl : public slab_comm {
  public:
   // unique_id: the 128 bytes of an ncclUniqueId made by rank 0 (get_unique_id) and handed to every
-  // rank by the launcher.  periodic_z: the global z faces are periodic (rank 0 <-> world-1 exchange).
+  // rank by the launcher.  periodic_z: the global faces of the slab axis are periodic (rank 0 <-> world-1 exchange).
   // world == 1 with periodic_z is the loop-back case: the rank is its own neighbour (RCCL send/recv to
   // self), which reproduces the single-domain periodic run bit for bit.
   slab_comm_rccl(int rank, int world, bool periodic_z, const void *unique_id, int device);
@@ -38,7 +39,7 @@ class slab_comm_rccl : public slab_comm {
 
   // create the communication stream and register it (pion_gpu_set_comm_stream); must precede start()
   int attach(void *gpu_handle) override;
-  // BC_update_BCMPI, first half: pack the on-grid planes next to the internal z faces of array `which`
+  // BC_update_BCMPI, first half: pack the on-grid planes next to the internal slab-axis faces of array `which`
   // (0 = P, 1 = Ph) and enqueue the grouped send / recv.  Returns at once.
   int start(int which) override;
   // second half: unpack into the ghost planes (communication stream; the library orders the

@@ -48,7 +48,8 @@ slab_comm_shm::slab_comm_shm(int rank, int world, bool periodic_z, const char *n
 {
   if (world < 1 || rank < 0 || rank >= world || name_.empty() || name_[0] != '/')
     throw std::runtime_error("slab_comm_shm: bad rank / world / segment name (\"/name\")");
-  // decomposeDomain along z (MCMD_control.cpp:231-309): rank r is below r+1; periodic wrap 0 <-> world-1
+  // decomposeDomain along the slab axis (the grid's last: z in 3-D, y in 2-D; MCMD_control.cpp:231-309): rank r is
+  // below r+1; periodic_z = periodic along that axis: wrap 0 <-> world-1
   if (periodic_z || rank < world - 1) up_ = (rank + 1) % world;
   if (periodic_z || rank > 0) down_ = (rank - 1 + world) % world;
   if (world == 1 && !periodic_z) up_ = down_ = -1;
@@ -78,7 +79,7 @@ int slab_comm_shm::attach(void *handle)
   h_ = handle;
   count_ = be_->halo_count(h_);
   if (count_ <= 0) {
-    err_ = "halo_count: not a 3-D slab";
+    err_ = "halo_count: not a 3-D or 2-D slab";
     return PION_GPU_EINVAL;
   }
   box_bytes_ = ((64 + (size_t)count_ * sizeof(double)) + 63) / 64 * 64;

@@ -70,6 +70,9 @@ def load_library():
     lib.pion_gpu_halo_count.restype = C.c_long
     lib.pion_gpu_pack_halo.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.pion_gpu_unpack_halo.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.pion_gpu_halo_spans.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.pion_gpu_halo_begin.argtypes = [C.c_void_p]
+    lib.pion_gpu_halo_end.argtypes = [C.c_void_p]
     lib.pion_gpu_interface_flux.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pion_gpu_cooling_update.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp]
     lib.pion_gpu_cooling_edot.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
@@ -100,6 +103,12 @@ EXPORTED_SYMBOLS = [
 
 def _p(a):
     return a.ctypes.data_as(_dp)
+
+
+class HaloSpans(C.Structure):
+    """pion_gpu_halo_spans_t (include/pion_gpu.h)"""
+    _fields_ = [("send_lo", C.c_void_p), ("send_hi", C.c_void_p), ("recv_lo", C.c_void_p), ("recv_hi", C.c_void_p),
+                ("count_per_var", C.c_long), ("var_stride", C.c_long), ("nvar", C.c_int)]
 
 
 class GpuSim:
@@ -279,6 +288,20 @@ class GpuSim:
 
     def unpack_halo(self, which, face, dbuf_ptr):
         self._chk(self.lib.pion_gpu_unpack_halo(self.h, which, face, C.c_void_p(dbuf_ptr)), "unpack_halo")
+
+    def halo_spans(self, which):
+        """pion_gpu_halo_spans: device addresses of the nbc planes (2-D: rows) next to the two faces of the slab axis
+        of array `which` (0 = P, 1 = Ph): dict send_lo / send_hi / recv_lo / recv_hi (addresses), count_per_var,
+        var_stride (doubles), nvar"""
+        sp = HaloSpans()
+        self._chk(self.lib.pion_gpu_halo_spans(self.h, which, C.byref(sp)), "halo_spans")
+        return {k: getattr(sp, k) for k, _ in HaloSpans._fields_}
+
+    def halo_begin(self):
+        self._chk(self.lib.pion_gpu_halo_begin(self.h), "halo_begin")
+
+    def halo_end(self):
+        self._chk(self.lib.pion_gpu_halo_end(self.h), "halo_end")
 
     # --- seams
     def interface_flux(self, axis, Pl, Pr, aux=None, dt=1.0):

@@ -1,4 +1,6 @@
-"""z-slab decomposition over the GPUs of one node (one process per GPU).
+"""Slab decomposition over the GPUs of one node (one process per GPU), along the last axis of the grid: z of a 3-D
+grid, y of a 2-D grid (Cartesian, or R of a cylindrical (z,R) grid).  The text below says z and planes; for a 2-D grid
+read y and rows (a row with its x ghosts).
 
 Replaces, for this path, the reference's source/decomposition/MCMD_control.cpp:231-309
 (slab decomposition along one axis) and the packed MPI halo exchange of
@@ -17,33 +19,52 @@ that was just written (Ph after a half step, P after a full step) is the one exc
 from . import abi
 
 
+def slab_axis(cfg):
+    """The axis a grid is cut along: its last one (2: z of a 3-D grid, 1: y of a 2-D grid)."""
+    if cfg.ndim not in (2, 3):
+        raise ValueError("slab decomposition needs a 2-D or 3-D grid")
+    return cfg.ndim - 1
+
+
+def slab_periodic(cfg_global):
+    """Is the global problem periodic along its slab axis?  (the `periodic` / `periodic_z` flag of the transports)"""
+    return cfg_global.bc_type[2 * slab_axis(cfg_global)] == abi.BC_PERIODIC
+
+
 def slab_config(cfg_global, rank, world):
-    """Per-rank configuration of a z-slab of the global problem."""
+    """Per-rank configuration of a slab of the global problem: ng and xmin of the slab axis, BC_SLAB on the faces a
+    neighbour owns.  The physical faces of the slab axis stay on the end ranks only: the axis of a cylindrical grid and
+    the internal DMR2 cells (below y = 0) are rank 0's, the time-dependent DMACH face is the last rank's.  The slab
+    computes positions from its own xmin (DESIGN s5, "2-D grids": exact for dyadic dx and xmin)."""
     import copy
-    if cfg_global.ndim != 3:
-        raise ValueError("slab decomposition needs a 3-D grid")
-    nz = cfg_global.ng[2]
+    ax = slab_axis(cfg_global)
+    nz = cfg_global.ng[ax]
     if nz % world != 0:
-        raise ValueError("NGridZ=%d not divisible by %d ranks" % (nz, world))
+        raise ValueError("NGrid%s=%d not divisible by %d ranks" % ("XYZ"[ax], nz, world))
     cfg = copy.deepcopy(cfg_global)
     nzl = nz // world
-    cfg.ng[2] = nzl
-    cfg.xmin[2] = cfg_global.xmin[2] + rank * nzl * cfg_global.dx
-    periodic = cfg_global.bc_type[4] == abi.BC_PERIODIC
+    cfg.ng[ax] = nzl
+    cfg.xmin[ax] = cfg_global.xmin[ax] + rank * nzl * cfg_global.dx
+    periodic = slab_periodic(cfg_global)
     if world > 1:
         if periodic or rank > 0:
-            cfg.bc_type[4] = abi.BC_SLAB
+            cfg.bc_type[2 * ax] = abi.BC_SLAB
+            if ax == 1:
+                cfg.bc_dmach2 = 0      # the internal DMR2 cells lie below the global YN face
         if periodic or rank < world - 1:
-            cfg.bc_type[5] = abi.BC_SLAB
+            cfg.bc_type[2 * ax + 1] = abi.BC_SLAB
     return cfg
 
 
 def slab_slice(P_global, cfg_global, rank, world):
-    """The rank's part [nvar][nzl+2nbc][ny_all][nx_all] of a global SoA array (ghost planes
-    taken from the global array; they are overwritten by the first boundary update)."""
+    """The rank's part [nvar][nzl+2nbc][ny_all][nx_all] (2-D: [nvar][1][nyl+2nbc][nx_all]) of a global SoA array
+    (ghost planes taken from the global array; they are overwritten by the first boundary update)."""
     nb = cfg_global.nbc
-    nzl = cfg_global.ng[2] // world
+    ax = slab_axis(cfg_global)
+    nzl = cfg_global.ng[ax] // world
     z0 = rank * nzl
+    if ax == 1:
+        return P_global[:, :, z0:z0 + nzl + 2 * nb].copy()
     return P_global[:, z0:z0 + nzl + 2 * nb].copy()
 
 
@@ -61,7 +82,9 @@ class SlabComm:
     (which, face, tensor.data_ptr())."""
 
     def __init__(self, rank, world, periodic, halo_count, device, host_staged=None, loopback=False):
-        """loopback: a single rank with periodic z whose z faces are BC_SLAB exchanges with itself
+        """This torch.distributed transport exchanges the z faces of a 3-D grid only: driver.SimControl refuses it
+        for any other grid (2-D slabs run through the C++ loop: host_rccl.HostSim with slab_comm_rccl / slab_comm_shm).
+        loopback: a single rank with periodic z whose z faces are BC_SLAB exchanges with itself
         through the backend (the only way to drive RCCL send/recv on a one-GPU box); the result
         equals the periodic single-domain run.
         host_staged: exchange through pinned host buffers (GPU state, CPU-only backend such as
