@@ -1,4 +1,4 @@
-// kernels.h -- launch interface between the C-ABI layer (pion_gpu.hip) and the
+// kernels.h -- launch interface between the C-ABI layer (pion_gpu.hip, pion_step.hip) and the
 // floating-point kernels (kernels_fp.hip).  kernels_fp.hip is compiled twice,
 // once per floating-point mode, into namespaces pion::fp_strict (-ffp-contract=off:
 // bit-parity with the reference's x86-64 -O3 build) and pion::fp_fast (FMA

@@ -1080,7 +1080,7 @@ int launch_prepass(const PrepassArgs &a, hipStream_t s)
 {
   const unsigned nb = (unsigned)((a.c1 - a.c0 + 255) / 256);
   if (a.hllflag && a.hsum) {
-    // (pion_gpu.hip passes a summary only for whole-array launches of a 3-D Cartesian grid without debug outputs)
+    // (pion_step.hip passes a summary only for whole-array launches of a 3-D Cartesian grid without debug outputs)
     const long nblk = scr_total(a.scr);
     if (hipMemsetAsync(a.hllflag, 0, (size_t)a.g.ncell, s) != hipSuccess) return -1;
     if (hipMemsetAsync(a.scr_count, 0, sizeof(int), s) != hipSuccess) return -1;
@@ -1089,12 +1089,12 @@ int launch_prepass(const PrepassArgs &a, hipStream_t s)
     hipLaunchKernelGGL(k_prepass_hlld_blocks, dim3(ngrid), dim3(256), 0, s, a);
   }
   else if (a.hllflag) {
-    // [c0,c1) is a whole number of planes (pion_gpu.hip)
+    // [c0,c1) is a whole number of planes (pion_step.hip)
     const long plane = (long)a.g.nga[0] * a.g.nga[1];
     const unsigned npl = (unsigned)((a.c1 - a.c0) / plane) + ((a.c3 > a.c2) ? (unsigned)((a.c3 - a.c2) / plane) : 0u);
     const unsigned ntile = (unsigned)((a.g.nga[0] + 63) / 64) * ((a.g.nga[1] + 3) / 4) * npl;
     if (a.g.ndim == 2 && (a.c0 != 0 || a.c1 != a.g.ncell)) {
-      // a part of a split 2-D stage (pion_gpu.hip): whole rows
+      // a part of a split 2-D stage (pion_step.hip): whole rows
       const long row = a.g.nga[0];
       const unsigned nr = (unsigned)((a.c1 - a.c0) / row) + ((a.c3 > a.c2) ? (unsigned)((a.c3 - a.c2) / row) : 0u);
       if (nr > 0)

@@ -1,25 +1,87 @@
 // pion_gpu.hip -- implementation of the C-ABI declared in include/pion_gpu.h.
 //
-// Host side of the boundary: owns device memory behind an opaque handle, launches
-// the floating-point kernels of kernels_fp.hip (strict or fast namespace), and
-// holds the data-movement kernels that have no arithmetic: ghost-cell fills
-// (boundaries/*.cpp of the reference), stellar-wind cell reset, halo pack/unpack.
+// Host side of the boundary: owns device memory behind an opaque handle (pion_handle.h): set-up and tear-down,
+// uploads, stellar winds, jet, cooling tables, the test seams and timing, and the data-movement kernels of the
+// boundary update, which have no arithmetic: ghost-cell fills (boundaries/*.cpp of the reference), stellar-wind
+// cell reset.  What a time step calls (time step, stages, halo) is pion_step.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
 
 #include <hipcub/hipcub.hpp>
 
-#include "../../include/pion_gpu.h"
 #include "dev_wind.h"
-#include "kernels.h"
+#include "pion_handle.h"
 
 using namespace pion;
+using namespace pion::impl;
+static_assert(ANGLE_NTHETA == PION_ANGLE_NTHETA && ANGLE_NOMEGA == PION_ANGLE_NOMEGA && ANGLE_NTEFF == PION_ANGLE_NTEFF);
+
+int impl::order_after_unpack(Handle *h)
+{
+  if (h->comm_stream && h->comm_stream != h->stream && h->ev_unpacked_valid) {
+    HCHECK(h, hipStreamWaitEvent(h->stream, h->ev_unpacked, 0));
+    h->ev_unpacked_valid = false;
+  }
+  return 0;
+}
+
+long impl::cell_id(const GridDesc &g, int ix, int iy, int iz)
+{
+  return (long)(ix + g.nbc[0]) + g.sy * (iy + g.nbc[1]) + g.sz * (iz + g.nbc[2]);
+}
+
+void impl::time_begin(Handle *h, int slot)
+{
+  if (!h->timing) return;
+  hipEvent_t e;
+  hipEventCreate(&e);
+  hipEventRecord(e, h->stream);
+  h->ev[slot].push_back(e);
+}
+
+FluxCtx impl::make_fluxctx(const Handle *h, double fv_dt)
+{
+  FluxCtx fc;
+  fc.gamma = h->cfg.gamma;
+  fc.dx = h->cfg.dx;
+  fc.fv_dt = fv_dt;
+  fc.etav = h->cfg.etav;
+  fc.chyp = h->glm_chyp;
+  fc.min_temp = h->cfg.min_temp;
+  fc.refRO = h->refvec_avg[0];
+  fc.refPG = h->refvec_avg[1];
+  fc.refV = h->refvec_avg[2];
+  fc.refB = h->refvec_avg[5];
+  fc.gndim = h->cfg.ndim;
+  fc.artvisc = h->cfg.artvisc;
+  fc.mp.present = (h->cfg.cooling != 0);
+  fc.mp.Mu_tot_over_kB = h->Mu_tot_over_kB;
+  return fc;
+}
+
+int impl::check_errword(Handle *h)
+{
+  int e = 0;
+  HCHECK(h, hipMemcpyAsync(&e, h->derr, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  if (e) {
+    char b[400];
+    snprintf(b, sizeof b, "device physics error word 0x%x:%s%s%s%s%s", e,
+             (e & ERR_NEG_DENSITY) ? " negative density (reference: rep.error -> exit)" : "",
+             (e & ERR_RIEMANN_INPUT) ? " density/pressure too small in Riemann solver" : "",
+             (e & ERR_COOLING) ? " cooling integration failed" : "", (e & ERR_BAD_DT) ? " invalid cell timestep" : "",
+             (e & ERR_MHD_RIEMANN) ? " linear MHD Riemann solver: bad wave speeds (reference: rep.error -> exit)" : "");
+    h->err = b;
+    int z = 0;
+    hipMemcpyAsync(h->derr, &z, sizeof(int), hipMemcpyHostToDevice, h->stream);
+    return PION_GPU_EPHYSICS;
+  }
+  return 0;
+}
 
 namespace {
 
@@ -402,246 +464,6 @@ __global__ void k_wind(double *T, const long *idx, const double *states, const l
   const long c = idx[t];
   for (int v = 0; v < nvar; v++) T[v * nc + c] = states[t * nvar + v];
 }
-
-// halo planes of the slab axis (the last axis: z planes in 3-D, y rows in 2-D): buffer layout
-// [nvar][nbc][ny_all][nx_all] (2-D: [nvar][nbc][nx_all])
-__global__ void k_halo(double *A, double *buf, const GridDesc g, const int nvar, const int face, const int pack)
-{
-  const int sa = g.ndim - 1;
-  const long plane = (sa == 2) ? (long)g.nga[0] * g.nga[1] : (long)g.nga[0];
-  const long per = plane * g.nbc[sa];
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= per * nvar) return;
-  const int v = (int)(t / per);
-  const long r = t % per;
-  const int k = (int)(r / plane);
-  const long xy = r % plane;
-  int izall;
-  if (pack) izall = (face == 2 * sa) ? g.nbc[sa] + k : g.ng[sa] + k;       // on-grid planes next to the face
-  else izall = (face == 2 * sa) ? k : g.nbc[sa] + g.ng[sa] + k;            // ghost planes of the face
-  const long c = xy + plane * izall;
-  if (pack) buf[t] = A[v * g.ncell + c];
-  else A[v * g.ncell + c] = buf[t];
-}
-
-// stellar_wind_angle's look-up tables for one xi (setup_tables, grid/stellar_wind_angle.cpp:92-212)
-struct AngleTables {
-  double xi = 0.0;
-  double theta[PION_ANGLE_NTHETA], omega[PION_ANGLE_NOMEGA], Teff[PION_ANGLE_NTEFF];
-  std::vector<double> delta;   // [omega][Teff]
-  std::vector<double> alpha;   // [omega][theta][Teff]
-};
-
-// one pion_gpu_add_wind_source source: its table, the parameters the next boundary update writes with, and the
-// activity bookkeeping of stellar_wind_evolution (evolving_wind_data: tstart, tfinish, t_next_update, is_active)
-struct WindSource {
-  int type = 0;
-  double pos[3] = {0.0, 0.0, 0.0};
-  double radius = 0.0, Bstar = 0.0;
-  std::vector<double> t, Teff, Mdot, vrot, vinf, R, X[7];
-  std::vector<double> vcrit;   // rotating source (type 2): the vcrit column
-  int elem[PION_MAX_NVAR];
-  double Mdot_c = 0.0, Vinf_c = 0.0, vrot_c = 0.0, Tw_c = 0.0, Rstar_c = 0.0;   // wind_source members, cgs
-  double vcrit_c = 0.0;
-  double tr[PION_MAX_NVAR];
-  bool active = true;
-  double tstart = 0.0, tfinish = 0.0, t_next_update = 1.0e99;
-  long off = 0, n = 0;   // range in the concatenated cell list (moving source: n = its capacity, the box size)
-  // orbital motion (orbit_period != 0): the position at set-up (dpos_init), the orbit, the box the cells are found
-  // in, the device count the compaction writes, and the compaction's scratch (all sized at set-up)
-  bool moving = false;
-  pion_gpu_wind_source orbit;   // pos = dpos_init, orbit_* (the pointers are not used)
-  int box_w[3] = {1, 1, 1};
-  long *dn = nullptr;
-  void *dscan = nullptr;
-  size_t scan_bytes = 0;
-};
-
-struct Handle {
-  pion_gpu_config cfg;
-  GridDesc g;
-  int device = 0;
-  int ncu = 0;            // compute units of the device (launch shaping)
-  hipStream_t stream = 0;
-  hipStream_t comm_stream = 0;     // pack/unpack of the z halo (0: the compute stream)
-  hipEvent_t ev_packed_src = nullptr, ev_unpacked = nullptr;
-  hipStream_t bstream = 0;         // the z-boundary strips of a split stage (two-stream mode): beside the interior part
-  hipEvent_t ev_pre = nullptr, ev_bdone = nullptr;
-  bool ev_pre_valid = false;
-  bool concurrent_strips = true;   // PION_CONCURRENT_STRIPS=0: strips after the interior part on the compute stream
-  bool ev_unpacked_valid = false;
-  double *dP = nullptr, *dPh = nullptr;
-  bool own_state = true;
-  uint8_t *dflags = nullptr, *dhll = nullptr;
-  double *deta = nullptr;
-  double *dsphvol = nullptr;   // spherical 1-D: shell volumes/(4 pi) per cell
-  int *derr = nullptr;
-  unsigned long long *ddt = nullptr;   // [0]=min t_dyn, [1]=min t_mp (bit patterns)
-  unsigned long long *ddt_init = nullptr;  // {1e100, 1e99} on the device: reset source (no host buffer in flight)
-  double *hdt = nullptr;               // pinned host staging of {t_dyn, t_mp, error word} (pion_gpu_dt_request)
-  hipEvent_t ev_dt = nullptr;
-  bool dt_requested = false;
-  std::vector<uint8_t> hflags;
-  // boundary state
-  double refval[6][PION_MAX_NVAR];
-  int dmr2_cols = 0;
-  long nwind = 0;
-  long njet = 0;          // jet inflow cells (XN ghosts), one state for all
-  long *djet_idx = nullptr;
-  double *djet_state = nullptr;
-  long *dwind_idx = nullptr;
-  double *dwind_state = nullptr;
-  // wind sources (pion_gpu_add_wind_source): cells of all sources concatenated in id order, each in cell-id order
-  std::vector<WindSource> wsrc;
-  long nws = 0;              // cells of all sources
-  long *dws_idx = nullptr;
-  double *dws_dist = nullptr, *dws_off = nullptr, *dws_state = nullptr;   // off: [3][nws]; state: [nws][nvar]
-  double *dws_theta = nullptr;   // stellar_wind::add_cell's theta (fixed sources; read by rotating ones)
-  // rotating sources (pion_gpu_add_rotating_wind_source): the LGM99 tables, built at the first one, for its xi
-  bool have_angle = false;
-  AngleTables angle;
-  // cooling
-  CoolDev cool;
-  double *dcoolT = nullptr, *dcooltab = nullptr, *dcoolslope = nullptr;
-  bool have_tables = false;
-  // solver state
-  double glm_chyp = 0.0, glm_cr = 0.0;
-  double refvec_avg[PION_MAX_NVAR];
-  bool ph_valid = false;  // dPh holds a genuine half-step state
-  bool dt_cached = false; // ddt holds the time-step minima of the current P (left by the last full stage)
-  std::string err;
-  // timing
-  bool timing = false;
-  std::vector<hipEvent_t> ev[4];
-  double Mu_tot_over_kB = 0.0;
-  int use_march = 3, zchunk = 0, rows = 0;  // zchunk 0: chosen per launch; rows 0: chosen per instance (rows2_plan, rows_tiling.h)
-  int rows1 = 0;                            // rows of the first-order stage (PION_ROWS1)
-  const double *xghost_fresh = nullptr;   // array whose x ghosts (periodic x) the last stage kernel wrote itself
-  int zslope_lds = 1;     // k_stage_rows2: carry the z slope in LDS (default; PION_ZSLOPE_LDS=0: rebuild it from plane k-1, R = 4)
-  double *ddE = nullptr;  // cooling source per cell (k_cooling_dE -> k_stage_rows2)
-  bool fuse_dt = true;    // PION_FUSE_DT=0: always run k_dt (A/B)
-  bool uneven_chunks = true;   // PION_UNEVEN_CHUNKS=0: equal plane chunks (A/B)
-  bool dt_mp_pending = false;  // k_dt_mp owed after the two streams of a split stage have joined
-  bool split_dt_mp = true;     // PION_SPLIT_DT_MP=0: cooling time inside the stage kernel's fused reduction (A/B)
-  bool fuse_bc = true;    // PION_FUSE_BC=0: periodic faces one launch per face (A/B)
-  // Screened HLLD -> HLL switch prepass (hll_screen.h): a whole-stage launch of k_stage_rows2 leaves the pressure range
-  // of every block of the array it writes in dsum; the next stage's prepass evaluates only the blocks that are not
-  // provably calm.  sum_arr: the array dsum describes (null: none), valid for the prepass once sum_bc says that the
-  // boundary update has refilled that array's ghost cells; dropped by everything else that writes the state.
-  bool hll_screen = true;      // PION_HLL_SCREEN=0: always the dense prepass (A/B)
-  bool screen_ok = false;      // grid, boundary types and cell lists admit the screen (screen_admitted)
-  ScrGeom scr;
-  unsigned long long *dsum = nullptr;   // [2][blocks]: keys of the maxima, of the minima
-  int *dscr_list = nullptr, *dscr_count = nullptr;
-  const double *sum_arr = nullptr;
-  bool sum_bc = false;
-  bool last_prepass_screened = false;
-};
-
-// the state arrays, the cell flags or the tables were written from outside the stages: what the last stage left
-// about its result (time-step minima, pressure summary) no longer holds
-static inline void state_changed(Handle *h)
-{
-  h->dt_cached = false;
-  h->sum_arr = nullptr;
-  h->sum_bc = false;
-}
-
-#define HCHECK(h, call)                                                            \
-  do {                                                                             \
-    hipError_t e_ = (call);                                                        \
-    if (e_ != hipSuccess) {                                                        \
-      (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
-      return PION_GPU_EDEVICE;                                                     \
-    }                                                                              \
-  } while (0)
-
-// Every entry point selects the handle's device first: the current device is per-thread state, and
-// distinct handles may be driven from distinct host threads (or interleaved on one thread).
-static inline Handle *use(void *handle)
-{
-  Handle *h = (Handle *)handle;
-  if (h) (void)hipSetDevice(h->device);
-  return h;
-}
-
-// Two-stream mode: everything on the compute stream that touches the z ghost planes must run after
-// the last unpack on the comm stream.  One wait is enough, later work is ordered behind it.
-int order_after_unpack(Handle *h)
-{
-  if (h->comm_stream && h->comm_stream != h->stream && h->ev_unpacked_valid) {
-    HCHECK(h, hipStreamWaitEvent(h->stream, h->ev_unpacked, 0));
-    h->ev_unpacked_valid = false;
-  }
-  return 0;
-}
-
-long cell_id(const GridDesc &g, int ix, int iy, int iz)
-{
-  return (long)(ix + g.nbc[0]) + g.sy * (iy + g.nbc[1]) + g.sz * (iz + g.nbc[2]);
-}
-
-void time_begin(Handle *h, int slot)
-{
-  if (!h->timing) return;
-  hipEvent_t e;
-  hipEventCreate(&e);
-  hipEventRecord(e, h->stream);
-  h->ev[slot].push_back(e);
-}
-void time_end(Handle *h, int slot) { time_begin(h, slot); }
-
-FluxCtx make_fluxctx(const Handle *h, double fv_dt)
-{
-  FluxCtx fc;
-  fc.gamma = h->cfg.gamma;
-  fc.dx = h->cfg.dx;
-  fc.fv_dt = fv_dt;
-  fc.etav = h->cfg.etav;
-  fc.chyp = h->glm_chyp;
-  fc.min_temp = h->cfg.min_temp;
-  fc.refRO = h->refvec_avg[0];
-  fc.refPG = h->refvec_avg[1];
-  fc.refV = h->refvec_avg[2];
-  fc.refB = h->refvec_avg[5];
-  fc.gndim = h->cfg.ndim;
-  fc.artvisc = h->cfg.artvisc;
-  fc.mp.present = (h->cfg.cooling != 0);
-  fc.mp.Mu_tot_over_kB = h->Mu_tot_over_kB;
-  return fc;
-}
-
-int check_errword(Handle *h)
-{
-  int e = 0;
-  HCHECK(h, hipMemcpyAsync(&e, h->derr, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HCHECK(h, hipStreamSynchronize(h->stream));
-  if (e) {
-    char b[400];
-    snprintf(b, sizeof b, "device physics error word 0x%x:%s%s%s%s%s", e,
-             (e & ERR_NEG_DENSITY) ? " negative density (reference: rep.error -> exit)" : "",
-             (e & ERR_RIEMANN_INPUT) ? " density/pressure too small in Riemann solver" : "",
-             (e & ERR_COOLING) ? " cooling integration failed" : "", (e & ERR_BAD_DT) ? " invalid cell timestep" : "",
-             (e & ERR_MHD_RIEMANN) ? " linear MHD Riemann solver: bad wave speeds (reference: rep.error -> exit)" : "");
-    h->err = b;
-    int z = 0;
-    hipMemcpyAsync(h->derr, &z, sizeof(int), hipMemcpyHostToDevice, h->stream);
-    return PION_GPU_EPHYSICS;
-  }
-  return 0;
-}
-
-// get_mp_timescales_no_radiation (calc_timestep.cpp:445-459): EP.MP_timestep_limit 1, 2, 3 ask
-// mp_only_cooling::timescales for the cooling time (tc = true); 4 (recombination time only) gets 1e99
-// from it (mp_only_cooling.cpp:338), i.e. no limit; anything else is fatal there (EINVAL in create).
-static inline bool mp_dt_limited(const pion_gpu_config &cfg)
-{
-  return cfg.cooling != 0 && cfg.mp_timestep_limit >= 1 && cfg.mp_timestep_limit <= 3;
-}
-
-// legacy wind list or wind sources present: the stage kernels read the cell flags, and the periodic ghost images
-// are not fused into one launch
-static inline bool any_wind(const Handle *h) { return h->nwind > 0 || h->nws > 0; }
 
 // constants::equalD (constants.cpp:48-68)
 static bool equalD(const double a, const double b)
@@ -2167,544 +1989,11 @@ int pion_gpu_update_bcs(void *handle, double simtime, int cstep, int maxstep, in
   return 0;
 }
 
-int pion_gpu_calc_dt_device(void *handle, void **dptr)
-{
-  Handle *h = use(handle);
-  DtArgs a;
-  a.g = h->g;
-  a.P = h->dP;
-  a.Ph = h->ph_valid ? h->dPh : h->dP;
-  a.flags = h->dflags;
-  a.result = h->ddt;
-  a.errword = h->derr;
-  a.eqntype = h->cfg.eqntype;
-  a.nvar = h->cfg.nvar;
-  a.gamma = h->cfg.gamma;
-  a.cfl = h->cfg.cfl;
-  a.do_mp = mp_dt_limited(h->cfg) ? 1 : 0;
-  a.cool = h->cool;
-  if (a.do_mp && !h->have_tables) {
-    h->err = "cooling tables not set";
-    return PION_GPU_EINVAL;
-  }
-  if (!h->dt_cached) {
-    // (after a full step through k_stage_rows2 the minima of the new state are already in ddt)
-    HCHECK(h, hipMemcpyAsync(h->ddt, h->ddt_init, 2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    time_begin(h, 3);
-    const int rc = h->cfg.strict_fp ? fp_strict::launch_dt(a, h->stream) : fp_fast::launch_dt(a, h->stream);
-    time_end(h, 3);
-    if (rc != 0) {
-      h->err = "dt kernel launch failed";
-      return PION_GPU_EDEVICE;
-    }
-    h->dt_cached = true;
-  }
-  if (dptr) *dptr = h->ddt;
-  return 0;
-}
-
-int pion_gpu_dt_request(void *handle)
-{
-  Handle *h = use(handle);
-  if (!h->hdt) HCHECK(h, hipHostMalloc((void **)&h->hdt, 4 * sizeof(double), hipHostMallocDefault));
-  if (!h->ev_dt) HCHECK(h, hipEventCreateWithFlags(&h->ev_dt, hipEventDisableTiming));
-  // {min t_dyn, min t_mp} and the device error word, one event for both
-  HCHECK(h, hipMemcpyAsync(h->hdt, h->ddt, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HCHECK(h, hipMemcpyAsync(h->hdt + 2, h->derr, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HCHECK(h, hipEventRecord(h->ev_dt, h->stream));
-  h->dt_requested = true;
-  return 0;
-}
-
-int pion_gpu_dt_wait(void *handle, double *t_dyn, double *t_mp)
-{
-  Handle *h = use(handle);
-  if (!h->dt_requested) {
-    h->err = "pion_gpu_dt_wait without pion_gpu_dt_request";
-    return PION_GPU_EINVAL;
-  }
-  HCHECK(h, hipEventSynchronize(h->ev_dt));
-  h->dt_requested = false;
-  *t_dyn = h->hdt[0];
-  *t_mp = h->hdt[1];
-  int e;
-  memcpy(&e, h->hdt + 2, sizeof e);
-  if (e) return check_errword(h);   // (re-reads and clears the word, builds the message)
-  return 0;
-}
-
-int pion_gpu_read_dt(void *handle, double *t_dyn, double *t_mp)
-{
-  if (int rc = pion_gpu_dt_request(handle)) return rc;
-  return pion_gpu_dt_wait(handle, t_dyn, t_mp);
-}
-
-int pion_gpu_calc_dt(void *handle, double *t_dyn, double *t_mp)
-{
-  if (int rc = pion_gpu_calc_dt_device(handle, nullptr)) return rc;
-  return pion_gpu_read_dt(handle, t_dyn, t_mp);
-}
-
 void *pion_gpu_get_stream(void *handle, int which)
 {
   Handle *h = use(handle);
   return (void *)(which == 0 ? h->stream : (h->comm_stream ? h->comm_stream : h->stream));
 }
-
-int pion_gpu_set_glm_speeds(void *handle, double dt, double dx, double cr)
-{
-  Handle *h = use(handle);
-  h->glm_chyp = h->cfg.cfl * dx / dt;  // GLMsetPsiSpeed(FV_cfl*delx/delt, cr)
-  h->glm_cr = cr;
-  return 0;
-}
-
-// One stage, or a part of one (PION_STAGE_WHOLE / _INTERIOR / _SLABBOUNDARY).  The split lets the halo
-// exchange of a slab run under the interior: the interior part reads no ghost plane of the slab axis (the last
-// axis: z planes in 3-D, y rows in 2-D), the boundary part (the nbc on-grid planes / rows next to each face of
-// that axis) waits for the unpacked halo.
-static inline int slab_axis(const Handle *h) { return h->g.ndim - 1; }
-static bool stage_can_split(const Handle *h)
-{
-  const int sa = slab_axis(h);
-  return h->use_march != 0 && !h->deta && (h->g.ndim == 3 || h->g.ndim == 2)
-         && h->g.ng[sa] > 2 * h->g.nbc[sa] && !(h->cfg.tm_ooa == 1 && h->cfg.sp_ooa == 1);
-}
-
-// min of the cooling time over the state the full step has just written (P), into ddt[1]: k_dt_mp
-static int launch_cooling_time(Handle *h, hipStream_t s)
-{
-  const pion_gpu_config &cfg = h->cfg;
-  DtArgs d;
-  d.g = h->g;
-  d.P = h->dP;
-  d.Ph = h->dP;
-  d.flags = h->dflags;
-  d.result = h->ddt;
-  d.errword = h->derr;
-  d.eqntype = cfg.eqntype;
-  d.nvar = cfg.nvar;
-  d.gamma = cfg.gamma;
-  d.cfl = cfg.cfl;
-  d.do_mp = 1;
-  d.cool = h->cool;
-  time_begin(h, 3);
-  const int rc = cfg.strict_fp ? fp_strict::launch_dt_mp(d, s) : fp_fast::launch_dt_mp(d, s);
-  time_end(h, 3);
-  if (rc != 0) {
-    h->err = "cooling-time kernel launch failed";
-    return PION_GPU_EDEVICE;
-  }
-  return 0;
-}
-
-// Does this handle admit the screened prepass?  3-D Cartesian grid run by k_stage_rows2 with HLLD; every face periodic,
-// outflow, one-way outflow, reflecting or axis-reflecting (k_bc_all / k_bc_face / k_bc_periodic_all leave exact copies
-// of on-grid pressures in the ghost cells of those, and of no other type); no wind, jet or DMR2 cells; blocks at
-// the faces wide enough to hold the copied cells.
-static bool screen_admitted(Handle *h)
-{
-  const pion_gpu_config &cfg = h->cfg;
-  if (!h->hll_screen || !h->dhll || cfg.ndim != 3 || h->g.cyl != 0 || h->use_march == 0 || h->g.nbc[2] < 2) return false;
-  if (any_wind(h) || h->njet > 0 || cfg.bc_dmach2) return false;
-  if (h->g.ncell * 8L >= (1L << 32)) return false;
-  int per[3];
-  for (int d = 0; d < 3; d++) {
-    for (int f = 2 * d; f < 2 * d + 2; f++) {
-      const int t = cfg.bc_type[f];
-      if (!(t == PION_BC_PERIODIC || t == PION_BC_OUTFLOW || t == PION_BC_ONEWAY_OUT || t == PION_BC_REFLECTING
-            || t == PION_BC_AXISYMMETRIC))
-        return false;
-    }
-    if ((cfg.bc_type[2 * d] == PION_BC_PERIODIC) != (cfg.bc_type[2 * d + 1] == PION_BC_PERIODIC)) return false;
-    per[d] = (cfg.bc_type[2 * d] == PION_BC_PERIODIC) ? 1 : 0;
-    if (!scr_axis_ok(h->g.ng[d], h->g.nbc[d])) return false;
-  }
-  h->scr = scr_geom(h->g.ng, h->g.nbc, per);
-  if (!h->dsum) {
-    const size_t n = (size_t)scr_total(h->scr);
-    if (hipMalloc(&h->dsum, 2 * n * sizeof(unsigned long long)) != hipSuccess) return false;
-    if (hipMalloc(&h->dscr_list, n * sizeof(int)) != hipSuccess) return false;
-    if (hipMalloc(&h->dscr_count, sizeof(int)) != hipSuccess) return false;
-    if (hipMemset(h->dscr_count, 0, sizeof(int)) != hipSuccess) return false;
-  }
-  return true;
-}
-
-// planes [kz0,kz1) and, if kz3 > kz2, also [kz2,kz3) (the two z-boundary strips go out as ONE launch).  2-D grids
-// run by the rows kernel: the same with on-grid ROWS (the slab axis is y); other 2-D / 1-D grids: whole stages only,
-// the ranges are not read.
-static int stage_launch(Handle *h, double dt_stage, int space_ooa, int is_full_step, int kz0, int kz1,
-                        bool first, bool last, int kz2 = 0, int kz3 = 0, hipStream_t ls = 0, bool use_ls = false)
-{
-  if (!use_ls) ls = h->stream;   // launch stream: the compute stream unless the caller runs this part beside it
-  const pion_gpu_config &cfg = h->cfg;
-  if (cfg.cooling != 0 && !h->have_tables) {
-    h->err = "cooling tables not set";
-    return PION_GPU_EINVAL;
-  }
-  // the stencil state: Ph.  At the start of a step Ph == P in every cell.
-  const double *S = h->ph_valid ? h->dPh : h->dP;
-  int rc = 0;
-  // preprocess_data (solver_eqn_base.cpp:353-415)
-  if (h->dhll || h->deta) {
-    PrepassArgs p;
-    p.g = h->g;
-    p.S = S;
-    p.hllflag = h->dhll;
-    p.divv = nullptr;
-    p.gradp = nullptr;
-    p.eta = h->deta;
-    p.eqntype = cfg.eqntype;
-    p.nvar = cfg.nvar;
-    p.space_ooa = space_ooa;
-    p.gamma = cfg.gamma;
-    // cells whose flag this part is the first to need: the faces of on-grid planes [kz0,kz1) touch
-    // planes kz0-1 .. kz1; a whole stage covers every cell incl. ghosts like the reference's loop
-    p.c0 = 0;
-    p.c1 = h->g.ncell;
-    p.c2 = p.c3 = 0;
-    // the summary the last stage left of S, if nothing but the boundary update has touched S since
-    p.hsum = nullptr;
-    p.scr_list = p.scr_count = nullptr;
-    h->screen_ok = screen_admitted(h);
-    if (first && last && h->screen_ok && h->sum_arr == S && h->sum_bc) {
-      p.hsum = h->dsum;
-      p.scr = h->scr;
-      p.scr_list = h->dscr_list;
-      p.scr_count = h->dscr_count;
-    }
-    h->last_prepass_screened = (p.hsum != nullptr);
-    const int sa = slab_axis(h);
-    const long sst = (sa == 2) ? h->g.sz : h->g.sy;   // cells per plane (3-D) / row (2-D) of the slab axis
-    if (!(first && last)) {
-      const int nb = h->g.nbc[sa], nz = h->g.ng[sa];
-      int lo = kz0 - 1, hi = kz1 + 1;        // on-grid plane numbers [lo,hi): the interior part
-      if (kz0 == 0) {                        // lower z-boundary part: the interior part did nb-1 ..
-        lo = -1;
-        hi = nb - 1;
-      }
-      else if (kz1 == nz) {                  // upper z-boundary part: the interior part did .. nz-nb
-        lo = nz - nb + 1;
-        hi = nz + 1;
-      }
-      p.c0 = (long)(lo + nb) * sst;
-      p.c1 = (long)(hi + nb) * sst;
-    }
-    if (kz3 > kz2) {
-      // second strip (the upper z boundary): its own plane range of flags, same launch
-      const int nb = h->g.nbc[sa], nz = h->g.ng[sa];
-      p.c2 = (long)(nz - nb + 1 + nb) * sst;
-      p.c3 = (long)(nz + 1 + nb) * sst;
-    }
-    time_begin(h, 1);
-    rc = cfg.strict_fp ? fp_strict::launch_prepass(p, ls) : fp_fast::launch_prepass(p, ls);
-    time_end(h, 1);
-    if (rc != 0) {
-      h->err = "prepass launch failed";
-      return PION_GPU_EDEVICE;
-    }
-  }
-  StageArgs a;
-  a.g = h->g;
-  a.S = S;
-  a.Pc = h->dP;
-  // first half step: P -> Ph.  Full step: in place on P (each thread reads P only at its own cell).
-  a.out = is_full_step ? h->dP : h->dPh;
-  if (is_full_step && !h->ph_valid && cfg.sp_ooa == 2 && space_ooa == 2) {
-    // a full second-order stage straight from P would read neighbours that are being overwritten
-    h->err = "full-step stage requires a preceding half-step stage";
-    return PION_GPU_EINVAL;
-  }
-  if (is_full_step && S == h->dP) {
-    // first-order scheme (OA1/OA1): stencil and destination coincide -> go through Ph
-    a.out = h->dPh;
-  }
-  a.flags = h->dflags;
-  a.hllflag = h->dhll;
-  a.eta = h->deta;
-  a.errword = h->derr;
-  a.fc = make_fluxctx(h, dt_stage);
-  a.eqntype = cfg.eqntype;
-  a.ntracer = cfg.ntracer;
-  a.solver = cfg.solver;
-  a.space_ooa = space_ooa;
-  a.cooling = cfg.cooling;
-  a.dt = dt_stage;
-  a.glm_damp = exp(-dt_stage * h->glm_chyp * h->glm_cr);
-  a.max_temp = cfg.max_temp;
-  a.cool = h->cool;
-  a.use_march = h->use_march;
-  a.kz0 = kz0;
-  a.kz1 = kz1;
-  a.kz2 = kz2;
-  a.kz3 = (kz3 > kz2) ? kz3 : kz2;
-  const bool rows2d = (h->g.ndim == 2 && h->use_march != 0);
-  if (h->g.ndim < 3) {
-    a.kz0 = 0;
-    a.kz1 = 1;
-    a.kz2 = a.kz3 = 0;
-  }
-  if (rows2d) {
-    // 2-D row ranges (rows_tiling.h, "2-D row ranges"): the kernels see a grid of as many rows as a range has, whose
-    // one "plane" per range is numbered by the range's first row
-    if (kz3 > kz2 && kz3 - kz2 != kz1 - kz0) {
-      h->err = "stage: the two row strips of a 2-D launch must have the same number of rows";
-      return PION_GPU_EINVAL;
-    }
-    a.g.ng[1] = kz1 - kz0;
-    a.kz0 = kz0;
-    a.kz1 = kz0 + 1;
-    a.kz2 = kz2;
-    a.kz3 = (kz3 > kz2) ? kz2 + 1 : kz2;
-  }
-  a.zslope_lds = h->zslope_lds;
-  a.plain_cells = any_wind(h) ? 0 : 1;
-  a.dE = nullptr;
-  // periodic x: k_stage_rows2 writes the x ghost images of its rows (the boundary launch then skips them)
-  a.xwrap = (a.use_march != 0 && h->fuse_bc && cfg.bc_type[0] == PION_BC_PERIODIC
-             && cfg.bc_type[1] == PION_BC_PERIODIC && h->g.ng[0] >= 2 * h->g.nbc[0]) ? 1 : 0;
-  a.ncu = h->ncu;
-  {
-    // rows per wavefront, plane chunks (rows_tiling.h; PION_ROWS / PION_ROWS1 / PION_ZCHUNK / PION_UNEVEN_CHUNKS
-    // override the choices)
-    Rows2PlanIn p;
-    p.ndim = h->g.ndim;
-    p.nx = h->g.ng[0];
-    p.ny = a.g.ng[1];                        // (2-D: the rows of the range, which is what the launch tiles)
-    p.np = (h->g.ndim == 3) ? kz1 - kz0 : 1;
-    p.ncu = h->ncu;
-    p.nv = cfg.nvar;
-    p.euler = (cfg.eqntype == PION_EQEUL);
-    p.march = (a.use_march != 0);
-    p.zslope_lds = (a.zslope_lds != 0);
-    p.second_order = (space_ooa == 2);
-    p.uneven = h->uneven_chunks;
-    p.want_rows = h->rows;
-    p.want_rows1 = h->rows1;
-    p.want_zchunk = h->zchunk;
-    const Rows2Plan pl = rows2_plan(p);
-    a.rows = pl.rows;
-    a.rows_auto = pl.rows_auto;
-    a.zchunk = pl.zchunk;
-    a.zcmax = pl.zcmax;
-    a.nzb = pl.nzb;
-  }
-  if (cfg.cooling != 0 && a.use_march != 0) {
-    // calc_noRT_microphysics_dU as its own launch (thread per cell, full occupancy): dE per cell
-    a.dE = h->ddE;
-    time_begin(h, 1);
-    rc = cfg.strict_fp ? fp_strict::launch_cooling_dE(a, ls) : fp_fast::launch_cooling_dE(a, ls);
-    time_end(h, 1);
-    if (rc != 0) {
-      h->err = "cooling kernel launch failed";
-      return PION_GPU_EDEVICE;
-    }
-  }
-  // fused time-step reduction: the full stage leaves min(t_dyn), min(t_mp) of the new state in ddt
-  // (second-order stages only: the first-order instances of k_stage_rows2 carry no reduction code)
-  const bool fuse_dt = h->fuse_dt && is_full_step && space_ooa == 2 && a.use_march != 0
-                       && ((h->g.ndim == 3 && h->g.nbc[2] >= 2) || h->g.ndim == 2) && a.out == h->dP;
-  a.dtres = nullptr;
-  a.cfl = cfg.cfl;
-  // pressure-range summary of the array this launch writes: whole stages of the rows kernel on a grid of ordinary
-  // cells, rows per wavefront dividing the block height
-  a.hsum = nullptr;
-  a.hsum_n = 0;
-  a.hsum_nbx = a.hsum_nby = a.hsum_nbz = 0;
-  h->sum_arr = nullptr;
-  h->sum_bc = false;
-  const bool leave_sum = first && last && h->dhll && h->screen_ok && a.plain_cells && a.rows >= 1 && cfg.cooling == 0
-                         && !h->deta && !a.fc.mp.present
-                         && PION_SCR_BY % a.rows == 0 && !(is_full_step && a.out == h->dPh);
-  if (leave_sum) {
-    a.hsum = h->dsum;
-    a.hsum_n = scr_total(h->scr);
-    a.hsum_nbx = h->scr.nb[0];
-    a.hsum_nby = h->scr.nb[1];
-    a.hsum_nbz = h->scr.nb[2];
-    HCHECK(h, hipMemsetAsync(h->dsum, 0, 2 * (size_t)a.hsum_n * sizeof(unsigned long long), ls));
-  }
-  // the cooling time: not in the stage kernel's fused reduction but in its own launch behind the last part of the
-  // stage (k_dt_mp, rate tables in LDS; PION_SPLIT_DT_MP=0: fused, A/B)
-  const bool split_mp = fuse_dt && mp_dt_limited(cfg) && h->split_dt_mp;
-  a.dt_mp = (mp_dt_limited(cfg) && !split_mp) ? 1 : 0;
-  h->dt_cached = false;
-  if (fuse_dt) {
-    if (first)
-      HCHECK(h, hipMemcpyAsync(h->ddt, h->ddt_init, 2 * sizeof(double), hipMemcpyDeviceToDevice, ls));
-    a.dtres = h->ddt;
-  }
-  if (first && !last && h->concurrent_strips && !h->timing && h->comm_stream && h->comm_stream != h->stream) {
-    // interior part of a split stage: everything the z-boundary strips depend on besides the halo (the
-    // previous stage, its boundary update, this part's flags, the reset of the dt minima) is on the stream up
-    // to here -- the strips may run beside the interior kernel from this point on (pion_gpu_stage_part)
-    if (!h->ev_pre) HCHECK(h, hipEventCreateWithFlags(&h->ev_pre, hipEventDisableTiming));
-    HCHECK(h, hipEventRecord(h->ev_pre, ls));
-    h->ev_pre_valid = true;
-  }
-  time_begin(h, 0);
-  rc = cfg.strict_fp ? fp_strict::launch_stage(a, ls) : fp_fast::launch_stage(a, ls);
-  time_end(h, 0);
-  if (rc != 0) {
-    h->err = "stage kernel launch failed (unsupported eqn/solver/tracer combination?)";
-    return PION_GPU_EDEVICE;
-  }
-  if (!last) return 0;
-  if (split_mp) {
-    // (a part launched on the side stream runs beside the interior part: the launch then follows where the compute
-    // stream has joined both, pion_gpu_stage_part)
-    if (use_ls) h->dt_mp_pending = true;
-    else if (int rc2 = launch_cooling_time(h, ls)) return rc2;
-  }
-  if (is_full_step && a.out == h->dPh) {
-    // OA1/OA1: copy the result back to P ("P = Ph", time_integrator.cpp:938-939)
-    const size_t nb = sizeof(double) * (size_t)cfg.nvar * h->g.ncell;
-    HCHECK(h, hipMemcpyAsync(h->dP, h->dPh, nb, hipMemcpyDeviceToDevice, ls));
-  }
-  h->ph_valid = !is_full_step;
-  h->dt_cached = fuse_dt;
-  if (leave_sum) h->sum_arr = a.out;
-  h->xghost_fresh = a.xwrap ? ((is_full_step && a.out == h->dPh) ? h->dP : a.out) : nullptr;
-  return 0;
-}
-
-int pion_gpu_stage_part(void *handle, double dt_stage, int space_ooa, int is_full_step, int part)
-{
-  Handle *h = use(handle);
-  // planes (3-D) / rows (2-D) of the slab axis; a 1-D grid has neither and never splits
-  const int nz = h->g.ng[slab_axis(h) > 0 ? slab_axis(h) : 2], nb = h->g.nbc[slab_axis(h) > 0 ? slab_axis(h) : 2];
-  if (part == PION_STAGE_WHOLE) {
-    if (int rc = order_after_unpack(h)) return rc;
-    return stage_launch(h, dt_stage, space_ooa, is_full_step, 0, nz, true, true);
-  }
-  const bool split = stage_can_split(h);
-  if (part == PION_STAGE_INTERIOR) {
-    if (!split) return 0;  // everything happens in the boundary call
-    return stage_launch(h, dt_stage, space_ooa, is_full_step, nb, nz - nb, true, false);
-  }
-  if (part != PION_STAGE_SLABBOUNDARY) return PION_GPU_EINVAL;
-  if (split && h->ev_pre_valid && h->ev_unpacked_valid) {
-    // Two-stream mode: the strips (4 of the slab's planes: a launch of ~2100 short wavefronts on 2048 slots)
-    // go to a third stream that waits for the halo and for the point of the compute stream just before the
-    // interior kernel, so that they fill the slots the interior launch leaves idle in its last round instead
-    // of running after it; the compute stream continues behind both.
-    h->ev_pre_valid = false;
-    if (!h->bstream) HCHECK(h, hipStreamCreateWithFlags(&h->bstream, hipStreamNonBlocking));
-    if (!h->ev_bdone) HCHECK(h, hipEventCreateWithFlags(&h->ev_bdone, hipEventDisableTiming));
-    HCHECK(h, hipStreamWaitEvent(h->bstream, h->ev_pre, 0));
-    HCHECK(h, hipStreamWaitEvent(h->bstream, h->ev_unpacked, 0));
-    const int rc = stage_launch(h, dt_stage, space_ooa, is_full_step, 0, nb, false, true, nz - nb, nz, h->bstream, true);
-    if (rc) return rc;
-    HCHECK(h, hipEventRecord(h->ev_bdone, h->bstream));
-    HCHECK(h, hipStreamWaitEvent(h->stream, h->ev_bdone, 0));
-    if (h->dt_mp_pending) {
-      h->dt_mp_pending = false;
-      if (int rc2 = launch_cooling_time(h, h->stream)) return rc2;
-    }
-    return order_after_unpack(h);
-  }
-  h->ev_pre_valid = false;
-  // the z ghost planes must have arrived: order the compute stream after the last unpack
-  if (int rc = order_after_unpack(h)) return rc;
-  if (!split) return stage_launch(h, dt_stage, space_ooa, is_full_step, 0, nz, true, true);
-  return stage_launch(h, dt_stage, space_ooa, is_full_step, 0, nb, false, true, nz - nb, nz);
-}
-
-int pion_gpu_stage(void *handle, double dt_stage, int space_ooa, int is_full_step)
-{
-  return pion_gpu_stage_part(handle, dt_stage, space_ooa, is_full_step, PION_STAGE_WHOLE);
-}
-
-int pion_gpu_advance_time(void *handle, double dt, double simtime)
-{
-  Handle *h = use(handle);
-  int rc;
-  if (h->cfg.tm_ooa == 1 && h->cfg.sp_ooa == 1) {
-    if ((rc = pion_gpu_stage(handle, dt, 1, 1))) return rc;
-    return pion_gpu_update_bcs(handle, simtime, 1, 1, 0);
-  }
-  if (h->cfg.tm_ooa == 2 && h->cfg.sp_ooa == 2) {
-    if ((rc = pion_gpu_stage(handle, 0.5 * dt, 1, 0))) return rc;
-    if ((rc = pion_gpu_update_bcs(handle, simtime, 1, 2, 0))) return rc;
-    if ((rc = pion_gpu_stage(handle, dt, 2, 1))) return rc;
-    return pion_gpu_update_bcs(handle, simtime, 2, 2, 0);
-  }
-  h->err = "Bad OOA requests; choose (1,1) or (2,2)";
-  return PION_GPU_EINVAL;
-}
-
-long pion_gpu_halo_count(void *handle)
-{
-  Handle *h = use(handle);
-  if (h->g.ndim == 2) return (long)h->cfg.nvar * h->g.nbc[1] * h->g.nga[0];   // rows of the slab axis y
-  return (long)h->cfg.nvar * h->g.nbc[2] * h->g.nga[0] * h->g.nga[1];         // (0 for a 1-D grid)
-}
-static int halo_go(Handle *h, int which, int face, void *dbuf, int pack)
-{
-  const int sa = slab_axis(h);
-  if (sa < 1 || (face != 2 * sa && face != 2 * sa + 1)) return PION_GPU_EINVAL;
-  double *A = (which == 0) ? h->dP : h->dPh;
-  const long n = pion_gpu_halo_count(h);
-  hipStream_t cs = h->comm_stream ? h->comm_stream : h->stream;
-  if (cs != h->stream && pack) {
-    // the planes to send were written (stage) and their x/y ghosts filled (BCs) on the compute stream
-    if (!h->ev_packed_src) HCHECK(h, hipEventCreateWithFlags(&h->ev_packed_src, hipEventDisableTiming));
-    HCHECK(h, hipEventRecord(h->ev_packed_src, h->stream));
-    HCHECK(h, hipStreamWaitEvent(cs, h->ev_packed_src, 0));
-  }
-  hipLaunchKernelGGL(k_halo, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cs, A, (double *)dbuf, h->g,
-                     h->cfg.nvar, face, pack);
-  HCHECK(h, hipGetLastError());
-  if (cs != h->stream && !pack) {
-    if (!h->ev_unpacked) HCHECK(h, hipEventCreateWithFlags(&h->ev_unpacked, hipEventDisableTiming));
-    HCHECK(h, hipEventRecord(h->ev_unpacked, cs));
-    h->ev_unpacked_valid = true;
-  }
-  return 0;
-}
-int pion_gpu_halo_spans(void *handle, int which, pion_gpu_halo_spans_t *out)
-{
-  Handle *h = use(handle);
-  const int sa = slab_axis(h);
-  if (sa < 1 || !out) return PION_GPU_EINVAL;
-  double *A = (which == 0) ? h->dP : h->dPh;
-  // (sz: cells per plane of the slab axis -- an x-y plane in 3-D, a row with its x ghosts in 2-D)
-  const long nb = h->g.nbc[sa], nz = h->g.ng[sa], sz = (sa == 2) ? h->g.sz : h->g.sy;
-  out->recv_lo = A;                       // ghost planes 0 .. nb-1
-  out->send_lo = A + nb * sz;             // first on-grid planes
-  out->send_hi = A + nz * sz;             // last on-grid planes (all-cell planes nz .. nz+nb-1)
-  out->recv_hi = A + (nz + nb) * sz;      // ghost planes nz+nb ..
-  out->count_per_var = nb * sz;
-  out->var_stride = h->g.ncell;
-  out->nvar = h->cfg.nvar;
-  return 0;
-}
-int pion_gpu_halo_begin(void *handle)
-{
-  Handle *h = use(handle);
-  hipStream_t cs = h->comm_stream ? h->comm_stream : h->stream;
-  if (cs != h->stream) {
-    // the planes to send were written (stage) and their x/y ghosts filled (BCs) on the compute stream
-    if (!h->ev_packed_src) HCHECK(h, hipEventCreateWithFlags(&h->ev_packed_src, hipEventDisableTiming));
-    HCHECK(h, hipEventRecord(h->ev_packed_src, h->stream));
-    HCHECK(h, hipStreamWaitEvent(cs, h->ev_packed_src, 0));
-  }
-  return 0;
-}
-int pion_gpu_halo_end(void *handle)
-{
-  Handle *h = use(handle);
-  hipStream_t cs = h->comm_stream ? h->comm_stream : h->stream;
-  if (cs != h->stream) {
-    if (!h->ev_unpacked) HCHECK(h, hipEventCreateWithFlags(&h->ev_unpacked, hipEventDisableTiming));
-    HCHECK(h, hipEventRecord(h->ev_unpacked, cs));
-    h->ev_unpacked_valid = true;
-  }
-  return 0;
-}
-int pion_gpu_pack_halo(void *handle, int which, int face, void *dbuf) { return halo_go(use(handle), which, face, dbuf, 1); }
-int pion_gpu_unpack_halo(void *handle, int which, int face, void *dbuf) { return halo_go(use(handle), which, face, dbuf, 0); }
 
 int pion_gpu_interface_flux(void *handle, int n, int axis, double dt, const double *Pl, const double *Pr,
                             const double *aux, double *F, double *Pstar)

@@ -1,0 +1,180 @@
+// pion_handle.h -- shared by the translation units of the C-ABI layer: the handle behind include/pion_gpu.h's opaque
+// pointer and the helpers every entry point uses (defined in pion_gpu.hip, used there and in pion_step.hip).
+#ifndef PION_HANDLE_H
+#define PION_HANDLE_H
+
+#include <string>
+#include <vector>
+
+#include "../../include/pion_gpu.h"
+#include "kernels.h"
+
+namespace pion::impl {
+
+// The knots of the LGM99 tables: dev_wind.h's PION_ANGLE_*.  That header defines kernels, so only pion_gpu.hip includes
+// it, and asserts there that these are its values.
+constexpr int ANGLE_NTHETA = 25, ANGLE_NOMEGA = 25, ANGLE_NTEFF = 22;
+
+// stellar_wind_angle's look-up tables for one xi (setup_tables, grid/stellar_wind_angle.cpp:92-212)
+struct AngleTables {
+  double xi = 0.0;
+  double theta[ANGLE_NTHETA], omega[ANGLE_NOMEGA], Teff[ANGLE_NTEFF];
+  std::vector<double> delta;   // [omega][Teff]
+  std::vector<double> alpha;   // [omega][theta][Teff]
+};
+
+// one pion_gpu_add_wind_source source: its table, the parameters the next boundary update writes with, and the
+// activity bookkeeping of stellar_wind_evolution (evolving_wind_data: tstart, tfinish, t_next_update, is_active)
+struct WindSource {
+  int type = 0;
+  double pos[3] = {0.0, 0.0, 0.0};
+  double radius = 0.0, Bstar = 0.0;
+  std::vector<double> t, Teff, Mdot, vrot, vinf, R, X[7];
+  std::vector<double> vcrit;   // rotating source (type 2): the vcrit column
+  int elem[PION_MAX_NVAR];
+  double Mdot_c = 0.0, Vinf_c = 0.0, vrot_c = 0.0, Tw_c = 0.0, Rstar_c = 0.0;   // wind_source members, cgs
+  double vcrit_c = 0.0;
+  double tr[PION_MAX_NVAR];
+  bool active = true;
+  double tstart = 0.0, tfinish = 0.0, t_next_update = 1.0e99;
+  long off = 0, n = 0;   // range in the concatenated cell list (moving source: n = its capacity, the box size)
+  // orbital motion (orbit_period != 0): the position at set-up (dpos_init), the orbit, the box the cells are found
+  // in, the device count the compaction writes, and the compaction's scratch (all sized at set-up)
+  bool moving = false;
+  pion_gpu_wind_source orbit;   // pos = dpos_init, orbit_* (the pointers are not used)
+  int box_w[3] = {1, 1, 1};
+  long *dn = nullptr;
+  void *dscan = nullptr;
+  size_t scan_bytes = 0;
+};
+
+struct Handle {
+  pion_gpu_config cfg;
+  GridDesc g;
+  int device = 0;
+  int ncu = 0;            // compute units of the device (launch shaping)
+  hipStream_t stream = 0;
+  hipStream_t comm_stream = 0;     // pack/unpack of the z halo (0: the compute stream)
+  hipEvent_t ev_packed_src = nullptr, ev_unpacked = nullptr;
+  hipStream_t bstream = 0;         // the z-boundary strips of a split stage (two-stream mode): beside the interior part
+  hipEvent_t ev_pre = nullptr, ev_bdone = nullptr;
+  bool ev_pre_valid = false;
+  bool concurrent_strips = true;   // PION_CONCURRENT_STRIPS=0: strips after the interior part on the compute stream
+  bool ev_unpacked_valid = false;
+  double *dP = nullptr, *dPh = nullptr;
+  bool own_state = true;
+  uint8_t *dflags = nullptr, *dhll = nullptr;
+  double *deta = nullptr;
+  double *dsphvol = nullptr;   // spherical 1-D: shell volumes/(4 pi) per cell
+  int *derr = nullptr;
+  unsigned long long *ddt = nullptr;   // [0]=min t_dyn, [1]=min t_mp (bit patterns)
+  unsigned long long *ddt_init = nullptr;  // {1e100, 1e99} on the device: reset source (no host buffer in flight)
+  double *hdt = nullptr;               // pinned host staging of {t_dyn, t_mp, error word} (pion_gpu_dt_request)
+  hipEvent_t ev_dt = nullptr;
+  bool dt_requested = false;
+  std::vector<uint8_t> hflags;
+  // boundary state
+  double refval[6][PION_MAX_NVAR];
+  int dmr2_cols = 0;
+  long nwind = 0;
+  long njet = 0;          // jet inflow cells (XN ghosts), one state for all
+  long *djet_idx = nullptr;
+  double *djet_state = nullptr;
+  long *dwind_idx = nullptr;
+  double *dwind_state = nullptr;
+  // wind sources (pion_gpu_add_wind_source): cells of all sources concatenated in id order, each in cell-id order
+  std::vector<WindSource> wsrc;
+  long nws = 0;              // cells of all sources
+  long *dws_idx = nullptr;
+  double *dws_dist = nullptr, *dws_off = nullptr, *dws_state = nullptr;   // off: [3][nws]; state: [nws][nvar]
+  double *dws_theta = nullptr;   // stellar_wind::add_cell's theta (fixed sources; read by rotating ones)
+  // rotating sources (pion_gpu_add_rotating_wind_source): the LGM99 tables, built at the first one, for its xi
+  bool have_angle = false;
+  AngleTables angle;
+  // cooling
+  CoolDev cool;
+  double *dcoolT = nullptr, *dcooltab = nullptr, *dcoolslope = nullptr;
+  bool have_tables = false;
+  // solver state
+  double glm_chyp = 0.0, glm_cr = 0.0;
+  double refvec_avg[PION_MAX_NVAR];
+  bool ph_valid = false;  // dPh holds a genuine half-step state
+  bool dt_cached = false; // ddt holds the time-step minima of the current P (left by the last full stage)
+  std::string err;
+  // timing
+  bool timing = false;
+  std::vector<hipEvent_t> ev[4];
+  double Mu_tot_over_kB = 0.0;
+  int use_march = 3, zchunk = 0, rows = 0;  // zchunk 0: chosen per launch; rows 0: chosen per instance (rows2_plan, rows_tiling.h)
+  int rows1 = 0;                            // rows of the first-order stage (PION_ROWS1)
+  const double *xghost_fresh = nullptr;   // array whose x ghosts (periodic x) the last stage kernel wrote itself
+  int zslope_lds = 1;     // k_stage_rows2: carry the z slope in LDS (default; PION_ZSLOPE_LDS=0: rebuild it from plane k-1, R = 4)
+  double *ddE = nullptr;  // cooling source per cell (k_cooling_dE -> k_stage_rows2)
+  bool fuse_dt = true;    // PION_FUSE_DT=0: always run k_dt (A/B)
+  bool uneven_chunks = true;   // PION_UNEVEN_CHUNKS=0: equal plane chunks (A/B)
+  bool dt_mp_pending = false;  // k_dt_mp owed after the two streams of a split stage have joined
+  bool split_dt_mp = true;     // PION_SPLIT_DT_MP=0: cooling time inside the stage kernel's fused reduction (A/B)
+  bool fuse_bc = true;    // PION_FUSE_BC=0: periodic faces one launch per face (A/B)
+  // Screened HLLD -> HLL switch prepass (hll_screen.h): a whole-stage launch of k_stage_rows2 leaves the pressure range
+  // of every block of the array it writes in dsum; the next stage's prepass evaluates only the blocks that are not
+  // provably calm.  sum_arr: the array dsum describes (null: none), valid for the prepass once sum_bc says that the
+  // boundary update has refilled that array's ghost cells; dropped by everything else that writes the state.
+  bool hll_screen = true;      // PION_HLL_SCREEN=0: always the dense prepass (A/B)
+  bool screen_ok = false;      // grid, boundary types and cell lists admit the screen (screen_admitted)
+  ScrGeom scr;
+  unsigned long long *dsum = nullptr;   // [2][blocks]: keys of the maxima, of the minima
+  int *dscr_list = nullptr, *dscr_count = nullptr;
+  const double *sum_arr = nullptr;
+  bool sum_bc = false;
+  bool last_prepass_screened = false;
+};
+
+// the state arrays, the cell flags or the tables were written from outside the stages: what the last stage left
+// about its result (time-step minima, pressure summary) no longer holds
+static inline void state_changed(Handle *h)
+{
+  h->dt_cached = false;
+  h->sum_arr = nullptr;
+  h->sum_bc = false;
+}
+
+#define HCHECK(h, call)                                                            \
+  do {                                                                             \
+    hipError_t e_ = (call);                                                        \
+    if (e_ != hipSuccess) {                                                        \
+      (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
+      return PION_GPU_EDEVICE;                                                     \
+    }                                                                              \
+  } while (0)
+
+// Every entry point selects the handle's device first: the current device is per-thread state, and
+// distinct handles may be driven from distinct host threads (or interleaved on one thread).
+static inline Handle *use(void *handle)
+{
+  Handle *h = (Handle *)handle;
+  if (h) (void)hipSetDevice(h->device);
+  return h;
+}
+
+// Two-stream mode: everything on the compute stream that touches the z ghost planes must run after
+// the last unpack on the comm stream.  One wait is enough, later work is ordered behind it.
+int order_after_unpack(Handle *h);
+long cell_id(const GridDesc &g, int ix, int iy, int iz);
+void time_begin(Handle *h, int slot);
+inline void time_end(Handle *h, int slot) { time_begin(h, slot); }
+FluxCtx make_fluxctx(const Handle *h, double fv_dt);
+int check_errword(Handle *h);
+
+// get_mp_timescales_no_radiation (calc_timestep.cpp:445-459): EP.MP_timestep_limit 1, 2, 3 ask
+// mp_only_cooling::timescales for the cooling time (tc = true); 4 (recombination time only) gets 1e99
+// from it (mp_only_cooling.cpp:338), i.e. no limit; anything else is fatal there (EINVAL in create).
+static inline bool mp_dt_limited(const pion_gpu_config &cfg)
+{
+  return cfg.cooling != 0 && cfg.mp_timestep_limit >= 1 && cfg.mp_timestep_limit <= 3;
+}
+
+// legacy wind list or wind sources present: the stage kernels read the cell flags, and the periodic ghost images
+// are not fused into one launch
+static inline bool any_wind(const Handle *h) { return h->nwind > 0 || h->nws > 0; }
+}  // namespace pion::impl
+#endif

@@ -1,6 +1,6 @@
 // rows_tiling.h -- geometry of the 3-D / 2-D stage kernel k_stage_rows2 (stage_rows2.h): which cells, rows and planes
 // a workgroup, wavefront and lane take, the grid that covers them, and the host's launch plan (rows per wavefront,
-// plane chunks).  Shared by the kernel, its launcher (stage_rows2.h), the C-ABI layer (pion_gpu.hip) and the tests'
+// plane chunks).  Shared by the kernel, its launcher (stage_rows2.h), the C-ABI layer (pion_step.hip) and the tests'
 // host-side coverage probe (tests/native/tiling_probe.cpp); it includes nothing, so that the probe compiles it as
 // plain host code.  The per-launch functions are templates over the argument struct: they read a.g.ng[0..1],
 // a.rows, a.kz0..a.kz3, a.zchunk, a.nzb and a.zcmax, nothing else.
@@ -13,7 +13,7 @@
 //
 // 2-D row ranges.  A 2-D launch has one "plane" and no z part; it updates a RANGE of on-grid rows [ky0, ky1) and, for
 // the two boundary strips of a slab cut along y, a second range [ky2, ky3) of the same length.  The launcher
-// (stage_launch, pion_gpu.hip) encodes a range in the members the geometry already reads, so nothing here changes:
+// (stage_ranges, pion_step.hip) encodes a range in the members the geometry already reads, so nothing here changes:
 //   a.g.ng[1] = ky1 - ky0            the rows that are tiled: rows_tiling, rows2_nblocks and rows2_pick_rows_2d_rule
 //                                    are sized from the range, row groups start at its first row;
 //   a.kz0 = ky0, a.kz1 = ky0 + 1     one chunk (zchunk >= 1, nzb = 0) whose "plane" number k0 is the range's first row;
@@ -300,7 +300,7 @@ inline int rows2_nzb(const int np, const int zcmax, const bool uneven)
   return (uneven && np >= 16) ? zchunk_bounds(np, zcmax, 0, &k0, &k1) : 0;
 }
 
-// The launch plan of one stage (pion_gpu.hip, launch of a stage part): rows per wavefront, whether the 2-D launcher
+// The launch plan of one stage (stage_tiling, pion_step.hip): rows per wavefront, whether the 2-D launcher
 // may refine them (rows2_pick_rows_2d_rule with the instance's occupancy), planes per equal chunk, the uneven chunks'
 // longest length and their number.  march: k_stage_rows2 runs (else only zchunk is set, for the cell kernel).
 struct Rows2PlanIn {

@@ -20,7 +20,7 @@ cd variants/r1/pion_amd/csrc
 make -j8 > /dev/null 2>&1
 cp libpion_gpu.so $ROOT/variants/r1_good.so
 C="--offload-arch=gfx950 -fno-slp-vectorize -fPIC -std=c++17 -Wno-unused-variable -Wno-unused-but-set-variable -Wno-pass-failed -Wno-unused-value -ffp-contract=off -DPION_FPNS=fp_strict -DPION_EQSEL=2 -O2"
-link() { /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $ROOT/variants/r1_$1.so build/kernels_strict_0.o build/kernels_strict_1.o build/s2_$1.o build/kernels_strict_3.o build/kernels_fast_0.o build/kernels_fast_1.o build/kernels_fast_2.o build/kernels_fast_3.o build/pion_gpu.o; }
+link() { /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $ROOT/variants/r1_$1.so build/kernels_strict_0.o build/kernels_strict_1.o build/s2_$1.o build/kernels_strict_3.o build/kernels_fast_0.o build/kernels_fast_1.o build/kernels_fast_2.o build/kernels_fast_3.o build/pion_gpu.o $(ls build/pion_step.o 2>/dev/null); }   # (pion_step.o: the trees that split the C-ABI layer)
 /opt/rocm/bin/hipcc $C -c kernels_fp.hip -o build/s2_bad.o && link bad
 i=0
 for f in -enable-misched=0 -enable-post-misched=0 -disable-machine-licm -disable-machine-sink -vgpr-regalloc=basic -sgpr-regalloc=basic -amdgpu-spill-sgpr-to-vgpr=0 -amdgpu-enable-rewrite-partial-reg-uses=0; do

@@ -1,12 +1,16 @@
 """pion_gpu_stage_part: interior + z-boundary parts with the z halo arriving in between (on a
 second stream) must give bit for bit the whole-stage result.  One process, one GPU: the slab's two
-z neighbours are the slab itself (periodic), so the 'transfer' is a device copy on the comm stream."""
+z neighbours are the slab itself (periodic), so the 'transfer' is a device copy on the comm stream.
+
+The HLLD cases also compare the HLLD -> HLL switch array the last stage's prepass left (check_hll_switch): the state
+alone would not notice a part that evaluates the wrong planes' flags where the switch happens to be zero."""
 import copy
 
 import numpy as np
 import pytest
 
 from pion_amd import abi, driver, problems
+from split_checks import check_hll_switch
 
 pytestmark = pytest.mark.gpu
 
@@ -56,7 +60,9 @@ def _run(cfg, P, nsteps, comm_mode):
             dts.append(sc.calculate_timestep())
             sc.advance_time()
         sc.finish_halo()
-        return dts, g.download(0)
+        nga = abi.ng_all(cfg)
+        hll = g.get_hll_switch().reshape(nga[2], nga[1], nga[0]) if cfg.solver == abi.FLUX_RS_HLLD else None
+        return dts, g.download(0), hll
 
 
 @pytest.mark.parametrize("strict", [1, 0])
@@ -68,7 +74,10 @@ def test_split_stage_equals_whole_stage(case, mode, strict):
         cfg.ng[0], cfg.ng[1] = 70, 9                      # two x tiles, ragged row groups
         cfg.ng[2] = {"glm_hlld_20": 20, "glm_hlld_nz5": 5, "glm_hlld_nz4": 4}[case]
         cfg.dx = 1.0 / 70
-        cfg.xmin[1], cfg.xmin[2] = -4.5 / 70, -0.5 * cfg.ng[2] / 70   # keep the hot sphere on the grid
+        # keep the hot sphere (radius 7 cells) on the grid: centred along y, and along z where the grid is thinner than the
+        # sphere; nz = 20: its lower edge on the ZN face, so that its surface crosses the flag planes of both strips (of
+        # the upper one through the periodic wrap) and of the interior part (check_hll_switch)
+        cfg.xmin[1], cfg.xmin[2] = -4.5 / 70, -min(0.5 * cfg.ng[2], 6.5) / 70
         P = problems.fill_mhd_blastwave(cfg)
     elif case == "mhd_hll_hcorr":
         cfg, P = problems.mhd_blastwave(12, 3, abi.EQMHD, abi.FLUX_RS_HLL, strict_fp=strict)
@@ -78,9 +87,11 @@ def test_split_stage_equals_whole_stage(case, mode, strict):
         for f in range(6):
             cfg0.bc_type[f] = abi.BC_PERIODIC
         cfg, P = cfg0, P0
-    dts_w, whole = _run(cfg, P, 3, None)
+    dts_w, whole, hll_w = _run(cfg, P, 3, None)
     cfg_s = copy.deepcopy(cfg)
     cfg_s.bc_type[4] = cfg_s.bc_type[5] = abi.BC_SLAB
-    dts_s, split = _run(cfg_s, P, 3, mode)
+    dts_s, split, hll_s = _run(cfg_s, P, 3, mode)
     assert dts_w == dts_s
     assert np.array_equal(whole, split), "%d values differ" % (whole != split).sum()
+    if hll_w is not None:
+        check_hll_switch(hll_w, hll_s, cfg.nbc)
