@@ -319,10 +319,12 @@ int pion_gpu_stage(void *handle, double dt_stage, int space_ooa, int is_full_ste
  *   PION_STAGE_WHOLE         every on-grid plane of the slab axis, after the last unpacked halo;
  *   PION_STAGE_INTERIOR      the on-grid planes [nbc, n - nbc) that read no ghost plane of the slab axis; may
  *                            be issued while the halo of the stencil array is still in flight;
- *   PION_STAGE_SLABBOUNDARY  the nbc planes next to each face of the slab axis (one launch for both strips);
- *                            ordered after the last pion_gpu_unpack_halo / pion_gpu_halo_end (comm stream)
- *                            inside the library.
- * INTERIOR followed by SLABBOUNDARY gives bit for bit the result of PION_STAGE_WHOLE (= pion_gpu_stage).
+ *   PION_STAGE_SLABBOUNDARY  the nbc planes next to each face of the slab axis (one launch for both strips; one
+ *                            launch per strip on a handle that runs its stages in plane windows, see
+ *                            pion_gpu_rows_windows); ordered after the last pion_gpu_unpack_halo /
+ *                            pion_gpu_halo_end (comm stream) inside the library.
+ * INTERIOR followed by SLABBOUNDARY gives bit for bit the result of PION_STAGE_WHOLE (= pion_gpu_stage), and so does
+ * every part run window by window.
  * Configurations the split does not cover (1-D grids, 2-D grids not run by the rows kernel -- PION_ROWS_2D=0,
  * nbc < 2 --, H-correction, first-order scheme, <= 2*nbc planes) do all the work in the SLABBOUNDARY call. */
 #define PION_STAGE_WHOLE 0
@@ -330,6 +332,28 @@ int pion_gpu_stage(void *handle, double dt_stage, int space_ooa, int is_full_ste
 #define PION_STAGE_ZBOUNDARY 2
 #define PION_STAGE_SLABBOUNDARY PION_STAGE_ZBOUNDARY
 int pion_gpu_stage_part(void *handle, double dt_stage, int space_ooa, int is_full_step, int part);
+
+/* Plane windows of the rows kernel.  k_stage_rows2 reaches fewer than 2^29 cells of an array from the array's base (a
+ * 32-bit byte offset per lane), so a grid of 2^29 cells or more per variable (ghosts included) is run in windows of
+ * planes of the slab axis (x-y planes in 3-D, rows in 2-D, Cartesian or cylindrical), one launch per window with the
+ * arrays' bases advanced to the window on the host; the result is bit for bit that of one launch.  With s cells per
+ * plane, W = floor((limit - 1) / s) - 2 nbc planes fit in one window; a range [lo, hi) of on-grid planes becomes
+ * ceil((hi - lo) / W) windows, in order, sizes balanced within one plane, longer ones first.  W < 1 (one plane with
+ * its ghost planes exceeds the limit), 1-D grids and grids with nbc < 2 stay on the cell-per-thread kernel.
+ *   pion_gpu_rows_windows      the plan for the slab axis of `cfg`: returns the number of windows of [lo, hi) and
+ *                              writes the first max_windows of them to w_lo[] / w_hi[] (NULL allowed for
+ *                              max_windows = 0); 0: not admitted, the cell-per-thread kernel runs.  limit_cells
+ *                              <= 0: the default, 2^29.  Host only: needs no device or handle.  EINVAL: a NULL or
+ *                              malformed cfg, lo < 0, hi > ng of the slab axis, lo >= hi, limit_cells > 2^29,
+ *                              max_windows < 0.
+ *   pion_gpu_get_rows_windows  what a handle does: its limit (2^29; PION_ROWS_WINDOW_CELLS in the environment at
+ *                              create, for tests and measurements; PION_ROWS_WINDOWS=0: no windows, the
+ *                              cell-per-thread kernel from 2^29 cells), the windows of a whole stage (1: one launch;
+ *                              0: the handle runs the cell-per-thread kernel) and the number of stage-kernel
+ *                              launches the last stage part issued.  NULL outputs are skipped. */
+int pion_gpu_rows_windows(const pion_gpu_config *cfg, long limit_cells, int lo, int hi, int max_windows, int *w_lo,
+                          int *w_hi);
+int pion_gpu_get_rows_windows(void *handle, long *limit_cells, int *windows_whole_stage, int *launches_last_part);
 
 /* time_integrator::advance_time (time_integrator.cpp:72-142) for OA1/OA1 and
  * OA2/OA2: stages + boundary updates. */

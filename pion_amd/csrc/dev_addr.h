@@ -8,7 +8,10 @@
 // folded into the scalar base, the x neighbours into the instruction's immediate offset, and the one
 // per-lane quantity -- the cell -- is a single VGPR per row.  (With 64-bit per-lane addresses the compiler
 // hoists one VGPR pair per load site out of the task loop: ~80 registers, which do not exist here.)
-// Needs 8 * ncell < 2^32 (pion_gpu_create picks the cell-per-thread kernel otherwise; 512^3 with ghosts is 1.1e9).
+// One launch therefore reaches fewer than 2^29 cells of an array from the base it is given (512^3 with ghosts is 1.4e8
+// cells, 1.1e9 bytes).  A larger grid is launched in plane windows, each with the bases advanced to its window on the
+// host (rows_tiling.h, "plane windows"; stage_launch, pion_step.hip): nothing here changes for it.  The marching
+// prepass is not windowed: launch_prepass uses it only while 8 * ncell < 2^32 and the dense 64-bit kernel otherwise.
 // (readfirstlane keeps the optimiser from re-associating base + offset into per-lane 64-bit arithmetic; on a
 // value that already lives in SGPRs it costs nothing.  The access is made through an address_space(1)
 // pointer so that it stays a global_ instruction after the integer round trip.)

@@ -1131,12 +1131,27 @@ int pion_gpu_create(const pion_gpu_config *cfg, int device, void **handle)
   g.sph_vol = nullptr;
   *handle = h;
   // k_stage_rows2 (3-D, two ghost layers) addresses every array as "uniform base + 32-bit byte offset of the
-  // cell": grids of 2^29 cells or more (ghosts included) use the cell-per-thread kernel with 64-bit addresses
-  // (2-D Cartesian grids run it without the z part; PION_ROWS_2D=0 puts them back on the cell-per-thread kernel)
+  // cell": one launch reaches fewer than 2^29 cells (ghosts included) of an array.  A larger grid runs it in plane
+  // windows, one launch per window with the arrays' bases advanced on the host (rows_tiling.h, "plane windows";
+  // stage_launch, pion_step.hip); a grid whose single plane with its ghost planes exceeds the limit, and with
+  // PION_ROWS_WINDOWS=0 every grid of 2^29 cells or more, uses the cell-per-thread kernel with 64-bit addresses
+  // (2-D grids run the rows kernel without the z part; PION_ROWS_2D=0 puts them back on the cell-per-thread kernel)
   const bool rows3d = (g.ndim == 3 && g.nbc[2] >= 2);
   bool rows2d = (g.ndim == 2 && g.cyl != 2 && g.nbc[1] >= 2 && g.nbc[0] >= 2);   // (cyl == 1: the CYL instance)
   if (const char *e = getenv("PION_ROWS_2D")) rows2d = rows2d && (atoi(e) != 0);
-  if (!((rows3d || rows2d) && (unsigned long long)g.ncell * 8ull < (1ull << 32))) h->use_march = 0;
+  bool windows = true;
+  if (const char *e = getenv("PION_ROWS_WINDOWS")) windows = (atoi(e) != 0);
+  if (const char *e = getenv("PION_ROWS_WINDOW_CELLS")) {
+    const long v = atol(e);
+    if (windows && v >= 1 && v <= PION_ROWS_WINDOW_CELLS) h->win_cells = v;   // (never more than the offsets can reach)
+  }
+  if (rows3d || rows2d) {
+    const int sa = g.ndim - 1;
+    h->win_whole = windows ? rows_windows_count(0, g.ng[sa], (sa == 2) ? g.sz : g.sy, g.nbc[sa], h->win_cells)
+                           : (g.ncell < PION_ROWS_WINDOW_CELLS ? 1 : 0);
+  }
+  if (h->win_whole < 1) h->use_march = 0;
+  if (h->use_march == 0) h->win_whole = 0;
 
   const size_t nb = sizeof(double) * (size_t)cfg->nvar * g.ncell;
   HCHECK(h, hipMalloc(&h->dP, nb));

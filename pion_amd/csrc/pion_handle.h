@@ -107,6 +107,12 @@ struct Handle {
   double Mu_tot_over_kB = 0.0;
   int use_march = 3, zchunk = 0, rows = 0;  // zchunk 0: chosen per launch; rows 0: chosen per instance (rows2_plan, rows_tiling.h)
   int rows1 = 0;                            // rows of the first-order stage (PION_ROWS1)
+  // Plane windows of the rows kernel (rows_tiling.h, "plane windows"): the cells one launch may reach (2^29;
+  // PION_ROWS_WINDOW_CELLS: tests and measurements), the windows a whole stage takes (1: today's one launch; 0: the
+  // cell-per-thread kernel runs) and the stage-kernel launches of the last part that was issued
+  long win_cells = PION_ROWS_WINDOW_CELLS;
+  int win_whole = 0;
+  int launches_last_part = 0;
   const double *xghost_fresh = nullptr;   // array whose x ghosts (periodic x) the last stage kernel wrote itself
   int zslope_lds = 1;     // k_stage_rows2: carry the z slope in LDS (default; PION_ZSLOPE_LDS=0: rebuild it from plane k-1, R = 4)
   double *ddE = nullptr;  // cooling source per cell (k_cooling_dE -> k_stage_rows2)

@@ -91,7 +91,8 @@ static bool screen_admitted(Handle *h)
   const pion_gpu_config &cfg = h->cfg;
   if (!h->hll_screen || !h->dhll || cfg.ndim != 3 || h->g.cyl != 0 || h->use_march == 0 || h->g.nbc[2] < 2) return false;
   if (any_wind(h) || h->njet > 0 || cfg.bc_dmach2) return false;
-  if (h->g.ncell * 8L >= (1L << 32)) return false;
+  // (plane windows: the summary's block indices are absolute plane numbers, which a rebased launch does not know)
+  if (h->g.ncell * 8L >= (1L << 32) || h->win_whole > 1) return false;
   int per[3];
   for (int d = 0; d < 3; d++) {
     for (int f = 2 * d; f < 2 * d + 2; f++) {
@@ -273,13 +274,13 @@ int stage_ranges(Handle *h, const StagePart &pt, StageArgs &a)
 }
 
 // rows per wavefront, plane chunks (rows_tiling.h; PION_ROWS / PION_ROWS1 / PION_ZCHUNK / PION_UNEVEN_CHUNKS override)
-void stage_tiling(const Handle *h, const StagePart &pt, StageArgs &a)
+void stage_tiling(const Handle *h, const int np, StageArgs &a)
 {
   Rows2PlanIn p;
   p.ndim = h->g.ndim;
   p.nx = h->g.ng[0];
   p.ny = a.g.ng[1];                        // (2-D: the rows of the range, which is what the launch tiles)
-  p.np = (h->g.ndim == 3) ? pt.r[0].n() : 1;   // (the first range only)
+  p.np = (h->g.ndim == 3) ? np : 1;        // (the planes of the first range)
   p.ncu = h->ncu;
   p.nv = h->cfg.nvar;
   p.euler = (h->cfg.eqntype == PION_EQEUL);
@@ -296,6 +297,35 @@ void stage_tiling(const Handle *h, const StagePart &pt, StageArgs &a)
   a.zchunk = pl.zchunk;
   a.zcmax = pl.zcmax;
   a.nzb = pl.nzb;
+}
+
+// Plane windows (rows_tiling.h, "plane windows"): while a whole stage of the handle takes more than one window, every
+// range of a part is launched window by window -- the two strips of a split stage as launches of their own --, each
+// launch a copy of the part's arguments REBASED to its window [w_lo, w_hi): every per-cell pointer advanced by w_lo
+// planes (3-D) / rows (2-D) of the slab axis in 64-bit host arithmetic, the window's planes numbered from 0, the tiling
+// planned for the window.  g.ncell, the stride from variable to variable, stays the grid's.  The cylindrical instance
+// takes R from the row number: its copy of xmin[1] moves with the window (the slab rule, DESIGN.md s5 "Positions").
+bool stage_windowed(const Handle *h) { return h->use_march != 0 && h->win_whole > 1 && h->g.ndim >= 2; }
+StageArgs stage_window(const Handle *h, const StageArgs &part, const int w_lo, const int w_hi)
+{
+  StageArgs a = part;
+  const long off = (long)w_lo * ((h->g.ndim == 3) ? h->g.sz : h->g.sy);   // cells from the array's base to the window's
+  a.S += off;
+  a.Pc += off;
+  a.out += off;
+  a.flags += off;
+  if (a.hllflag) a.hllflag += off;
+  if (a.eta) a.eta += off;
+  if (a.dE) a.dE += off;
+  a.kz0 = a.kz2 = a.kz3 = 0;
+  if (h->g.ndim == 3) a.kz1 = w_hi - w_lo;
+  else {
+    a.g.ng[1] = w_hi - w_lo;   // (rows_tiling.h, "2-D row ranges": the range [0, w_hi - w_lo) of the rebased array)
+    a.kz1 = 1;
+    if (h->g.cyl == 1) a.g.xmin[1] = h->g.xmin[1] + w_lo * h->g.dx;
+  }
+  stage_tiling(h, w_hi - w_lo, a);
+  return a;
 }
 
 // what a launch does besides the update: decided, then into StageArgs and onto the stream
@@ -368,7 +398,7 @@ int stage_launch(Handle *h, const StageStep &st, const StagePart &pt)
   if (int rc = stage_arrays(h, st, S, a)) return rc;
   stage_physics(h, st, a);
   if (int rc = stage_ranges(h, pt, a)) return rc;
-  stage_tiling(h, pt, a);
+  stage_tiling(h, pt.r[0].n(), a);
   if (h->cfg.cooling != 0 && a.use_march != 0) {
     // calc_noRT_microphysics_dU as its own launch (thread per cell, full occupancy): dE per cell
     a.dE = h->ddE;
@@ -386,9 +416,26 @@ int stage_launch(Handle *h, const StageStep &st, const StagePart &pt)
     HCHECK(h, hipEventRecord(h->ev_pre, pt.stream));
     h->ev_pre_valid = true;
   }
-  if (int rc = fp_launch(h, 0, fp_strict::launch_stage, fp_fast::launch_stage, a, pt.stream,
-                         "stage kernel launch failed (unsupported eqn/solver/tracer combination?)"))
-    return rc;
+  const char *const failed = "stage kernel launch failed (unsupported eqn/solver/tracer combination?)";
+  h->launches_last_part = 0;
+  if (!stage_windowed(h)) {
+    if (int rc = fp_launch(h, 0, fp_strict::launch_stage, fp_fast::launch_stage, a, pt.stream, failed)) return rc;
+    h->launches_last_part = 1;
+  }
+  else {
+    const int sa = slab_axis(h);
+    const long sst = (sa == 2) ? h->g.sz : h->g.sy;
+    for (const Range &r : pt.r) {
+      const int nw = rows_windows_count(r.lo, r.hi, sst, h->g.nbc[sa], h->win_cells);   // (0 for an empty range)
+      for (int i = 0; i < nw; i++) {
+        int w_lo, w_hi;
+        rows_window(r.lo, r.hi, nw, i, &w_lo, &w_hi);
+        const StageArgs w = stage_window(h, a, w_lo, w_hi);
+        if (int rc = fp_launch(h, 0, fp_strict::launch_stage, fp_fast::launch_stage, w, pt.stream, failed)) return rc;
+        h->launches_last_part++;
+      }
+    }
+  }
   return pt.last ? stage_end(h, st, pt, x, a) : 0;
 }
 
@@ -528,6 +575,36 @@ int pion_gpu_stage_part(void *handle, double dt_stage, int space_ooa, int is_ful
 int pion_gpu_stage(void *handle, double dt_stage, int space_ooa, int is_full_step)
 {
   return pion_gpu_stage_part(handle, dt_stage, space_ooa, is_full_step, PION_STAGE_WHOLE);
+}
+
+int pion_gpu_rows_windows(const pion_gpu_config *cfg, long limit_cells, int lo, int hi, int max_windows, int *w_lo,
+                          int *w_hi)
+{
+  if (!cfg || cfg->ndim < 1 || cfg->ndim > 3 || cfg->nbc < 1 || max_windows < 0) return PION_GPU_EINVAL;
+  if (max_windows > 0 && (!w_lo || !w_hi)) return PION_GPU_EINVAL;
+  if (limit_cells > PION_ROWS_WINDOW_CELLS) return PION_GPU_EINVAL;   // (more than a 32-bit byte offset reaches)
+  for (int a = 0; a < cfg->ndim; a++)
+    if (cfg->ng[a] < 1) return PION_GPU_EINVAL;
+  const int sa = cfg->ndim - 1;
+  if (lo < 0 || hi > cfg->ng[sa] || lo >= hi) return PION_GPU_EINVAL;
+  // the grids pion_gpu_create gives to the rows kernel: 3-D and 2-D (not spherical) with two ghost layers
+  if (cfg->ndim == 1 || cfg->nbc < 2 || cfg->coord_sys == 3) return 0;
+  const long L = (limit_cells <= 0) ? PION_ROWS_WINDOW_CELLS : limit_cells;
+  long s = cfg->ng[0] + 2L * cfg->nbc;
+  if (sa == 2) s *= cfg->ng[1] + 2L * cfg->nbc;
+  const int nw = rows_windows_count(lo, hi, s, cfg->nbc, L);
+  for (int i = 0; i < nw && i < max_windows; i++) rows_window(lo, hi, nw, i, &w_lo[i], &w_hi[i]);
+  return nw;
+}
+
+int pion_gpu_get_rows_windows(void *handle, long *limit_cells, int *windows_whole_stage, int *launches_last_part)
+{
+  const Handle *h = (const Handle *)handle;
+  if (!h) return PION_GPU_EINVAL;
+  if (limit_cells) *limit_cells = h->win_cells;
+  if (windows_whole_stage) *windows_whole_stage = h->win_whole;
+  if (launches_last_part) *launches_last_part = h->launches_last_part;
+  return 0;
 }
 
 int pion_gpu_advance_time(void *handle, double dt, double simtime)

@@ -341,6 +341,38 @@ inline Rows2Plan rows2_plan(const Rows2PlanIn &p)
   return o;
 }
 
+// ---- plane windows ----
+//
+// k_stage_rows2 addresses a cell as "uniform base + one 32-bit byte offset per lane" (dev_addr.h): one launch reaches
+// fewer than PION_ROWS_WINDOW_CELLS = 2^29 cells of a per-cell array from the array's base.  A larger grid is run in
+// WINDOWS of planes of the slab axis (z planes in 3-D, rows in 2-D): the host (stage_launch, pion_step.hip) launches
+// the kernel once per window, with every per-cell pointer advanced to the window's first plane in 64-bit host
+// arithmetic and the window's planes numbered from 0 -- the kernel reads no absolute plane number.
+//
+// A launch that updates n planes touches n + 2 nbc planes of the all-cell array (its stencil, the priming plane
+// included), counted from the all-cell plane the pointers were advanced to.  With s cells per plane and a limit of L
+// cells, W = floor((L - 1) / s) - 2 nbc planes fit in one window: (W + 2 nbc) s <= L - 1 < L.  W < 1 -- one plane with
+// its ghost planes already exceeds the limit -- is not admitted: such a grid stays on the cell-per-thread kernel.
+// A range [lo, hi) of on-grid planes becomes ceil((hi - lo) / W) windows -- no plan has fewer --, in order, sizes
+// balanced within one plane, the longer ones first.  A range that fits is ONE window, the range itself.
+#define PION_ROWS_WINDOW_CELLS (1L << 29)
+
+inline long rows_window_planes(const long s, const int nbc, const long L) { return (s > 0) ? (L - 1) / s - 2L * nbc : 0; }
+// number of windows of [lo, hi) (0: not admitted, or an empty range)
+inline int rows_windows_count(const int lo, const int hi, const long s, const int nbc, const long L)
+{
+  const long W = rows_window_planes(s, nbc, L);
+  if (W < 1 || hi <= lo) return 0;
+  return (int)(((long)(hi - lo) + W - 1) / W);
+}
+// window number i of the nw windows of [lo, hi): [*w_lo, *w_hi)
+inline void rows_window(const int lo, const int hi, const int nw, const int i, int *w_lo, int *w_hi)
+{
+  const int n = hi - lo, base = n / nw, extra = n % nw;   // the first `extra` windows take one plane more
+  *w_lo = lo + i * base + (i < extra ? i : extra);
+  *w_hi = *w_lo + base + (i < extra ? 1 : 0);
+}
+
 }  // namespace pion
 
 #endif

@@ -60,6 +60,10 @@ def load_library():
     if hasattr(lib, "pion_gpu_get_hll_switch"):   # (a PION_GPU_LIB build for A/B runs may predate these two read-backs)
         lib.pion_gpu_get_hll_switch.argtypes = [C.c_void_p, C.c_void_p]
         lib.pion_gpu_get_hll_screen_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(lib, "pion_gpu_rows_windows"):   # (likewise)
+        _ip = C.POINTER(C.c_int)
+        lib.pion_gpu_rows_windows.argtypes = [C.POINTER(abi.PionGpuConfig), C.c_long, C.c_int, C.c_int, C.c_int, _ip, _ip]
+        lib.pion_gpu_get_rows_windows.argtypes = [C.c_void_p, C.POINTER(C.c_long), _ip, _ip]
     lib.pion_gpu_set_cooling_tables.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     lib.pion_gpu_update_bcs.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int]
     lib.pion_gpu_calc_dt.argtypes = [C.c_void_p, _dp, _dp]
@@ -98,7 +102,24 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_add_wind_source", "pion_gpu_get_wind_cells", "pion_gpu_get_wind_source_pos",
     "pion_gpu_wind_orbit_position", "pion_gpu_get_flags", "pion_gpu_add_rotating_wind_source",
     "pion_gpu_wind_angle_tables", "pion_gpu_get_hll_switch", "pion_gpu_get_hll_screen_counts",
+    "pion_gpu_rows_windows", "pion_gpu_get_rows_windows",
 ]
+
+
+def rows_windows(cfg, lo=0, hi=None, limit=None):
+    """pion_gpu_rows_windows: the plane windows [(w_lo, w_hi), ...] the rows kernel takes for the on-grid planes
+    [lo, hi) of the slab axis of `cfg` (hi None: all of them) under a limit of `limit` cells per launch (None: the
+    default, 2^29); [] where the grid stays on the cell-per-thread kernel.  Host only: needs no GPU."""
+    lib = load_library()
+    if hi is None:
+        hi = cfg.ng[cfg.ndim - 1]
+    lim = 0 if limit is None else int(limit)
+    n = lib.pion_gpu_rows_windows(C.byref(cfg), lim, lo, hi, 0, None, None)
+    if n < 0:
+        raise PionGpuError("rows_windows", n, "invalid arguments")
+    w_lo, w_hi = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
+    n = lib.pion_gpu_rows_windows(C.byref(cfg), lim, lo, hi, n, w_lo, w_hi)
+    return [(w_lo[i], w_hi[i]) for i in range(n)]
 
 
 def _p(a):
@@ -246,6 +267,13 @@ class GpuSim:
         a, t = C.c_int(0), C.c_int(0)
         self._chk(self.lib.pion_gpu_get_hll_screen_counts(self.h, C.byref(a), C.byref(t)), "get_hll_screen_counts")
         return a.value, t.value
+
+    def rows_windows(self):
+        """pion_gpu_get_rows_windows: dict limit_cells, windows_whole_stage (1: one launch per stage; 0: the
+        cell-per-thread kernel runs), launches_last_part (stage-kernel launches of the last stage part issued)"""
+        lim, nw, nl = C.c_long(0), C.c_int(0), C.c_int(0)
+        self._chk(self.lib.pion_gpu_get_rows_windows(self.h, C.byref(lim), C.byref(nw), C.byref(nl)), "get_rows_windows")
+        return {"limit_cells": lim.value, "windows_whole_stage": nw.value, "launches_last_part": nl.value}
 
     def set_jet(self, jetradius, jetstate):
         st = np.ascontiguousarray(jetstate, dtype=np.float64)
