@@ -147,6 +147,20 @@ int pion_gpu_ng_all(void *handle, int axis);
 int pion_gpu_upload(void *handle, const double *P_soa);
 /* which = 0: P, 1: Ph */
 int pion_gpu_download(void *handle, int which, double *P_soa);
+/* The on-grid cells of planes [plane_lo, plane_hi) of the slab axis (the last axis: x-y planes of a 3-D grid, rows of
+ * a 2-D grid; a 1-D grid has the one "plane" [0, 1), its row), for all variables, as a contiguous DEVICE buffer
+ * [nvar][planes][ny][nx] (2-D: [nvar][planes][nx]; 1-D: [nvar][nx]) of pion_gpu_ongrid_count(handle, planes) doubles
+ * -- what dataio's writers visit with FirstPt / NextPt (no ghost cells), a chunk of planes at a time, so that a
+ * snapshot never needs a host array of the whole grid (pion_host_sim_write_snapshot streams through these).
+ *   pion_gpu_pack_ongrid    copies from the array pion_gpu_download(which) reads; enqueued on the compute stream,
+ *                           returns at once (synchronise, or order a copy on that stream, before reading dbuf).
+ *   pion_gpu_unpack_ongrid  the reverse, into BOTH P and Ph as pion_gpu_upload does; ghost cells and other planes keep
+ *                           their bits; discards what upload discards (cached time step, a requested read-back, the
+ *                           HLL-screen summary).  Between steps only; a boundary update with assign != 0 must follow.
+ * Cell ids and buffer indices are 64-bit.  EINVAL: a range outside [0, planes of the grid], an empty one, NULL dbuf. */
+long pion_gpu_ongrid_count(void *handle, int planes);
+int pion_gpu_pack_ongrid(void *handle, int which, int plane_lo, int plane_hi, void *dbuf);
+int pion_gpu_unpack_ongrid(void *handle, int plane_lo, int plane_hi, void *dbuf);
 /* adopt caller-owned device buffers (e.g. torch tensors) instead of internal ones;
  * both must hold nvar*ncell_all doubles */
 int pion_gpu_bind_device_state(void *handle, void *dP, void *dPh);

@@ -48,6 +48,57 @@ int pion_host_sim_add_rotating_wind_source(void *sim, const pion_gpu_wind_source
                                            double xi, int *id);
 int pion_host_sim_last_error(void *sim, char *buf, int len);
 
+/* ---- output times, checkpoints, snapshot and restart (pion_amd/host/snapshot_io.h)
+ *   sim_init::output_data                          sim_control/sim_init.cpp:671-760
+ *   the output-time clip of the time step          sim_control/calc_timestep.cpp:245-249
+ *   constants::equalD                              constants.cpp:48-70
+ *   the header names                               dataIO/dataio_base.cpp:60-440, 1372-1390
+ * pion_host_sim_set_output: SimPM.outFileBase, op_criterion (0: every opfreq steps, opfreq 0 = only the final state;
+ * 1: every opfreq_time time units, next_optime = simtime + opfreq_time), checkpoint_freq (<= 0: 250 steps).  From then
+ * on pion_host_sim_time_int writes <base>_<rank, 4 digits>.<step, 8 digits>.pionraw at step 0, at every output step /
+ * time and once when simtime reaches finishtime, and the checkpoints <base>_<rank>.99999998 / 99999999.pionraw in turn;
+ * with op_criterion 1 the time step is clipped to land on next_optime ("Went past output time without outputting!"
+ * when it cannot).  Without this call nothing is written and the time steps are unchanged.  Call it after
+ * pion_host_sim_init and before pion_host_sim_read_snapshot (a restart takes next_optime from the file).
+ * EINVAL: op_criterion outside {0, 1}, opfreq < 0, opfreq_time <= 0 with criterion 1, a NULL or empty base. */
+int pion_host_sim_set_output(void *sim, const char *outfile_base, int op_criterion, int opfreq, double opfreq_time,
+                             int checkpoint_freq);
+/* A rank of a slab run: the planes of the slab axis in the global problem, the first one this sim owns, and the
+ * global problem's boundary types (PION_BC_*) on the two faces of that axis -- a rank's PION_BC_SLAB faces are not a
+ * property of the problem.  Default: the sim is the whole domain.  EINVAL: a 1-D grid, a range outside the global
+ * planes, PION_BC_SLAB as a global face. */
+int pion_host_sim_set_slab_extent(void *sim, int global_planes, int plane_lo, int bc_lo, int bc_hi);
+/* The PIONRAW2 file of this sim's on-grid cells: 8-byte magic, a text header of "name value" lines (the reference's
+ * parameter names where one exists, pion_-prefixed keys otherwise; NGrid, Xmin, Xmax and BC_* describe the GLOBAL
+ * problem), then fp64 little-endian [nvar][slab_n][ny][nx] at pion_data_offset, code units, no ghost cells.  The
+ * planes leave the device a chunk at a time (pion_gpu_pack_ongrid): host memory is two chunks whatever the grid. */
+int pion_host_sim_write_snapshot(void *sim, const char *path);
+typedef struct pion_host_snapshot_info {
+  double t_start, t_finish, t_sim, min_timestep, last_dt;   /* SimPM.starttime, finishtime, simtime, min_timestep, last_dt */
+  double opfreq_time, next_optime;
+  int t_step, op_criterion, op_freq;                         /* SimPM.timestep, op_criterion, opfreq */
+  int rank, world;                                           /* the writer's */
+  int slab_lo, slab_n;                                       /* planes of the slab axis the file holds */
+  long data_offset;
+  char outfile[256];
+} pion_host_snapshot_info;
+/* Header of a snapshot: cfg = the GLOBAL configuration (ng, xmin, bc_type of the whole problem).  Host only: needs no
+ * device.  Returns EINVAL for a file that is not a complete PIONRAW2 header; sim == NULL here, so the text is in
+ * pion_host_sim_last_error(NULL, .). */
+int pion_host_snapshot_read_header(const char *path, pion_gpu_config *cfg, pion_host_snapshot_info *info);
+/* Restart (dataio->ReadData + sim_init::Init, sim_init.cpp:219-267): checks every header against the sim's own
+ * configuration (geometry, equations, nvar, solver, orders, gamma, dx, global extents; EINVAL with a text otherwise),
+ * takes the planes this sim owns from whichever of the files hold them -- a run written by M ranks restarts on N --,
+ * sets P and Ph, simtime, timestep, last_dt, next_optime, t_start (and finishtime, min_timestep), discards a pending
+ * time-step request, and assigns + updates the boundaries.  Inflow and fixed faces capture their state again from the
+ * on-grid neighbour, as in the reference's restart.  Wind sources (an evolving one with t_now = the file's t_sim),
+ * jets and cooling tables are set up by the caller first, as before pion_host_sim_init; the header only counts them.
+ * Never exits: a wrong magic, a missing key, truncated data, planes no file covers, files of different times all
+ * return EINVAL and a text. */
+int pion_host_sim_read_snapshot(void *sim, const char *const *paths, int npaths);
+/* SimTime of the loop: out[0..5] = simtime, last_dt, next_optime, finishtime, starttime, (double) timestep */
+int pion_host_sim_get_time(void *sim, double *out6);
+
 /* ---- slab communicators (both return a pion_host::slab_comm*).  A grid is cut along its slab axis, the last one:
  * z of a 3-D grid, y of a 2-D grid (Cartesian or cylindrical (z,R)).  periodic_z: the global problem is periodic along the slab
  * axis (rank 0 <-> world-1 exchange); physical faces of the slab axis apply on the end ranks only. */

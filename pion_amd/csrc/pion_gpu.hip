@@ -1050,6 +1050,92 @@ static int add_fixed_wind_source(Handle *h, WindSource &W, int *id)
   return 0;
 }
 
+// On-grid cells of planes [plane_lo, plane_lo + planes) of the slab axis <-> a contiguous buffer
+// [nvar][planes][rows][nx] (pion_gpu_pack_ongrid / _unpack_ongrid).  A plane of the slab axis is `rows` runs of nx
+// on-grid cells (3-D: the ny rows of an x-y plane; 2-D: one row; 1-D: the one row there is).  A pure copy, bound by
+// HBM: one lane per double, consecutive along x; a wavefront takes one stretch of up to ONGRID_SEG cells of one row,
+// so the (64-bit) index arithmetic is paid once per stretch and the loads and stores are whole lines.  No LDS.
+// blockIdx.y: the variable.  Every cell id and buffer index is 64-bit (grids of 2^29 cells and more).
+constexpr int ONGRID_SEG = 1024, ONGRID_WAVES = 4;
+struct OngridGeom {
+  long off0;     // cell id of the first on-grid cell of plane 0
+  long ps, rs;   // cell-id strides of a plane and of a row inside a plane
+  long ncell;    // stride of a variable in the state arrays
+  int nx, rows, nseg;   // nseg: stretches per row
+};
+template <bool PACK>
+__global__ void __launch_bounds__(64 * ONGRID_WAVES)
+k_pack_ongrid(double *__restrict__ A0, double *__restrict__ A1, double *__restrict__ buf, const OngridGeom q,
+              const long plane_lo, const long planes)
+{
+  const long u = (long)blockIdx.x * ONGRID_WAVES + (threadIdx.x >> 6);   // stretch: (plane, row, segment)
+  const long nunit = planes * q.rows * q.nseg;
+  if (u >= nunit) return;
+  const long row = u / q.nseg;
+  const int seg = (int)(u - row * q.nseg);
+  const long k = row / q.rows;
+  const long j = row - k * q.rows;
+  const long v = blockIdx.y;
+  const long c0 = v * q.ncell + q.off0 + (plane_lo + k) * q.ps + j * q.rs;
+  const long b0 = ((v * planes + k) * q.rows + j) * q.nx;
+  const int x1 = min(q.nx, (seg + 1) * ONGRID_SEG);
+  for (int ix = seg * ONGRID_SEG + (threadIdx.x & 63); ix < x1; ix += 64) {
+    if (PACK) buf[b0 + ix] = A0[c0 + ix];
+    else {
+      const double x = buf[b0 + ix];
+      A0[c0 + ix] = x;
+      A1[c0 + ix] = x;
+    }
+  }
+}
+
+OngridGeom ongrid_geom(const Handle *h)
+{
+  const GridDesc &g = h->g;
+  OngridGeom q;
+  q.ncell = g.ncell;
+  q.nx = g.ng[0];
+  q.nseg = (q.nx + ONGRID_SEG - 1) / ONGRID_SEG;
+  q.off0 = g.nbc[0];
+  q.ps = q.rs = 0;
+  q.rows = 1;
+  if (g.ndim == 2) {
+    q.off0 += g.sy * g.nbc[1];
+    q.ps = g.sy;
+  }
+  else if (g.ndim == 3) {
+    q.off0 += g.sy * g.nbc[1] + g.sz * g.nbc[2];
+    q.ps = g.sz;
+    q.rs = g.sy;
+    q.rows = g.ng[1];
+  }
+  return q;
+}
+// planes of the slab axis (1-D: the one row)
+inline int ongrid_planes(const Handle *h) { return h->g.ndim == 1 ? 1 : h->g.ng[h->g.ndim - 1]; }
+
+int ongrid_go(Handle *h, double *A0, double *A1, int plane_lo, int plane_hi, void *dbuf, bool pack)
+{
+  if (!dbuf || plane_lo < 0 || plane_hi > ongrid_planes(h) || plane_lo >= plane_hi) {
+    h->err = "pack / unpack_ongrid: plane range outside the grid, or no buffer";
+    return PION_GPU_EINVAL;
+  }
+  const OngridGeom q = ongrid_geom(h);
+  // the launch grid in long: one wavefront per stretch, ONGRID_WAVES per block.  (2^31 blocks are 2^33 stretches:
+  // no grid that fits a card comes near; a range that did would have to be passed in parts.)
+  const long planes = plane_hi - plane_lo;
+  const long nblk = (planes * q.rows * q.nseg + ONGRID_WAVES - 1) / ONGRID_WAVES;
+  if (nblk > (1L << 31) - 1) {
+    h->err = "pack / unpack_ongrid: plane range too large for one launch; pass it in parts";
+    return PION_GPU_EINVAL;
+  }
+  const dim3 grid((unsigned)nblk, (unsigned)h->cfg.nvar), block(64 * ONGRID_WAVES);
+  if (pack) hipLaunchKernelGGL(k_pack_ongrid<true>, grid, block, 0, h->stream, A0, A1, (double *)dbuf, q, (long)plane_lo, planes);
+  else hipLaunchKernelGGL(k_pack_ongrid<false>, grid, block, 0, h->stream, A0, A1, (double *)dbuf, q, (long)plane_lo, planes);
+  HCHECK(h, hipGetLastError());
+  return 0;
+}
+
 // device scratch of the test seams: freed on every return path
 struct DevBuf {
   double *p = nullptr;
@@ -1379,6 +1465,39 @@ int pion_gpu_download(void *handle, int which, double *P_soa)
   HCHECK(h, hipMemcpyAsync(P_soa, src, nb, hipMemcpyDeviceToHost, h->stream));
   HCHECK(h, hipStreamSynchronize(h->stream));
   return check_errword(h);
+}
+
+long pion_gpu_ongrid_count(void *handle, int planes)
+{
+  Handle *h = use(handle);
+  if (!h || planes < 0) return 0;
+  const OngridGeom q = ongrid_geom(h);
+  return (long)h->cfg.nvar * planes * q.rows * q.nx;
+}
+
+int pion_gpu_pack_ongrid(void *handle, int which, int plane_lo, int plane_hi, void *dbuf)
+{
+  Handle *h = use(handle);
+  if (!h) return PION_GPU_EINVAL;
+  // the array pion_gpu_download(which) reads
+  double *src = (which == 1 && h->ph_valid) ? h->dPh : h->dP;
+  if (int rc = order_after_unpack(h)) return rc;
+  return ongrid_go(h, src, nullptr, plane_lo, plane_hi, dbuf, true);
+}
+
+int pion_gpu_unpack_ongrid(void *handle, int plane_lo, int plane_hi, void *dbuf)
+{
+  Handle *h = use(handle);
+  if (!h) return PION_GPU_EINVAL;
+  if (int rc = order_after_unpack(h)) return rc;
+  if (int rc = ongrid_go(h, h->dP, h->dPh, plane_lo, plane_hi, dbuf, false)) return rc;
+  // what pion_gpu_upload invalidates
+  h->xghost_fresh = nullptr;
+  h->ph_valid = false;
+  state_changed(h);
+  h->dt_requested = false;
+  h->dt_mp_pending = false;
+  return 0;
 }
 
 int pion_gpu_bind_device_state(void *handle, void *dP, void *dPh)

@@ -42,6 +42,23 @@ typedef struct pion_backend {
   int (*halo_to_host_begin)(void *handle, int which, double *lo, double *hi);
   int (*halo_to_host_end)(void *handle);
   int (*halo_from_host)(void *handle, int which, const double *lo, const double *hi);
+  /* Snapshots (snapshot_io.h): the ON-GRID cells of planes [plane_lo, plane_hi) of the slab axis, all variables, as
+   * [nvar][planes][ny][nx] (pion_gpu_pack_ongrid's layout), streamed through two staging slots (0, 1) the backend owns,
+   * so that a write or a read keeps two chunks on the host whatever the grid.  All four NULL (a table initialised
+   * before they existed): the snapshot code takes the whole array through download / upload and strips / embeds the
+   * ghost cells on the host.
+   *   ongrid_count:         doubles of a chunk of `planes` planes
+   *   ongrid_to_host_begin: start copying the planes of array `which` into staging slot `slot`; returns at once
+   *   ongrid_to_host_end:   slot `slot` has arrived; *host = its buffer, valid until the slot's next _begin
+   *   ongrid_from_host:     wait until slot `slot` is free, have fill(ctx, buffer) write the planes into its host
+   *                         buffer (non-zero: give up and return it), then start copying them into P and Ph (ghost
+   *                         cells untouched); returns without waiting for the copy -- the boundary update that
+   *                         follows is ordered after it */
+  long (*ongrid_count)(void *handle, int planes);
+  int (*ongrid_to_host_begin)(void *handle, int which, int plane_lo, int plane_hi, int slot);
+  int (*ongrid_to_host_end)(void *handle, int slot, const double **host);
+  int (*ongrid_from_host)(void *handle, int plane_lo, int plane_hi, int slot, int (*fill)(void *ctx, double *host),
+                          void *ctx);
 } pion_backend;
 
 /* the product's backend: libpion_gpu.so */

@@ -3,6 +3,9 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <map>
+#include <mutex>
+
 namespace {
 
 int gpu_dt_begin(void *h)
@@ -57,10 +60,125 @@ int gpu_halo_from_host(void *h, int which, const double *lo, const double *hi)
   return pion_gpu_halo_end(h);   // the z-boundary part of the next stage waits for this point
 }
 
+// Snapshot streaming: per handle, two device staging buffers and two pinned host buffers of one chunk each,
+// allocated at the first chunk (grown if a later chunk is larger) and freed with the handle.  Everything is enqueued
+// on the handle's compute stream -- a snapshot is taken between steps, so there is nothing to overlap with on the
+// device; what overlaps is the host's file I/O on one slot with the pack + copy of the other.
+struct Staging {
+  double *dev[2] = {nullptr, nullptr}, *host[2] = {nullptr, nullptr};
+  long cap[2] = {0, 0};              // doubles
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool busy[2] = {false, false};     // an event was recorded for the slot and not waited for yet
+};
+std::mutex g_staging_mu;
+std::map<void *, Staging> g_staging;
+
+void staging_free(Staging &st)
+{
+  for (int i = 0; i < 2; i++) {
+    if (st.ev[i]) (void)hipEventDestroy(st.ev[i]);
+    if (st.dev[i]) (void)hipFree(st.dev[i]);
+    if (st.host[i]) (void)hipHostFree(st.host[i]);
+  }
+  st = Staging();
+}
+// the slot's buffers, holding at least n doubles; a slot in flight is waited for before it is touched
+int staging_slot(void *h, int slot, long n, Staging **out)
+{
+  if (slot < 0 || slot > 1 || n <= 0) return PION_GPU_EINVAL;
+  Staging *st;
+  {
+    std::lock_guard<std::mutex> lk(g_staging_mu);
+    st = &g_staging[h];   // (std::map: the address stays valid)
+  }
+  if (st->busy[slot]) {
+    if (hipEventSynchronize(st->ev[slot]) != hipSuccess) return PION_GPU_EDEVICE;
+    st->busy[slot] = false;
+  }
+  if (!st->ev[slot] && hipEventCreateWithFlags(&st->ev[slot], hipEventDisableTiming) != hipSuccess) return PION_GPU_EDEVICE;
+  if (st->cap[slot] < n) {
+    if (st->dev[slot]) (void)hipFree(st->dev[slot]);
+    if (st->host[slot]) (void)hipHostFree(st->host[slot]);
+    st->dev[slot] = st->host[slot] = nullptr;
+    st->cap[slot] = 0;
+    if (hipMalloc((void **)&st->dev[slot], (size_t)n * sizeof(double)) != hipSuccess) return PION_GPU_ENOMEM;
+    if (hipHostMalloc((void **)&st->host[slot], (size_t)n * sizeof(double), hipHostMallocDefault) != hipSuccess)
+      return PION_GPU_ENOMEM;
+    st->cap[slot] = n;
+  }
+  *out = st;
+  return 0;
+}
+hipStream_t compute_stream_of(void *h) { return (hipStream_t)pion_gpu_get_stream(h, 0); }
+
+int gpu_ongrid_to_host_begin(void *h, int which, int plane_lo, int plane_hi, int slot)
+{
+  const long n = pion_gpu_ongrid_count(h, plane_hi - plane_lo);
+  Staging *st;
+  if (int rc = staging_slot(h, slot, n, &st)) return rc;
+  if (int rc = pion_gpu_pack_ongrid(h, which, plane_lo, plane_hi, st->dev[slot])) return rc;
+  hipStream_t s = compute_stream_of(h);
+  if (hipMemcpyAsync(st->host[slot], st->dev[slot], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
+    return PION_GPU_EDEVICE;
+  if (hipEventRecord(st->ev[slot], s) != hipSuccess) return PION_GPU_EDEVICE;
+  st->busy[slot] = true;
+  return 0;
+}
+int gpu_ongrid_to_host_end(void *h, int slot, const double **host)
+{
+  if (slot < 0 || slot > 1 || !host) return PION_GPU_EINVAL;
+  Staging *st;
+  {
+    std::lock_guard<std::mutex> lk(g_staging_mu);
+    auto it = g_staging.find(h);
+    if (it == g_staging.end()) return PION_GPU_EINVAL;
+    st = &it->second;
+  }
+  if (!st->busy[slot]) return PION_GPU_EINVAL;   // no _begin for this slot
+  if (hipEventSynchronize(st->ev[slot]) != hipSuccess) return PION_GPU_EDEVICE;
+  st->busy[slot] = false;
+  *host = st->host[slot];
+  return 0;
+}
+int gpu_ongrid_from_host(void *h, int plane_lo, int plane_hi, int slot, int (*fill)(void *, double *), void *ctx)
+{
+  if (!fill) return PION_GPU_EINVAL;
+  const long n = pion_gpu_ongrid_count(h, plane_hi - plane_lo);
+  Staging *st;
+  if (int rc = staging_slot(h, slot, n, &st)) return rc;   // (waits for the slot's previous copy)
+  if (int rc = fill(ctx, st->host[slot])) return rc;
+  hipStream_t s = compute_stream_of(h);
+  if (hipMemcpyAsync(st->dev[slot], st->host[slot], (size_t)n * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
+    return PION_GPU_EDEVICE;
+  if (int rc = pion_gpu_unpack_ongrid(h, plane_lo, plane_hi, st->dev[slot])) return rc;
+  if (hipEventRecord(st->ev[slot], s) != hipSuccess) return PION_GPU_EDEVICE;
+  st->busy[slot] = true;
+  return 0;
+}
+void gpu_destroy(void *h)
+{
+  Staging st;
+  bool have = false;
+  {
+    std::lock_guard<std::mutex> lk(g_staging_mu);
+    auto it = g_staging.find(h);
+    if (it != g_staging.end()) {
+      st = it->second;
+      have = true;
+      g_staging.erase(it);
+    }
+  }
+  if (have) {
+    (void)pion_gpu_synchronize(h);
+    staging_free(st);
+  }
+  pion_gpu_destroy(h);
+}
+
 const pion_backend k_gpu = {
     "libpion_gpu.so",
     pion_gpu_create,
-    pion_gpu_destroy,
+    gpu_destroy,
     pion_gpu_last_error,
     pion_gpu_upload,
     pion_gpu_download,
@@ -75,6 +193,10 @@ const pion_backend k_gpu = {
     gpu_halo_to_host_begin,
     gpu_halo_to_host_end,
     gpu_halo_from_host,
+    pion_gpu_ongrid_count,
+    gpu_ongrid_to_host_begin,
+    gpu_ongrid_to_host_end,
+    gpu_ongrid_from_host,
 };
 
 }  // namespace

@@ -2,6 +2,7 @@
 #include "sim_control_gpu.h"
 
 #include "slab_comm.h"
+#include "snapshot_io.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -90,6 +91,7 @@ int sim_control_gpu::add_wind_source(const pion_gpu_wind_source &src, int *id, c
   const int err = rotating ? pion_gpu_add_rotating_wind_source(h_, &src, evo_vcrit, xi, id)
                            : pion_gpu_add_wind_source(h_, &src, id);
   if (err) return err;
+  n_wind_sources_++;
   // SWP.params[v]->Vinf is the parameter-file value in km/s (0 for most evolving sources: no limit)
   const double lim = 0.1 * cfg.cfl * cfg.dx / (src.vinf * 1.0e5);
   T.wind_dt_limit = (T.wind_dt_limit < 0.0) ? lim : std::min(T.wind_dt_limit, lim);
@@ -115,6 +117,11 @@ int sim_control_gpu::calculate_timestep()
   // timestep_checking_and_limiting (calc_timestep.cpp:219-262)
   if (T.dt < T.min_timestep) throw std::runtime_error("Timestep too short!");
   T.dt = std::min(T.dt, 1.3 * T.last_dt);  // TIMESTEP_LIMITING
+  // outputting every opfreq_time: land on the next output time (calc_timestep.cpp:245-249)
+  if (!T.outfile.empty() && T.op_criterion == 1) {
+    T.dt = std::min(T.dt, T.next_optime - T.simtime);
+    if (T.dt <= 0.0) throw std::runtime_error("Went past output time without outputting!");
+  }
   T.dt = std::min(T.dt, T.finishtime - T.simtime);
   if (T.dt <= 0.0) throw std::runtime_error("Negative timestep!");
   return err;
@@ -153,14 +160,95 @@ double sim_control_gpu::advance_time()
   return T.dt;
 }
 
+int sim_control_gpu::set_output(const char *base, int op_criterion, int opfreq, double opfreq_time, int checkpoint_freq)
+{
+  if (!base || !*base || (op_criterion != 0 && op_criterion != 1) || opfreq < 0
+      || (op_criterion == 1 && !(opfreq_time > 0.0)))
+    return PION_GPU_EINVAL;
+  T.outfile = base;
+  T.op_criterion = op_criterion;
+  T.opfreq = opfreq;
+  T.opfreq_time = opfreq_time;
+  T.checkpoint_freq = checkpoint_freq;
+  // (sim_init::Init sets next_optime from the start time; a restart takes it from the file)
+  T.next_optime = T.simtime + opfreq_time;
+  T.starttime = T.simtime;
+  last_output_step_ = -1;
+  return 0;
+}
+
+int sim_control_gpu::set_slab_extent(int global_planes, int plane_lo, int bc_lo, int bc_hi)
+{
+  if (cfg.ndim < 2) return PION_GPU_EINVAL;
+  const int n = cfg.ng[cfg.ndim - 1];
+  if (plane_lo < 0 || plane_lo + n > global_planes || bc_lo == PION_BC_SLAB || bc_hi == PION_BC_SLAB) return PION_GPU_EINVAL;
+  slab.set = true;
+  slab.global_planes = global_planes;
+  slab.plane_lo = plane_lo;
+  slab.bc_lo = bc_lo;
+  slab.bc_hi = bc_hi;
+  return 0;
+}
+
+std::string sim_control_gpu::snapshot_name(long id) const
+{
+  char b[64];
+  snprintf(b, sizeof b, "_%04d.%08ld.pionraw", comm_ ? comm_->rank() : 0, id);
+  return T.outfile + b;
+}
+
+// sim_init::output_data (sim_init.cpp:671-760)
+int sim_control_gpu::output_data()
+{
+  if (T.outfile.empty()) return 0;
+  // first the checkpoint, alternating between two files
+  const int checkpoint_freq = (T.checkpoint_freq > 0) ? T.checkpoint_freq : 250;
+  if (T.timestep != 0 && (T.timestep % checkpoint_freq) == 0) {
+    const long id = ((T.timestep % (2 * checkpoint_freq)) == 0) ? 99999998L : 99999999L;
+    if (int rc = write_snapshot(snapshot_name(id).c_str())) return rc;
+  }
+  // always output at the start
+  if (T.timestep == 0) {}
+  // every opfreq steps (0: only the final state)
+  else if (T.op_criterion == 0) {
+    if (T.opfreq == 0 && !T.maxtime) return 0;
+    if (!T.maxtime && (T.timestep % T.opfreq) != 0) return 0;
+  }
+  // every opfreq_time time units: at an output time advance the 'next' counter and go on
+  else if (T.op_criterion == 1) {
+    if (!equalD(T.simtime, T.next_optime) && !T.maxtime) return 0;
+    T.next_optime += T.opfreq_time;
+  }
+  else {
+    io_error_ = "op_criterion must be 0 or 1";
+    return PION_GPU_EINVAL;
+  }
+  // (the reference writes a final state that is also a regular output twice, from Time_Int and from Finalise; once here)
+  if (last_output_step_ == T.timestep) return 0;
+  if (int rc = write_snapshot(snapshot_name(T.timestep).c_str())) return rc;
+  last_output_step_ = T.timestep;
+  return 0;
+}
+
 int sim_control_gpu::Time_Int(int nsteps)
 {
   int n = 0;
+  const bool output = !T.outfile.empty();
+  T.maxtime = false;
+  if (output && output_data()) throw std::runtime_error("output_data: " + io_error_);
   while (T.simtime < T.finishtime && (nsteps < 0 || n < nsteps)) {
     int err = calculate_timestep();
     if (err) throw std::runtime_error("calculate_timestep: " + last_error());
     advance_time();
     n++;
+    if (output) {
+      if (output_data()) throw std::runtime_error("output_data: " + io_error_);
+      // the end of the run: the final state (the reference: Finalise -> output_data with maxtime set)
+      if (T.simtime >= T.finishtime) {
+        T.maxtime = true;
+        if (output_data()) throw std::runtime_error("output_data: " + io_error_);
+      }
+    }
   }
   if (finish_halo()) throw std::runtime_error("finish_halo: " + last_error());
   return n;
@@ -249,6 +337,72 @@ int pion_host_sim_last_error(void *s, char *buf, int len)
     if (!h.empty()) m += (m.empty() ? "" : " | ") + h;
   }
   snprintf(buf, (size_t)len, "%s", m.c_str());
+  return 0;
+}
+static int io_result(pion_host::sim_control_gpu *c, int rc)
+{
+  if (rc) g_last_exception = c->io_error();
+  return rc;
+}
+int pion_host_sim_set_output(void *s, const char *base, int op_criterion, int opfreq, double opfreq_time, int checkpoint_freq)
+{
+  if (!s) return PION_GPU_EINVAL;
+  return static_cast<pion_host::sim_control_gpu *>(s)->set_output(base, op_criterion, opfreq, opfreq_time, checkpoint_freq);
+}
+int pion_host_sim_set_slab_extent(void *s, int global_planes, int plane_lo, int bc_lo, int bc_hi)
+{
+  if (!s) return PION_GPU_EINVAL;
+  return static_cast<pion_host::sim_control_gpu *>(s)->set_slab_extent(global_planes, plane_lo, bc_lo, bc_hi);
+}
+int pion_host_sim_write_snapshot(void *s, const char *path)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  try {
+    return io_result(c, c->write_snapshot(path));
+  }
+  catch (const std::exception &e) {
+    g_last_exception = e.what();
+    return PION_GPU_EINVAL;
+  }
+}
+int pion_host_sim_read_snapshot(void *s, const char *const *paths, int npaths)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  try {
+    return io_result(c, c->read_snapshot(paths, npaths));
+  }
+  catch (const std::exception &e) {
+    g_last_exception = e.what();
+    return PION_GPU_EINVAL;
+  }
+}
+int pion_host_snapshot_read_header(const char *path, pion_gpu_config *cfg, pion_host_snapshot_info *info)
+{
+  try {
+    pion_host::snapshot_header hd;
+    std::string err;
+    const int rc = pion_host::snapshot_read_header(path, hd, err);
+    if (rc) {
+      g_last_exception = err;
+      return rc;
+    }
+    if (cfg) *cfg = hd.cfg;
+    if (info) *info = hd.info;
+    return 0;
+  }
+  catch (const std::exception &e) {
+    g_last_exception = e.what();
+    return PION_GPU_EINVAL;
+  }
+}
+int pion_host_sim_get_time(void *s, double *out)
+{
+  if (!s || !out) return PION_GPU_EINVAL;
+  const pion_host::SimTime &T = static_cast<pion_host::sim_control_gpu *>(s)->T;
+  out[0] = T.simtime, out[1] = T.last_dt, out[2] = T.next_optime, out[3] = T.finishtime, out[4] = T.starttime;
+  out[5] = (double)T.timestep;
   return 0;
 }
 int pion_host_sim_download(void *s, int which, double *P)

@@ -6,6 +6,8 @@
 //                                     source/sim_control/calc_timestep.cpp:68-153, 219-262
 //   time_integrator::advance_time, first_order_update, second_order_update
 //                                     source/sim_control/time_integrator.cpp:72-250
+//   sim_init::output_data             source/sim_control/sim_init.cpp:671-760   (output times, cadence, checkpoints;
+//                                     the file it writes and the restart that reads it: snapshot_io.h)
 // so that a maintainer can swap these three functions in a PION build and
 // sim_control drives the GPU path unchanged.  Errors follow the reference's convention:
 // int error counts are returned and accumulated; unrecoverable conditions throw (the reference
@@ -28,6 +30,23 @@ struct SimTime {
   int timestep = 0;
   double first_step_dt_limit = -1.0;  // wind / jet limit of calc_dynamics_dt (calc_timestep.cpp:313-323); <0: none
   double wind_dt_limit = -1.0;        // the same for the sources of add_wind_source, min over them; <0: none
+  // output (SimParams::op_criterion, opfreq, opfreq_time, next_optime, checkpoint_freq, starttime, maxtime,
+  // outFileBase; sim_params.h:200-285).  outfile empty: no output is configured -- nothing is written and
+  // calculate_timestep has no output-time clip, whatever the other fields hold
+  int op_criterion = 0;        // 0: every opfreq steps (0: the final state only); 1: every opfreq_time time units
+  int opfreq = 0;
+  double opfreq_time = 0.0, next_optime = 0.0;
+  int checkpoint_freq = 0;     // steps between checkpoints; <= 0: 250
+  double starttime = 0.0;
+  bool maxtime = false;        // the run has reached finishtime (set by Time_Int; check_eosim, sim_control.cpp:289-318)
+  std::string outfile;         // outFileBase
+};
+
+// where this sim's grid sits in the global problem along the slab axis (the last axis), and the global problem's two
+// faces of that axis (PION_BC_*): what a snapshot header describes (set_slab_extent)
+struct SlabExtent {
+  bool set = false;
+  int global_planes = 0, plane_lo = 0, bc_lo = 0, bc_hi = 0;
 };
 
 class sim_control_gpu {
@@ -45,8 +64,28 @@ class sim_control_gpu {
   double advance_time();
   int first_order_update(double dt, int ooa);
   int second_order_update(double dt, int ooa);
-  // sim_control::Time_Int without I/O; nsteps<0: until finishtime
+  // sim_control::Time_Int (sim_control.cpp:202-281); nsteps<0: until finishtime.  With output configured
+  // (set_output) it calls output_data() before the loop and after every advance_time, and writes the final state
+  // once when simtime reaches finishtime (the reference does that from Finalise with maxtime set)
   int Time_Int(int nsteps);
+
+  // output times and cadence: SimPM.op_criterion / opfreq / opfreq_time / checkpoint_freq / outFileBase; with
+  // op_criterion 1, next_optime = simtime + opfreq_time.  EINVAL: op_criterion outside {0, 1}, opfreq < 0,
+  // opfreq_time <= 0 with criterion 1, a null or empty base
+  int set_output(const char *outfile_base, int op_criterion, int opfreq, double opfreq_time, int checkpoint_freq);
+  // a rank of a slab run: the global number of planes of the slab axis, the first one this sim owns, and the global
+  // problem's boundary types on the two faces of that axis.  Default: this sim is the whole domain
+  int set_slab_extent(int global_planes, int plane_lo, int bc_lo, int bc_hi);
+  // sim_init::output_data (sim_init.cpp:671-760): checkpoint, then the regular output if this step is due
+  int output_data();
+  // <base>_<rank, 4 digits>.<id, 8 digits>.pionraw
+  std::string snapshot_name(long id) const;
+  // the PIONRAW2 file (snapshot_io.h) of this sim's on-grid cells; completes a halo exchange in flight first
+  int write_snapshot(const char *path);
+  // restart from the files that hold this sim's planes (written by any number of ranks); sets P, Ph, simtime,
+  // timestep, last_dt, next_optime, starttime, finishtime and min_timestep, then assigns and updates the boundaries as
+  // Init does.  Wind sources, jets and cooling tables are set up by the caller first, as before Init.
+  int read_snapshot(const char *const *paths, int npaths);
 
   // z-slab of a larger domain: exchange the z ghost planes after every boundary update (under the
   // interior part of the next stage) and min-reduce the time step over the ranks
@@ -66,15 +105,20 @@ class sim_control_gpu {
   const pion_backend *backend() const { return be_; }
   void *handle() { return h_; }
   std::string last_error() const;
+  const std::string &io_error() const { return io_error_; }   // text of the last output / snapshot failure
 
   SimTime T;
   pion_gpu_config cfg;
+  SlabExtent slab;
 
  private:
   const pion_backend *be_;
   void *h_;
   slab_comm *comm_ = nullptr;
   bool dt_requested_ = false;
+  int n_wind_sources_ = 0;
+  long last_output_step_ = -1;   // step whose regular output has been written
+  std::string io_error_;
 };
 
 }  // namespace pion_host

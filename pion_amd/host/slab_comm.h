@@ -33,6 +33,9 @@ class slab_comm {
   // a new state was uploaded (sim_control_gpu::Init): complete an exchange in flight, forget a pending request
   virtual int reset() = 0;
   virtual const std::string &last_error() const = 0;
+  // this process's place among the ranks (file names and headers of snapshots)
+  virtual int rank() const { return 0; }
+  virtual int world() const { return 1; }
 };
 
 }  // namespace pion_host

@@ -55,6 +55,8 @@ class slab_comm_rccl : public slab_comm {
 
   bool has_neighbours() const { return up_ >= 0 || down_ >= 0; }
   const std::string &last_error() const override { return err_; }
+  int rank() const override { return rank_; }
+  int world() const override { return world_; }
 
  private:
   int rank_, world_, device_, up_, down_;

@@ -32,6 +32,8 @@ class slab_comm_shm : public slab_comm {
   int allreduce_min(double *t_dyn, double *t_mp) override;
   int reset() override;
   const std::string &last_error() const override { return err_; }
+  int rank() const override { return rank_; }
+  int world() const override { return world_; }
 
  private:
   struct Box;   // one mailbox (header + planes) inside the segment

@@ -1,0 +1,588 @@
+// snapshot_io.cpp -- see snapshot_io.h
+#include "snapshot_io.h"
+
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cerrno>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <sstream>
+
+#include "sim_control_gpu.h"
+#include "slab_comm.h"
+
+namespace pion_host {
+
+namespace {
+
+const char MAGIC[9] = "PIONRAW2";
+const long HEADER_MAX = 1 << 16;        // a header is a few KiB
+const long CHUNK_BYTES = 64L << 20;     // per staging buffer
+
+// constants.h:150-152
+const double SMALLVALUE = 1.0e-12, TINYVALUE = 1.0e-100;
+
+// boundary types <-> the reference's strings (SimPM.BC_XN ..., setup_fixed_grid.cpp:912-944); "NONE" on unused axes
+// (get_sim_info.cpp:386-395)
+struct BcName { int type; const char *name; };
+const BcName BC_TABLE[] = {{0, "NONE"}, {PION_BC_PERIODIC, "periodic"}, {PION_BC_OUTFLOW, "outflow"},
+                           {PION_BC_INFLOW, "inflow"}, {PION_BC_REFLECTING, "reflecting"}, {PION_BC_FIXED, "fixed"},
+                           {PION_BC_ONEWAY_OUT, "one-way-outflow"}, {PION_BC_DMACH, "DMR"},
+                           {PION_BC_AXISYMMETRIC, "axisymmetric"}, {PION_BC_JETREFLECT, "jetreflect"}};
+const char *bc_name(int t)
+{
+  for (const BcName &b : BC_TABLE)
+    if (b.type == t) return b.name;
+  return nullptr;
+}
+int bc_type(const std::string &s)
+{
+  for (const BcName &b : BC_TABLE)
+    if (s == b.name) return b.type;
+  return -1;
+}
+const char *const BC_KEYS[6] = {"BC_XN", "BC_XP", "BC_YN", "BC_YP", "BC_ZN", "BC_ZP"};
+
+std::string fmt_d(double x)
+{
+  char b[64];
+  snprintf(b, sizeof b, "%.17g", x);
+  return b;
+}
+
+// geometry of the on-grid data of one sim / one file
+struct Shape {
+  int sa;            // slab axis (-1: 1-D, the one row is the one plane)
+  long nx, rows;     // cells per row, rows per plane
+  long plane() const { return nx * rows; }
+};
+Shape shape_of(const pion_gpu_config &c)
+{
+  Shape s;
+  s.sa = (c.ndim == 1) ? -1 : c.ndim - 1;
+  s.nx = c.ng[0];
+  s.rows = (c.ndim == 3) ? c.ng[1] : 1;
+  return s;
+}
+
+int full_pwrite(int fd, const void *p, size_t n, off_t off)
+{
+  const char *c = (const char *)p;
+  while (n > 0) {
+    const ssize_t w = pwrite(fd, c, n, off);
+    if (w < 0 && errno == EINTR) continue;
+    if (w <= 0) return -1;
+    c += w, off += w, n -= (size_t)w;
+  }
+  return 0;
+}
+int full_pread(int fd, void *p, size_t n, off_t off)
+{
+  char *c = (char *)p;
+  while (n > 0) {
+    const ssize_t r = pread(fd, c, n, off);
+    if (r < 0 && errno == EINTR) continue;
+    if (r <= 0) return -1;
+    c += r, off += r, n -= (size_t)r;
+  }
+  return 0;
+}
+
+struct Fd {
+  int fd = -1;
+  ~Fd()
+  {
+    if (fd >= 0) close(fd);
+  }
+};
+
+// planes per chunk: the largest number that fits CHUNK_BYTES, at least one; PION_SNAPSHOT_CHUNK_PLANES forces it
+long chunk_planes(long doubles_per_plane_all_vars, long planes)
+{
+  long c = CHUNK_BYTES / (long)sizeof(double) / std::max(1L, doubles_per_plane_all_vars);
+  if (const char *e = getenv("PION_SNAPSHOT_CHUNK_PLANES")) {
+    const long f = atol(e);
+    if (f > 0) c = f;
+  }
+  return std::max(1L, std::min(c, planes));
+}
+
+bool get(const snapshot_header &hd, const char *key, std::string &v, std::string &err)
+{
+  auto it = hd.kv.find(key);
+  if (it == hd.kv.end()) {
+    err = std::string("snapshot header: key '") + key + "' is missing";
+    return false;
+  }
+  v = it->second;
+  return true;
+}
+bool get_doubles(const snapshot_header &hd, const char *key, double *out, int n, std::string &err)
+{
+  std::string v;
+  if (!get(hd, key, v, err)) return false;
+  const char *p = v.c_str();
+  for (int i = 0; i < n; i++) {
+    char *e = nullptr;
+    out[i] = strtod(p, &e);
+    if (e == p) {
+      err = std::string("snapshot header: key '") + key + "' holds too few numbers";
+      return false;
+    }
+    p = e;
+  }
+  return true;
+}
+bool get_longs(const snapshot_header &hd, const char *key, long *out, int n, std::string &err)
+{
+  std::string v;
+  if (!get(hd, key, v, err)) return false;
+  const char *p = v.c_str();
+  for (int i = 0; i < n; i++) {
+    char *e = nullptr;
+    out[i] = strtol(p, &e, 10);
+    if (e == p) {
+      err = std::string("snapshot header: key '") + key + "' holds too few numbers";
+      return false;
+    }
+    p = e;
+  }
+  return true;
+}
+bool get_int(const snapshot_header &hd, const char *key, int &out, std::string &err)
+{
+  long v;
+  if (!get_longs(hd, key, &v, 1, err)) return false;
+  out = (int)v;
+  return true;
+}
+
+}  // namespace
+
+bool equalD(const double a, const double b)
+{
+  if (a == b) return true;
+  if (fabs(a) + fabs(b) < TINYVALUE) return true;
+  return (fabs(a - b) / (fabs(a) + fabs(b) + TINYVALUE)) < SMALLVALUE;
+}
+
+const std::vector<std::string> &snapshot_header_keys()
+{
+  static const std::vector<std::string> k = {
+      "gridndim", "NGrid", "Ncell", "Xmin", "Xmax", "eqn_type", "eqn_nvar", "num_tracer", "solver", "coord_sys",
+      "Space_OOA", "Time_OOA", "Gamma", "CFL", "art_visc", "eta_visc", "Ref_Vector", "EP_cooling",
+      "EP_MP_timestep_limit", "EP_Min_Temperature", "EP_Max_Temperature", "t_start", "t_finish", "t_step", "t_sim",
+      "min_timestep", "last_dt", "op_freq", "opfreq_time", "op_criterion", "outfile", "BC_XN", "BC_XP", "BC_YN",
+      "BC_YP", "BC_ZN", "BC_ZP", "BC_Ninternal", "JetSim", "WIND_Nsources", "pion_nbc", "pion_strict_fp",
+      "pion_bc_dmach2", "pion_dx", "pion_next_optime", "pion_rank", "pion_world", "pion_slab_lo", "pion_slab_n",
+      "pion_data_offset"};
+  return k;
+}
+
+int snapshot_read_header(const char *path, snapshot_header &hd, std::string &err)
+{
+  hd = snapshot_header();
+  if (!path) {
+    err = "snapshot: no path";
+    return PION_GPU_EINVAL;
+  }
+  Fd f;
+  f.fd = open(path, O_RDONLY);
+  if (f.fd < 0) {
+    err = std::string("snapshot: cannot open ") + path + ": " + strerror(errno);
+    return PION_GPU_EINVAL;
+  }
+  std::string buf((size_t)HEADER_MAX, '\0');
+  ssize_t n = pread(f.fd, &buf[0], (size_t)HEADER_MAX, 0);
+  if (n < 8 || memcmp(buf.data(), MAGIC, 8) != 0) {
+    err = std::string("snapshot: ") + path + " is not a PIONRAW2 file (wrong magic)";
+    return PION_GPU_EINVAL;
+  }
+  buf.resize((size_t)n);
+  // "name value" lines up to and including pion_data_offset
+  size_t pos = 8;
+  bool complete = false;
+  while (pos < buf.size() && !complete) {
+    size_t eol = buf.find('\n', pos);
+    if (eol == std::string::npos) break;
+    const std::string line = buf.substr(pos, eol - pos);
+    pos = eol + 1;
+    if (line.empty()) continue;
+    const size_t sp = line.find(' ');
+    const std::string key = line.substr(0, sp);
+    const std::string val = (sp == std::string::npos) ? "" : line.substr(sp + 1);
+    hd.kv[key] = val;
+    complete = (key == "pion_data_offset");
+  }
+  if (!complete) {
+    err = std::string("snapshot header of ") + path + ": key 'pion_data_offset' is missing (header incomplete)";
+    return PION_GPU_EINVAL;
+  }
+  for (const std::string &k : snapshot_header_keys())
+    if (!hd.kv.count(k)) {
+      err = std::string("snapshot header of ") + path + ": key '" + k + "' is missing";
+      return PION_GPU_EINVAL;
+    }
+  pion_gpu_config &c = hd.cfg;
+  pion_host_snapshot_info &I = hd.info;
+  memset(&c, 0, sizeof c);
+  memset(&I, 0, sizeof I);
+  long ng[3], l;
+  double xmax[3];
+  bool ok = get_int(hd, "gridndim", c.ndim, err) && get_longs(hd, "NGrid", ng, 3, err)
+            && get_doubles(hd, "Xmin", c.xmin, 3, err) && get_doubles(hd, "Xmax", xmax, 3, err)
+            && get_int(hd, "eqn_type", c.eqntype, err) && get_int(hd, "eqn_nvar", c.nvar, err)
+            && get_int(hd, "num_tracer", c.ntracer, err) && get_int(hd, "solver", c.solver, err)
+            && get_int(hd, "coord_sys", c.coord_sys, err) && get_int(hd, "Space_OOA", c.sp_ooa, err)
+            && get_int(hd, "Time_OOA", c.tm_ooa, err) && get_doubles(hd, "Gamma", &c.gamma, 1, err)
+            && get_doubles(hd, "CFL", &c.cfl, 1, err) && get_int(hd, "art_visc", c.artvisc, err)
+            && get_doubles(hd, "eta_visc", &c.etav, 1, err) && get_int(hd, "EP_cooling", c.cooling, err)
+            && get_int(hd, "EP_MP_timestep_limit", c.mp_timestep_limit, err)
+            && get_doubles(hd, "EP_Min_Temperature", &c.min_temp, 1, err)
+            && get_doubles(hd, "EP_Max_Temperature", &c.max_temp, 1, err) && get_int(hd, "pion_nbc", c.nbc, err)
+            && get_int(hd, "pion_strict_fp", c.strict_fp, err) && get_int(hd, "pion_bc_dmach2", c.bc_dmach2, err)
+            && get_doubles(hd, "pion_dx", &c.dx, 1, err);
+  if (ok && (c.ndim < 1 || c.ndim > 3 || c.nvar < 1 || c.nvar > PION_MAX_NVAR)) {
+    err = std::string("snapshot header of ") + path + ": gridndim / eqn_nvar out of range";
+    return PION_GPU_EINVAL;
+  }
+  ok = ok && get_doubles(hd, "Ref_Vector", c.refvec, c.nvar, err);
+  for (int i = 0; ok && i < 3; i++) c.ng[i] = (int)ng[i];
+  for (int fc = 0; ok && fc < 6; fc++) {
+    std::string v;
+    ok = get(hd, BC_KEYS[fc], v, err);
+    if (ok && (c.bc_type[fc] = bc_type(v)) < 0) {
+      err = std::string("snapshot header: unknown boundary '") + v + "' for " + BC_KEYS[fc];
+      ok = false;
+    }
+  }
+  ok = ok && get_doubles(hd, "t_start", &I.t_start, 1, err) && get_doubles(hd, "t_finish", &I.t_finish, 1, err)
+       && get_int(hd, "t_step", I.t_step, err) && get_doubles(hd, "t_sim", &I.t_sim, 1, err)
+       && get_doubles(hd, "min_timestep", &I.min_timestep, 1, err) && get_doubles(hd, "last_dt", &I.last_dt, 1, err)
+       && get_int(hd, "op_freq", I.op_freq, err) && get_doubles(hd, "opfreq_time", &I.opfreq_time, 1, err)
+       && get_int(hd, "op_criterion", I.op_criterion, err)
+       && get_doubles(hd, "pion_next_optime", &I.next_optime, 1, err) && get_int(hd, "pion_rank", I.rank, err)
+       && get_int(hd, "pion_world", I.world, err) && get_int(hd, "pion_slab_lo", I.slab_lo, err)
+       && get_int(hd, "pion_slab_n", I.slab_n, err) && get_longs(hd, "pion_data_offset", &l, 1, err);
+  if (!ok) {
+    err += std::string(" (") + path + ")";
+    return PION_GPU_EINVAL;
+  }
+  I.data_offset = l;
+  snprintf(I.outfile, sizeof I.outfile, "%s", hd.kv["outfile"].c_str());
+  const int np = (c.ndim == 1) ? 1 : c.ng[c.ndim - 1];
+  bool sane = I.slab_lo >= 0 && I.slab_n >= 1 && I.slab_lo + I.slab_n <= np && I.data_offset >= (long)pos;
+  for (int a = 0; a < 3; a++) sane = sane && c.ng[a] >= 1;
+  if (!sane) {
+    err = std::string("snapshot header of ") + path + ": plane range, NGrid or data offset out of range";
+    return PION_GPU_EINVAL;
+  }
+  return 0;
+}
+
+// ---- the sim's view of the global problem ------------------------------------------------------
+namespace {
+struct Global {
+  int ng[3], bc[6];
+  double xmin[3], xmax[3];
+  int slab_lo, slab_n;   // this sim's planes
+};
+int global_view(const sim_control_gpu &sim, Global &G, std::string &err)
+{
+  const pion_gpu_config &c = sim.cfg;
+  const Shape s = shape_of(c);
+  for (int a = 0; a < 3; a++) G.ng[a] = c.ng[a], G.xmin[a] = c.xmin[a];
+  for (int f = 0; f < 6; f++) G.bc[f] = c.bc_type[f];
+  G.slab_lo = 0;
+  G.slab_n = (s.sa < 0) ? 1 : c.ng[s.sa];
+  if (sim.slab.set && s.sa >= 0) {
+    G.ng[s.sa] = sim.slab.global_planes;
+    G.xmin[s.sa] = c.xmin[s.sa] - sim.slab.plane_lo * c.dx;
+    G.bc[2 * s.sa] = sim.slab.bc_lo;
+    G.bc[2 * s.sa + 1] = sim.slab.bc_hi;
+    G.slab_lo = sim.slab.plane_lo;
+  }
+  for (int f = 0; f < 6; f++)
+    if (G.bc[f] == PION_BC_SLAB || !bc_name(G.bc[f])) {
+      err = "snapshot: this sim is a slab of a larger problem (or has a boundary type without a name): say where it "
+            "sits with set_slab_extent first";
+      return PION_GPU_EINVAL;
+    }
+  for (int a = 0; a < 3; a++) G.xmax[a] = (a < c.ndim) ? G.xmin[a] + G.ng[a] * c.dx : G.xmin[a];
+  return 0;
+}
+}  // namespace
+
+int sim_control_gpu::write_snapshot(const char *path)
+{
+  io_error_.clear();
+  if (!path || !*path) {
+    io_error_ = "write_snapshot: no path";
+    return PION_GPU_EINVAL;
+  }
+  Global G;
+  if (int rc = global_view(*this, G, io_error_)) return rc;
+  if (int rc = finish_halo()) {
+    io_error_ = "write_snapshot: finish_halo failed";
+    return rc;
+  }
+  const Shape s = shape_of(cfg);
+  const long nloc = G.slab_n, plane = s.plane();
+
+  std::ostringstream h;
+  h << "gridndim " << cfg.ndim << "\n";
+  h << "NGrid " << G.ng[0] << " " << G.ng[1] << " " << G.ng[2] << "\n";
+  h << "Ncell " << (long)G.ng[0] * G.ng[1] * G.ng[2] << "\n";
+  h << "Xmin " << fmt_d(G.xmin[0]) << " " << fmt_d(G.xmin[1]) << " " << fmt_d(G.xmin[2]) << "\n";
+  h << "Xmax " << fmt_d(G.xmax[0]) << " " << fmt_d(G.xmax[1]) << " " << fmt_d(G.xmax[2]) << "\n";
+  h << "eqn_type " << cfg.eqntype << "\neqn_nvar " << cfg.nvar << "\nnum_tracer " << cfg.ntracer << "\n";
+  h << "solver " << cfg.solver << "\ncoord_sys " << cfg.coord_sys << "\n";
+  h << "Space_OOA " << cfg.sp_ooa << "\nTime_OOA " << cfg.tm_ooa << "\n";
+  h << "Gamma " << fmt_d(cfg.gamma) << "\nCFL " << fmt_d(cfg.cfl) << "\n";
+  h << "art_visc " << cfg.artvisc << "\neta_visc " << fmt_d(cfg.etav) << "\n";
+  h << "Ref_Vector";
+  for (int v = 0; v < cfg.nvar; v++) h << " " << fmt_d(cfg.refvec[v]);
+  h << "\n";
+  h << "EP_cooling " << cfg.cooling << "\nEP_MP_timestep_limit " << cfg.mp_timestep_limit << "\n";
+  h << "EP_Min_Temperature " << fmt_d(cfg.min_temp) << "\nEP_Max_Temperature " << fmt_d(cfg.max_temp) << "\n";
+  h << "t_start " << fmt_d(T.starttime) << "\nt_finish " << fmt_d(T.finishtime) << "\n";
+  h << "t_step " << T.timestep << "\nt_sim " << fmt_d(T.simtime) << "\n";
+  h << "min_timestep " << fmt_d(T.min_timestep) << "\nlast_dt " << fmt_d(T.last_dt) << "\n";
+  h << "op_freq " << T.opfreq << "\nopfreq_time " << fmt_d(T.opfreq_time) << "\n";
+  h << "op_criterion " << T.op_criterion << "\n";
+  h << "outfile " << (T.outfile.empty() ? "NONE" : T.outfile) << "\n";
+  for (int f = 0; f < 6; f++) h << BC_KEYS[f] << " " << bc_name(G.bc[f]) << "\n";
+  // internal boundaries and sources are set up by the caller before a restart: the header only counts them
+  h << "BC_Ninternal " << (cfg.bc_dmach2 ? 1 : 0) + (n_wind_sources_ > 0 ? 1 : 0) << "\n";
+  h << "JetSim 0\n";
+  h << "WIND_Nsources " << n_wind_sources_ << "\n";
+  h << "pion_nbc " << cfg.nbc << "\npion_strict_fp " << cfg.strict_fp << "\npion_bc_dmach2 " << cfg.bc_dmach2 << "\n";
+  h << "pion_dx " << fmt_d(cfg.dx) << "\n";
+  h << "pion_next_optime " << fmt_d(T.next_optime) << "\n";
+  h << "pion_rank " << (comm_ ? comm_->rank() : 0) << "\npion_world " << (comm_ ? comm_->world() : 1) << "\n";
+  h << "pion_slab_lo " << G.slab_lo << "\npion_slab_n " << nloc << "\n";
+  std::string head = std::string(MAGIC, 8) + h.str();
+  // the data start at a multiple of 4096 bytes
+  long off = ((long)head.size() + 64 + 4095) / 4096 * 4096;
+  head += "pion_data_offset " + std::to_string(off) + "\n";
+  head.resize((size_t)off, '\n');
+
+  // written under a temporary name and renamed: a checkpoint that replaces an older one is whole or absent
+  const std::string tmp = std::string(path) + ".part";
+  Fd f;
+  f.fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  if (f.fd < 0) {
+    io_error_ = "write_snapshot: cannot create " + tmp + ": " + strerror(errno);
+    return PION_GPU_EINVAL;
+  }
+  int rc = 0;
+  if (full_pwrite(f.fd, head.data(), head.size(), 0)) rc = PION_GPU_EINVAL;
+  const size_t run = (size_t)nloc * plane;   // doubles of one variable in the file
+  if (!rc && be_->ongrid_to_host_begin && be_->ongrid_to_host_end && be_->ongrid_count) {
+    const long cp = chunk_planes(be_->ongrid_count(h_, 1), nloc);
+    const long nchunk = (nloc + cp - 1) / cp;
+    rc = be_->ongrid_to_host_begin(h_, 0, 0, (int)std::min(cp, nloc), 0);
+    for (long i = 0; i < nchunk && !rc; i++) {
+      const long a = i * cp, b = std::min(nloc, a + cp);
+      if (i + 1 < nchunk) rc = be_->ongrid_to_host_begin(h_, 0, (int)b, (int)std::min(nloc, b + cp), (int)((i + 1) & 1));
+      const double *src = nullptr;
+      if (!rc) rc = be_->ongrid_to_host_end(h_, (int)(i & 1), &src);
+      if (rc) {
+        io_error_ = "write_snapshot: staging the planes failed: " + last_error();
+        break;
+      }
+      const size_t n = (size_t)(b - a) * plane;
+      for (int v = 0; v < cfg.nvar && !rc; v++)
+        if (full_pwrite(f.fd, src + (size_t)v * n, n * sizeof(double), off + (off_t)(((size_t)v * run + (size_t)a * plane) * sizeof(double))))
+          rc = PION_GPU_EINVAL;
+    }
+    if (rc && io_error_.empty()) io_error_ = "write_snapshot: staging the planes failed: " + last_error();
+  }
+  else if (!rc) {
+    // no streaming entries: the whole array with its ghosts, stripped here
+    const long nb = cfg.nbc, nxa = cfg.ng[0] + 2 * nb, nya = (cfg.ndim >= 2) ? cfg.ng[1] + 2 * nb : 1,
+               nza = (cfg.ndim == 3) ? cfg.ng[2] + 2 * nb : 1;
+    const size_t ncell = (size_t)nxa * nya * nza;
+    std::vector<double> A((size_t)cfg.nvar * ncell), R(run);
+    rc = be_->download(h_, 0, A.data());
+    if (rc) io_error_ = "write_snapshot: download failed: " + last_error();
+    for (int v = 0; v < cfg.nvar && !rc; v++) {
+      size_t o = 0;
+      for (long k = 0; k < (cfg.ndim == 3 ? cfg.ng[2] : 1); k++)
+        for (long j = 0; j < (cfg.ndim >= 2 ? cfg.ng[1] : 1); j++) {
+          const size_t c0 = (size_t)v * ncell + nb + (size_t)nxa * ((cfg.ndim >= 2 ? j + nb : 0) + (size_t)nya * (cfg.ndim == 3 ? k + nb : 0));
+          memcpy(&R[o], &A[c0], (size_t)cfg.ng[0] * sizeof(double));
+          o += cfg.ng[0];
+        }
+      if (full_pwrite(f.fd, R.data(), run * sizeof(double), off + (off_t)((size_t)v * run * sizeof(double)))) rc = PION_GPU_EINVAL;
+    }
+  }
+  if (rc && io_error_.empty()) io_error_ = "write_snapshot: writing " + tmp + " failed: " + strerror(errno);
+  close(f.fd);
+  f.fd = -1;
+  if (!rc && rename(tmp.c_str(), path) != 0) {
+    io_error_ = std::string("write_snapshot: cannot rename to ") + path + ": " + strerror(errno);
+    rc = PION_GPU_EINVAL;
+  }
+  if (rc) unlink(tmp.c_str());
+  return rc;
+}
+
+namespace {
+struct FillCtx {
+  int fd;
+  off_t off;          // data offset of the file
+  size_t frun;        // doubles of one variable in the file
+  size_t first;       // first double of the chunk inside a variable's run
+  size_t n;           // doubles of the chunk per variable
+  int nvar;
+};
+int fill_chunk(void *p, double *dst)
+{
+  const FillCtx *c = (const FillCtx *)p;
+  for (int v = 0; v < c->nvar; v++)
+    if (full_pread(c->fd, dst + (size_t)v * c->n, c->n * sizeof(double),
+                   c->off + (off_t)(((size_t)v * c->frun + c->first) * sizeof(double))))
+      return PION_GPU_EINVAL;
+  return 0;
+}
+}  // namespace
+
+int sim_control_gpu::read_snapshot(const char *const *paths, int npaths)
+{
+  io_error_.clear();
+  if (!paths || npaths < 1) {
+    io_error_ = "read_snapshot: no files";
+    return PION_GPU_EINVAL;
+  }
+  Global G;
+  if (int rc = global_view(*this, G, io_error_)) return rc;
+  const Shape s = shape_of(cfg);
+  const long nloc = G.slab_n, plane = s.plane();
+
+  // every header: the same problem as this sim's, and the same moment as the first file's
+  std::vector<snapshot_header> H((size_t)npaths);
+  for (int i = 0; i < npaths; i++) {
+    if (int rc = snapshot_read_header(paths[i], H[i], io_error_)) return rc;
+    const pion_gpu_config &c = H[i].cfg;
+    const char *bad = nullptr;
+    if (c.ndim != cfg.ndim || c.coord_sys != cfg.coord_sys) bad = "gridndim / coord_sys";
+    else if (c.eqntype != cfg.eqntype || c.nvar != cfg.nvar || c.ntracer != cfg.ntracer) bad = "eqn_type / eqn_nvar / num_tracer";
+    else if (c.solver != cfg.solver) bad = "solver";
+    else if (c.sp_ooa != cfg.sp_ooa || c.tm_ooa != cfg.tm_ooa) bad = "Space_OOA / Time_OOA";
+    else if (c.gamma != cfg.gamma) bad = "Gamma";
+    else if (c.dx != cfg.dx) bad = "pion_dx";
+    else if (c.ng[0] != G.ng[0] || c.ng[1] != G.ng[1] || c.ng[2] != G.ng[2]) bad = "NGrid";
+    // (a slab's own xmin is the global one plus plane_lo * dx, rounded: compare to a small fraction of a cell)
+    for (int a = 0; a < cfg.ndim && !bad; a++)
+      if (fabs(c.xmin[a] - G.xmin[a]) > 1.0e-9 * cfg.dx) bad = "Xmin";
+    if (bad) {
+      io_error_ = std::string("read_snapshot: ") + paths[i] + " does not match this sim's configuration: " + bad;
+      return PION_GPU_EINVAL;
+    }
+    const pion_host_snapshot_info &a = H[0].info, &b = H[i].info;
+    if (a.t_sim != b.t_sim || a.t_step != b.t_step || a.last_dt != b.last_dt || a.next_optime != b.next_optime
+        || a.t_start != b.t_start) {
+      io_error_ = std::string("read_snapshot: ") + paths[i] + " and " + paths[0] + " are of different moments of a run (t_sim, t_step, last_dt, pion_next_optime or t_start differ)";
+      return PION_GPU_EINVAL;
+    }
+    struct stat st;
+    const long need = b.data_offset + (long)cfg.nvar * b.slab_n * plane * (long)sizeof(double);
+    if (stat(paths[i], &st) != 0 || (long)st.st_size < need) {
+      io_error_ = std::string("read_snapshot: ") + paths[i] + " is truncated: its header promises " + std::to_string(need) + " bytes";
+      return PION_GPU_EINVAL;
+    }
+  }
+  // which file gives which of this sim's planes (the first that holds a plane)
+  std::vector<int> owner((size_t)nloc, -1);
+  for (int i = 0; i < npaths; i++)
+    for (long p = 0; p < nloc; p++) {
+      const long gp = G.slab_lo + p;
+      if (owner[p] < 0 && gp >= H[i].info.slab_lo && gp < H[i].info.slab_lo + H[i].info.slab_n) owner[p] = i;
+    }
+  for (long p = 0; p < nloc; p++)
+    if (owner[p] < 0) {
+      io_error_ = "read_snapshot: plane " + std::to_string(G.slab_lo + p) + " of the slab axis is in none of the files given";
+      return PION_GPU_EINVAL;
+    }
+
+  // as Init: the previous state's time-step request and halo exchange are void
+  dt_requested_ = false;
+  if (comm_) comm_->reset();
+
+  const bool stream = be_->ongrid_from_host && be_->ongrid_count;
+  std::vector<double> A;   // the whole array with zero ghosts, when the backend cannot stream
+  const long nb = cfg.nbc, nxa = cfg.ng[0] + 2 * nb, nya = (cfg.ndim >= 2) ? cfg.ng[1] + 2 * nb : 1,
+             nza = (cfg.ndim == 3) ? cfg.ng[2] + 2 * nb : 1;
+  const size_t ncell = (size_t)nxa * nya * nza;
+  if (!stream) A.assign((size_t)cfg.nvar * ncell, 0.0);
+  int rc = 0, slot = 0;
+  for (long p0 = 0; p0 < nloc && !rc;) {
+    const int i = owner[p0];
+    long p1 = p0;
+    while (p1 < nloc && owner[p1] == i) p1++;
+    Fd f;
+    f.fd = open(paths[i], O_RDONLY);
+    if (f.fd < 0) {
+      io_error_ = std::string("read_snapshot: cannot open ") + paths[i];
+      return PION_GPU_EINVAL;
+    }
+    const pion_host_snapshot_info &I = H[i].info;
+    FillCtx c;
+    c.fd = f.fd, c.off = I.data_offset, c.frun = (size_t)I.slab_n * plane, c.nvar = cfg.nvar;
+    const long cp = stream ? chunk_planes(be_->ongrid_count(h_, 1), p1 - p0) : p1 - p0;
+    for (long a = p0; a < p1 && !rc; a += cp) {
+      const long b = std::min(p1, a + cp);
+      c.first = (size_t)(G.slab_lo + a - I.slab_lo) * plane;
+      c.n = (size_t)(b - a) * plane;
+      if (stream) {
+        rc = be_->ongrid_from_host(h_, (int)a, (int)b, slot, fill_chunk, &c);
+        slot ^= 1;
+      }
+      else {
+        std::vector<double> R((size_t)cfg.nvar * c.n);
+        rc = fill_chunk(&c, R.data());
+        for (int v = 0; v < cfg.nvar && !rc; v++) {
+          size_t o = (size_t)v * c.n;
+          for (long pl = a; pl < b; pl++)
+            for (long j = 0; j < s.rows; j++) {
+              // plane pl, row j -> (iy, iz) of the ghosted array
+              const long iy = (cfg.ndim == 3) ? j + nb : (cfg.ndim == 2 ? pl + nb : 0);
+              const long iz = (cfg.ndim == 3) ? pl + nb : 0;
+              memcpy(&A[(size_t)v * ncell + nb + (size_t)nxa * (iy + (size_t)nya * iz)], &R[o], (size_t)s.nx * sizeof(double));
+              o += s.nx;
+            }
+        }
+      }
+      if (rc) io_error_ = std::string("read_snapshot: reading the planes from ") + paths[i] + " failed: " + last_error();
+    }
+    p0 = p1;
+  }
+  if (!rc && !stream) {
+    rc = be_->upload(h_, A.data());
+    if (rc) io_error_ = "read_snapshot: upload failed: " + last_error();
+  }
+  if (rc) return rc;
+  const pion_host_snapshot_info &I = H[0].info;
+  T.simtime = I.t_sim;
+  T.timestep = I.t_step;
+  T.last_dt = I.last_dt;
+  T.starttime = I.t_start;
+  T.finishtime = I.t_finish;
+  T.min_timestep = I.min_timestep;
+  T.maxtime = false;
+  if (T.op_criterion == 1 && I.op_criterion == 1) T.next_optime = I.next_optime;
+  else if (T.op_criterion == 1) T.next_optime = T.simtime + T.opfreq_time;
+  last_output_step_ = -1;
+  // assign_boundary_data + TimeUpdateInternalBCs/ExternalBCs (sim_init.cpp:246-267)
+  rc = update_boundaries(cfg.tm_ooa, cfg.tm_ooa, 1);
+  if (rc) io_error_ = "read_snapshot: boundary update failed: " + last_error();
+  return rc;
+}
+
+}  // namespace pion_host

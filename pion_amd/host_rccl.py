@@ -19,6 +19,29 @@ _host = None
 UNIQUE_ID_BYTES = 128
 
 
+class SnapshotInfo(C.Structure):
+    """pion_host_snapshot_info (include/pion_host.h)"""
+    _fields_ = [("t_start", C.c_double), ("t_finish", C.c_double), ("t_sim", C.c_double), ("min_timestep", C.c_double),
+                ("last_dt", C.c_double), ("opfreq_time", C.c_double), ("next_optime", C.c_double),
+                ("t_step", C.c_int), ("op_criterion", C.c_int), ("op_freq", C.c_int),
+                ("rank", C.c_int), ("world", C.c_int), ("slab_lo", C.c_int), ("slab_n", C.c_int),
+                ("data_offset", C.c_long), ("outfile", C.c_char * 256)]
+
+
+def read_snapshot_header(path):
+    """pion_host_snapshot_read_header: (global cfg, dict of pion_host_snapshot_info); host only, needs no device"""
+    lib = load_host_library()
+    cfg, info = abi.PionGpuConfig(), SnapshotInfo()
+    rc = lib.pion_host_snapshot_read_header(os.fsencode(path), C.byref(cfg), C.byref(info))
+    if rc != 0:
+        buf = C.create_string_buffer(600)
+        lib.pion_host_sim_last_error(None, buf, 600)
+        raise ValueError("pion_host_snapshot_read_header rc=%d: %s" % (rc, buf.value.decode(errors="replace")))
+    d = {k: getattr(info, k) for k, _ in SnapshotInfo._fields_}
+    d["outfile"] = d["outfile"].decode()
+    return cfg, d
+
+
 def load_host_library():
     global _host
     if _host is not None:
@@ -46,6 +69,14 @@ def load_host_library():
     h.pion_host_sim_set_comm.argtypes = [C.c_void_p, C.c_void_p]
     h.pion_host_sim_finish_halo.argtypes = [C.c_void_p]
     h.pion_host_sim_last_error.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    h.pion_host_sim_add_wind_source.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    if hasattr(h, "pion_host_sim_set_output"):   # (an older build swapped in for A/B runs has no snapshot entries)
+        h.pion_host_sim_set_output.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_int]
+        h.pion_host_sim_set_slab_extent.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        h.pion_host_sim_write_snapshot.argtypes = [C.c_void_p, C.c_char_p]
+        h.pion_host_sim_read_snapshot.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int]
+        h.pion_host_snapshot_read_header.argtypes = [C.c_char_p, C.POINTER(abi.PionGpuConfig), C.POINTER(SnapshotInfo)]
+        h.pion_host_sim_get_time.argtypes = [C.c_void_p, _dp]
     h.pion_host_comm_unique_id.argtypes = [C.c_void_p]
     h.pion_host_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     h.pion_host_comm_destroy.argtypes = [C.c_void_p]
@@ -143,6 +174,55 @@ class HostSim:
         if n < 0:
             raise RuntimeError("pion_host_sim_time_int: " + self.last_error())
         return n, t.value, ldt.value
+
+    def add_wind_source(self, src):
+        """pion_host_sim_add_wind_source: a device-built source (pion_amd.wind.WindSource, not a rotating one) and its
+        first-step limit; before init() or restart().  Returns its id."""
+        st, keep = src.to_c()
+        i = C.c_int(-1)
+        rc = self.lib.pion_host_sim_add_wind_source(self.s, C.byref(st), C.byref(i))
+        del keep
+        if rc != 0:
+            raise RuntimeError("pion_host_sim_add_wind_source rc=%d: %s" % (rc, self.last_error()))
+        return i.value
+
+    def set_output(self, outfile_base, op_criterion=0, opfreq=0, opfreq_time=0.0, checkpoint_freq=0):
+        """SimPM.outFileBase / op_criterion / opfreq / opfreq_time / checkpoint_freq: from now on time_int writes
+        <base>_<rank>.<step>.pionraw snapshots and checkpoints (pion_host_sim_set_output).  After init(), before
+        restart()."""
+        rc = self.lib.pion_host_sim_set_output(self.s, os.fsencode(outfile_base), int(op_criterion), int(opfreq),
+                                               float(opfreq_time), int(checkpoint_freq))
+        if rc != 0:
+            raise ValueError("pion_host_sim_set_output rc=%d (op_criterion 0 or 1, opfreq_time > 0 with criterion 1)" % rc)
+
+    def set_slab_extent(self, global_planes, plane_lo, bc_lo, bc_hi):
+        """where this rank's slab sits in the global problem, and the global problem's two slab-axis faces (abi.BC_*)"""
+        rc = self.lib.pion_host_sim_set_slab_extent(self.s, int(global_planes), int(plane_lo), int(bc_lo), int(bc_hi))
+        if rc != 0:
+            raise ValueError("pion_host_sim_set_slab_extent rc=%d" % rc)
+
+    def write_snapshot(self, path):
+        """the PIONRAW2 file of this sim's on-grid cells (pion_host_sim_write_snapshot)"""
+        rc = self.lib.pion_host_sim_write_snapshot(self.s, os.fsencode(path))
+        if rc != 0:
+            raise RuntimeError("pion_host_sim_write_snapshot rc=%d: %s" % (rc, self.last_error()))
+
+    def restart(self, paths):
+        """pion_host_sim_read_snapshot: restart from the file(s) that hold this sim's planes (one path or a list)"""
+        if isinstance(paths, (str, bytes, os.PathLike)):
+            paths = [paths]
+        arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+        rc = self.lib.pion_host_sim_read_snapshot(self.s, arr, len(paths))
+        if rc != 0:
+            raise RuntimeError("pion_host_sim_read_snapshot rc=%d: %s" % (rc, self.last_error()))
+
+    def get_time(self):
+        """dict simtime, last_dt, next_optime, finishtime, starttime, timestep of the loop"""
+        out = np.zeros(6)
+        self.lib.pion_host_sim_get_time(self.s, out.ctypes.data_as(_dp))
+        d = dict(zip(["simtime", "last_dt", "next_optime", "finishtime", "starttime"], out[:5].tolist()))
+        d["timestep"] = int(out[5])
+        return d
 
     def download(self, which=0):
         out = np.empty(int(np.prod(self.shape)))

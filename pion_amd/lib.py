@@ -77,6 +77,11 @@ def load_library():
     lib.pion_gpu_halo_spans.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.pion_gpu_halo_begin.argtypes = [C.c_void_p]
     lib.pion_gpu_halo_end.argtypes = [C.c_void_p]
+    if hasattr(lib, "pion_gpu_pack_ongrid"):   # (likewise)
+        lib.pion_gpu_ongrid_count.argtypes = [C.c_void_p, C.c_int]
+        lib.pion_gpu_ongrid_count.restype = C.c_long
+        lib.pion_gpu_pack_ongrid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        lib.pion_gpu_unpack_ongrid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.pion_gpu_interface_flux.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pion_gpu_cooling_update.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp]
     lib.pion_gpu_cooling_edot.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
@@ -103,6 +108,7 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_wind_orbit_position", "pion_gpu_get_flags", "pion_gpu_add_rotating_wind_source",
     "pion_gpu_wind_angle_tables", "pion_gpu_get_hll_switch", "pion_gpu_get_hll_screen_counts",
     "pion_gpu_rows_windows", "pion_gpu_get_rows_windows",
+    "pion_gpu_ongrid_count", "pion_gpu_pack_ongrid", "pion_gpu_unpack_ongrid",
 ]
 
 
@@ -330,6 +336,20 @@ class GpuSim:
 
     def halo_end(self):
         self._chk(self.lib.pion_gpu_halo_end(self.h), "halo_end")
+
+    # --- on-grid planes (snapshots)
+    def ongrid_count(self, planes):
+        """pion_gpu_ongrid_count: doubles in a buffer of `planes` planes of the slab axis, all variables"""
+        return self.lib.pion_gpu_ongrid_count(self.h, int(planes))
+
+    def pack_ongrid(self, which, plane_lo, plane_hi, dbuf_ptr):
+        """pion_gpu_pack_ongrid: on-grid cells of planes [plane_lo, plane_hi) of array `which` into the device buffer
+        at dbuf_ptr, [nvar][planes][ny][nx]; enqueued on the handle's stream (synchronize() before reading it)"""
+        self._chk(self.lib.pion_gpu_pack_ongrid(self.h, which, plane_lo, plane_hi, C.c_void_p(dbuf_ptr)), "pack_ongrid")
+
+    def unpack_ongrid(self, plane_lo, plane_hi, dbuf_ptr):
+        """pion_gpu_unpack_ongrid: the reverse, into P and Ph; ghost cells and other planes are left alone"""
+        self._chk(self.lib.pion_gpu_unpack_ongrid(self.h, plane_lo, plane_hi, C.c_void_p(dbuf_ptr)), "unpack_ongrid")
 
     # --- seams
     def interface_flux(self, axis, Pl, Pr, aux=None, dt=1.0):
