@@ -1,9 +1,9 @@
 // pion_gpu.hip -- implementation of the C-ABI declared in include/pion_gpu.h.
 //
 // Host side of the boundary: owns device memory behind an opaque handle (pion_handle.h): set-up and tear-down,
-// uploads, stellar winds, jet, cooling tables, the test seams and timing, and the data-movement kernels of the
-// boundary update, which have no arithmetic: ghost-cell fills (boundaries/*.cpp of the reference), stellar-wind
-// cell reset.  What a time step calls (time step, stages, halo) is pion_step.hip.
+// uploads, jet, cooling tables, the test seams and timing, and the data-movement kernels of the boundary update, which
+// have no arithmetic: ghost-cell fills (boundaries/*.cpp of the reference), the cell reset of the legacy wind list and
+// the jet.  What a time step calls is pion_step.hip; the stellar-wind sources are pion_wind.hip and wind_host.cpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -11,14 +11,10 @@
 #include <cstdlib>
 #include <cstring>
 
-#include <hipcub/hipcub.hpp>
-
-#include "dev_wind.h"
 #include "pion_handle.h"
 
 using namespace pion;
 using namespace pion::impl;
-static_assert(ANGLE_NTHETA == PION_ANGLE_NTHETA && ANGLE_NOMEGA == PION_ANGLE_NOMEGA && ANGLE_NTEFF == PION_ANGLE_NTEFF);
 
 int impl::order_after_unpack(Handle *h)
 {
@@ -465,591 +461,6 @@ __global__ void k_wind(double *T, const long *idx, const double *states, const l
   for (int v = 0; v < nvar; v++) T[v * nc + c] = states[t * nvar + v];
 }
 
-// constants::equalD (constants.cpp:48-68)
-static bool equalD(const double a, const double b)
-{
-  if (a == b) return true;
-  if (fabs(a) + fabs(b) < 1.0e-100) return true;
-  return (fabs(a - b) / (fabs(a) + fabs(b) + 1.0e-100)) < 1.0e-12;
-}
-
-// interpolate_arrays::root_find_linear_vec (tools/interpolate.cpp:121-161), as written: bisection, then linear
-// interpolation with the requested x clamped to the bracketing nodes (zero slope outside the table)
-static double root_find_linear_vec(const std::vector<double> &xarr, const std::vector<double> &yarr, const double xreq)
-{
-  const size_t len = xarr.size();
-  size_t ihi = len - 1, ilo = 0, imid = 0;
-  do {
-    imid = ilo + (size_t)floor((ihi - ilo) / 2.0);
-    if (xarr[imid] < xreq) ilo = imid;
-    else ihi = imid;
-  } while (ihi - ilo > 1);
-  double xval = 0.0;
-  if (xreq > xarr[ihi]) xval = xarr[ihi];
-  else if (xreq < xarr[ilo]) xval = xarr[ilo];
-  else xval = xreq;
-  return yarr[ilo] + (yarr[ihi] - yarr[ilo]) * (xval - xarr[ilo]) / (xarr[ihi] - xarr[ilo]);
-}
-
-// Append n slots to the concatenated wind-source lists (cell ids, dist, offsets, states; the new states zeroed); the
-// earlier sources' entries keep their place at the front.  h->nws grows by n.
-static int wind_lists_grow(Handle *h, const long n)
-{
-  const long o = h->nws, ntot = o + n;
-  const int nvar = h->cfg.nvar;
-  long *nidx = nullptr;
-  double *ndist = nullptr, *noff = nullptr, *nstate = nullptr, *ntheta = nullptr;
-  if (ntot > 0) {
-    HCHECK(h, hipMalloc(&nidx, sizeof(long) * ntot));
-    HCHECK(h, hipMalloc(&ndist, sizeof(double) * ntot));
-    HCHECK(h, hipMalloc(&ntheta, sizeof(double) * ntot));
-    HCHECK(h, hipMemsetAsync(ntheta, 0, sizeof(double) * ntot, h->stream));
-    HCHECK(h, hipMalloc(&noff, sizeof(double) * 3 * ntot));
-    HCHECK(h, hipMalloc(&nstate, sizeof(double) * ntot * nvar));
-    HCHECK(h, hipMemsetAsync(nstate, 0, sizeof(double) * ntot * nvar, h->stream));
-  }
-  if (o > 0) {
-    HCHECK(h, hipMemcpyAsync(nidx, h->dws_idx, sizeof(long) * o, hipMemcpyDeviceToDevice, h->stream));
-    HCHECK(h, hipMemcpyAsync(ndist, h->dws_dist, sizeof(double) * o, hipMemcpyDeviceToDevice, h->stream));
-    HCHECK(h, hipMemcpyAsync(ntheta, h->dws_theta, sizeof(double) * o, hipMemcpyDeviceToDevice, h->stream));
-    for (int a = 0; a < 3; a++)
-      HCHECK(h, hipMemcpyAsync(noff + a * ntot, h->dws_off + a * o, sizeof(double) * o, hipMemcpyDeviceToDevice,
-                               h->stream));
-    HCHECK(h, hipMemcpyAsync(nstate, h->dws_state, sizeof(double) * o * nvar, hipMemcpyDeviceToDevice, h->stream));
-  }
-  HCHECK(h, hipStreamSynchronize(h->stream));
-  hipFree(h->dws_idx);
-  hipFree(h->dws_dist);
-  hipFree(h->dws_off);
-  hipFree(h->dws_state);
-  hipFree(h->dws_theta);
-  h->dws_idx = nidx;
-  h->dws_theta = ntheta;
-  h->dws_dist = ndist;
-  h->dws_off = noff;
-  h->dws_state = nstate;
-  h->nws = ntot;
-  return 0;
-}
-
-// BC_update_STWIND's new source position (stellar_wind_boundaries.cpp:294-314): the ellipse in the x-y plane, in
-// plain double, the reference's expressions in their order (no contraction).  abs is std::abs(double) there;
-// pconst.pi() and pconst.year() are constants.h:45,107.  z stays at dpos_init.
-static void wind_orbit_position(const pion_gpu_wind_source &s, const int ndim, const double simtime, double *pos)
-{
-#pragma clang fp contract(off)
-  for (int v = 0; v < 3; v++) pos[v] = (v < ndim) ? s.pos[v] : 0.0;
-  if (s.orbit_period == 0) return;
-  const double pi = 3.14159265358979324, year = 3.1558150e7;
-  const double px = s.orbit_periastron[0], py = s.orbit_periastron[1];
-  const double f = s.orbit_ecc_fac, P = s.orbit_period;
-  const double cos_a = -1 * px / std::abs(px) * cos(atan(py / px));
-  const double sin_a = sin(-1 * py / std::abs(py) * acos(cos_a));
-  const double a = sqrt(px * px + py * py) * f;
-  const double e = a * (f - 1) / f;
-  const double b = sqrt(a * a - e * e);
-  const double sin_t = sin(2 * pi * simtime / (P * year));
-  const double cos_t = cos(2 * pi * simtime / (P * year));
-  pos[0] = s.pos[0] - a * cos_a + cos_a * a * cos_t - sin_a * b * sin_t;
-  pos[1] = s.pos[1] - a * sin_a + sin_a * a * cos_t + cos_a * b * sin_t;
-}
-
-// ---- rotating stars, LGM99 (grid/stellar_wind_angle.cpp): the tables of setup_tables (:92-212) and the fn_*
-// functions, in plain double, the reference's expressions in their order (no contraction).  pconst.pi(), sqrt2()
-// are constants.h:45,48; pow_fast(a, b) = exp(b*log(a)) (constants.cpp:78-84); ONE_MINUS_EPS = 1 - 1e-12
-// (constants.h:157).  c_gamma = 0.35, c_beta = -1 (unused), c_xi = xi (:58-63).  The tables are AngleTables.
-
-namespace lgm99 {
-const double pi = 3.14159265358979324, sqrt2 = 1.4142135623730950, c_gamma = 0.35;
-
-static double pow_fast(const double a, const double b) { return exp(b * log(a)); }
-
-// stellar_wind::beta (stellar_wind_BC.cpp:820-867)
-static double beta(const double Teff)
-{
-#pragma clang fp contract(off)
-  const double rsg = 0.125;
-  if (Teff <= 3600.0) return rsg;
-  if (Teff >= 22000.0) return 2.6;
-  double b0, b1, T0, T1;
-  if (Teff < 6000.0) {
-    T0 = 3600.0; b0 = rsg; T1 = 6000.0; b1 = 0.5;
-  }
-  else if (Teff < 8000.0) {
-    T0 = 6000.0; b0 = 0.5; T1 = 8000.0; b1 = 0.7;
-  }
-  else if (Teff < 10000.0) {
-    T0 = 8000.0; b0 = 0.7; T1 = 10000.0; b1 = 1.3;
-  }
-  else if (Teff < 20000.0) {
-    T0 = 10000.0; b0 = 1.3; T1 = 20000.0; b1 = 1.3;
-  }
-  else {
-    T0 = 20000.0; b0 = 1.3; T1 = 22000.0; b1 = 2.6;
-  }
-  return b0 + (Teff - T0) * (b1 - b0) / (T1 - T0);
-}
-
-// fn_phi (:286-294)
-static double fn_phi(const double omega, const double theta, const double Teff)
-{
-#pragma clang fp contract(off)
-  const double ans = (omega / (22.0 * sqrt2 * beta(Teff))) * sin(theta) * pow_fast(1.0 - omega * sin(theta), -c_gamma);
-  const double cap = 0.5 * pi * (1.0 - 1.0e-12);
-  return (cap < ans) ? cap : ans;   // std::min(ans, cap)
-}
-
-// fn_alpha (:304-315)
-static double fn_alpha(const double omega, const double theta, const double Teff)
-{
-#pragma clang fp contract(off)
-  return pow_fast(cos(fn_phi(omega, theta, Teff)) + pow_fast(tan(theta), -2.0) *
-                                                        (1.0 + c_gamma * (omega * sin(theta) / (1.0 - omega * sin(theta)))) *
-                                                        fn_phi(omega, theta, Teff) * sin(fn_phi(omega, theta, Teff)),
-                  -1.0);
-}
-
-// integrand (:222-229), integrate_Simpson (:239-276), fn_delta (:325-333)
-static double integrand(const double theta, const double omega, const double Teff, const double xi)
-{
-#pragma clang fp contract(off)
-  return fn_alpha(omega, theta, Teff) * pow_fast(1.0 - omega * sin(theta), xi) * sin(theta);
-}
-
-static double fn_delta(const double omega, const double Teff, const double xi)
-{
-#pragma clang fp contract(off)
-  const double min = 0.001, max = pi / 2.0;
-  const long npt = 230;
-  const double hh = (max - min) / npt;
-  double ans = 0.0;
-  ans += integrand(min, omega, Teff, xi);
-  ans += integrand(max, omega, Teff, xi);
-  int wt = 4;
-  double x = 0.0;
-  for (long i = 1; i < npt; i++) {
-    x = min + i * hh;
-    ans += wt * integrand(x, omega, Teff, xi);
-    wt = 6 - wt;
-  }
-  ans *= hh / 3.0;
-  return 2.0 * pow_fast(ans, -1.0);
-}
-
-// setup_tables (:92-212)
-static void setup_tables(const double xi, AngleTables &T)
-{
-#pragma clang fp contract(off)
-  T.xi = xi;
-  const int nth = PION_ANGLE_NTHETA, nom = PION_ANGLE_NOMEGA, nT = PION_ANGLE_NTEFF;
-  const double theta_min = 0.1, theta_mid = 60.0, theta_max = 89.9;
-  for (int k = 0; k < nth; k++) {
-    if (k <= 4) T.theta[k] = (theta_min + k * ((theta_mid - theta_min) / 4.0)) * (pi / 180.0);
-    else T.theta[k] = (theta_mid + (k - 4) * ((theta_max - theta_mid) / (nth - 5))) * (pi / 180.0);
-  }
-  double log_mu[PION_ANGLE_NOMEGA];
-  for (int i = 0; i < nom; i++) log_mu[nom - i - 1] = -4.0 + i * (4.0 / (nom - 1));
-  for (int j = 0; j < nom; j++) T.omega[j] = 1 - pow_fast(10, log_mu[j]);
-  const double T0 = 1000.0, T1 = 3600.0, T2 = 6000.0, T3 = 8000.0, T4 = 10000.0, T5 = 20000.0, T6 = 22000.0,
-               T7 = 150000.0;
-  for (int i = 0; i < nT; i++) {
-    if (i == 0) T.Teff[i] = T0;
-    if (i == 1) T.Teff[i] = T1;
-    if (2 <= i && i <= 6) T.Teff[i] = T1 + i * ((T2 - T1) / 6);
-    if (i == 7) T.Teff[i] = T2;
-    if (8 <= i && i <= 10) T.Teff[i] = T2 + (i - 6) * ((T3 - T2) / 4);
-    if (i == 11) T.Teff[i] = T3;
-    if (12 <= i && i <= 14) T.Teff[i] = T3 + (i - 10) * ((T4 - T3) / 4);
-    if (i == 15) T.Teff[i] = T4;
-    if (i == 16) T.Teff[i] = T5;
-    if (17 <= i && i <= 19) T.Teff[i] = T5 + (i - 15) * ((T6 - T5) / 4);
-    if (i == 20) T.Teff[i] = T6;
-    if (i == 21) T.Teff[i] = T7;
-  }
-  T.delta.assign((size_t)nom * nT, 0.0);
-  for (int i = 0; i < nom; i++)
-    for (int j = 0; j < nT; j++) T.delta[(size_t)i * nT + j] = fn_delta(T.omega[i], T.Teff[j], xi);
-  T.alpha.assign((size_t)nom * nth * nT, 0.0);
-  for (int i = 0; i < nom; i++)
-    for (int j = 0; j < nth; j++)
-      for (int k = 0; k < nT; k++) T.alpha[((size_t)i * nth + j) * nT + k] = fn_alpha(T.omega[i], T.theta[j], T.Teff[k]);
-}
-
-// interpolate_arrays::root_find_bilinear_vec (tools/interpolate.cpp:300-380) on delta(omega, Teff)
-static double delta_interp(const AngleTables &T, const double xr, const double yr)
-{
-#pragma clang fp contract(off)
-  const double *x = T.omega, *y = T.Teff;
-  size_t ihi = PION_ANGLE_NOMEGA - 1, jhi = PION_ANGLE_NTEFF - 1, ilo = 0, jlo = 0, imid = 0, jmid = 0;
-  do {
-    imid = ilo + (size_t)floor((ihi - ilo) / 2.0);
-    if (x[imid] < xr) ilo = imid;
-    else ihi = imid;
-  } while (ihi - ilo > 1);
-  do {
-    jmid = jlo + (size_t)floor((jhi - jlo) / 2.0);
-    if (y[jmid] < yr) jlo = jmid;
-    else jhi = jmid;
-  } while (jhi - jlo > 1);
-  double xval, yval;
-  if (xr > x[ihi]) xval = x[ihi];
-  else if (xr < x[ilo]) xval = x[ilo];
-  else xval = xr;
-  if (yr > y[jhi]) yval = y[jhi];
-  else if (yr < y[jlo]) yval = y[jlo];
-  else yval = yr;
-  const size_t nT = PION_ANGLE_NTEFF;
-  const std::vector<double> &f = T.delta;
-  double result = (f[ilo * nT + jlo] * (x[ihi] - xval) * (y[jhi] - yval) + f[ihi * nT + jlo] * (xval - x[ilo]) * (y[jhi] - yval) +
-                   f[ilo * nT + jhi] * (x[ihi] - xval) * (yval - y[jlo]) + f[ihi * nT + jhi] * (xval - x[ilo]) * (yval - y[jlo]));
-  result /= ((x[ihi] - x[ilo]) * (y[jhi] - y[jlo]));
-  return result;
-}
-}  // namespace lgm99
-
-// The box of moving source W centred on `pos`: per axis the w cells from one below the first cell whose centre can
-// lie within the radius (the exact test runs in the kernels).  A NaN position gives some box; no cell passes there.
-static WindBox wind_box(const Handle *h, const WindSource &W, const double *pos)
-{
-  const GridDesc &g = h->g;
-  WindBox b;
-  b.n = 1;
-  for (int a = 0; a < 3; a++) {
-    b.w[a] = W.box_w[a];
-    b.lo[a] = 0;
-    if (a < g.ndim && b.w[a] < g.nga[a]) {
-      // all-cell index i has its centre at xmin + (i - nbc + 0.5) dx
-      double t = (pos[a] - W.radius - g.xmin[a]) / g.dx - 0.5 + g.nbc[a];
-      if (!(t == t)) t = 0.0;
-      t = std::min(std::max(t, -2.0 * g.nga[a]), 2.0 * g.nga[a]);
-      b.lo[a] = (int)floor(t) - 1;
-    }
-    b.n *= b.w[a];
-  }
-  return b;
-}
-
-static WindMember wind_member(const Handle *h, const WindSource &W)
-{
-  WindMember m;
-  m.g = h->g;
-  for (int a = 0; a < 3; a++) m.pos[a] = W.pos[a];
-  m.radius = W.radius;
-  return m;
-}
-
-typedef hipcub::TransformInputIterator<long, WindBoxCell, hipcub::CountingInputIterator<long>> WindBoxIter;
-
-// BC_assign_STWIND_add_cells2src for a moving source at W.pos: the cells of its box within the radius, in cell-id
-// order, compacted into its slot of the lists with the count left in W.dn; then dist, offsets and the flags
-// (stellar_wind::add_cell, stellar_wind_BC.cpp:255-283).  Asynchronous, no allocation.
-static int wind_add_cells_box(Handle *h, const WindSource &W)
-{
-  const WindMember m = wind_member(h, W);
-  WindBoxCell bc;
-  bc.g = h->g;
-  bc.b = wind_box(h, W, W.pos);
-  WindBoxMember pred;
-  pred.m = m;
-  WindBoxIter cells(hipcub::CountingInputIterator<long>(0), bc);
-  size_t bytes = W.scan_bytes;
-  HCHECK(h, hipcub::DeviceSelect::If(W.dscan, bytes, cells, h->dws_idx + W.off, W.dn, (int)W.n, pred, h->stream));
-  hipLaunchKernelGGL(k_wind_cells_dn, dim3((unsigned)((W.n + 255) / 256)), dim3(256), 0, h->stream, m,
-                     h->dws_idx + W.off, W.dn, h->dws_dist + W.off, h->dws_off + W.off, h->nws, h->dflags);
-  return 0;
-}
-
-// pion_gpu_add_wind_source for a source with orbit_period != 0 (2-D / 3-D Cartesian): its slot in the lists, the
-// count and the compaction scratch are sized once, to the box.  The cells at dpos_init join it now, as for a fixed
-// source.
-static int add_moving_wind_source(Handle *h, WindSource &W, int *id)
-{
-  const GridDesc &g = h->g;
-  long cap = 1;
-  for (int a = 0; a < 3; a++) {
-    W.box_w[a] = 1;
-    if (a < g.ndim) {
-      // the sphere spans at most floor(2 radius / dx) + 1 cell centres per axis; plus the margin, plus rounding
-      const double w = floor(2.0 * W.radius / g.dx) + 5.0;
-      W.box_w[a] = (w >= (double)g.nga[a]) ? g.nga[a] : (int)w;
-    }
-    cap *= W.box_w[a];
-  }
-  if (cap > 0x7fffffffL) {
-    h->err = "wind source: the orbit box is too large";
-    return PION_GPU_EINVAL;
-  }
-  if (int rc = wind_lists_grow(h, cap)) return rc;
-  W.off = h->nws - cap;
-  W.n = cap;
-  HCHECK(h, hipMalloc(&W.dn, sizeof(long)));
-  HCHECK(h, hipMemsetAsync(W.dn, 0, sizeof(long), h->stream));
-  {
-    WindBoxCell bc;
-    bc.g = g;
-    bc.b = wind_box(h, W, W.pos);
-    WindBoxMember pred;
-    pred.m = wind_member(h, W);
-    WindBoxIter cells(hipcub::CountingInputIterator<long>(0), bc);
-    W.scan_bytes = 0;
-    HCHECK(h, hipcub::DeviceSelect::If(nullptr, W.scan_bytes, cells, h->dws_idx + W.off, W.dn, (int)cap, pred,
-                                       h->stream));
-    HCHECK(h, hipMalloc(&W.dscan, W.scan_bytes > 0 ? W.scan_bytes : 1));
-  }
-  h->wsrc.push_back(W);
-  if (int rc = wind_add_cells_box(h, h->wsrc.back())) return rc;
-  HCHECK(h, hipGetLastError());
-  HCHECK(h, hipStreamSynchronize(h->stream));
-  state_changed(h);   // the ISBD flags decide which cells enter the time-step reduction
-  if (id) *id = (int)h->wsrc.size() - 1;
-  return 0;
-}
-
-// BC_update_STWIND (stellar_wind_boundaries.cpp:270-322) for every moving source, in id order: remove_cells on the
-// cells within the radius of the current position, the new position from simtime, then the cells within the radius
-// of that position join the source.  Launches only, over the two boxes; nothing waits for the device.
-static int wind_sources_move(Handle *h, const double simtime)
-{
-  bool moved = false;
-  for (size_t s = 0; s < h->wsrc.size(); s++) {
-    WindSource &W = h->wsrc[s];
-    if (!W.moving) continue;
-    const WindBox ob = wind_box(h, W, W.pos);
-    hipLaunchKernelGGL(k_wind_unflag, dim3((unsigned)((ob.n + 255) / 256)), dim3(256), 0, h->stream,
-                       wind_member(h, W), ob, h->dflags);
-    double np[3];
-    wind_orbit_position(W.orbit, h->cfg.ndim, simtime, np);
-    for (int a = 0; a < 3; a++) {
-      moved = moved || !(np[a] == W.pos[a]);
-      W.pos[a] = np[a];
-    }
-    if (int rc = wind_add_cells_box(h, W)) return rc;
-  }
-  // An unchanged position leaves the flags as they were: every cell an unflag touches lies in the sphere of that
-  // moving source, which re-adds it at once.  A move changes them, and with them the cached time step.
-  if (moved) state_changed(h);
-  return 0;
-}
-
-// omega of a rotating source: fn_density_interp's std::min(std::min(0.9999, v_rot/vcrit), 0.999)
-// (stellar_wind_angle.cpp:395, :493); fn_v_inf's clip (:350) gives the same value
-static double angle_omega(const double vrot, const double vcrit)
-{
-  const double r = vrot / vcrit;
-  const double o = (r < 0.9999) ? r : 0.9999;
-  return (0.999 < o) ? 0.999 : o;
-}
-
-// The values a rotating source writes with at simtime (update_source, stellar_wind_angle.cpp:941-1019, when it is
-// due), without changing the source.  false: the source does not write.
-static bool angle_values_at(const Handle *h, const WindSource &W, const double simtime, double *Tw, double *omega)
-{
-  const bool due = simtime >= W.t_next_update;
-  if (!(W.active || due)) return false;
-  double tw = W.Tw_c, vrot = W.vrot_c, vcrit = W.vcrit_c;
-  if (due) {
-    const double T = root_find_linear_vec(W.t, W.Teff, simtime), Tmax = h->angle.Teff[PION_ANGLE_NTEFF - 1];
-    tw = (Tmax < T) ? Tmax : T;
-    vrot = root_find_linear_vec(W.t, W.vrot, simtime);
-    vcrit = root_find_linear_vec(W.t, W.vcrit, simtime);
-  }
-  *Tw = tw;
-  *omega = angle_omega(vrot, vcrit);
-  return true;
-}
-
-// Before any launch of a boundary update: root_find_trilinear_vec calls rep.error for omega <= omega_vec[0] and
-// Teff <= Teff_vec[0] (tools/interpolate.cpp:420-440), so a rotating source that would write with such values
-// makes the update EINVAL, with nothing written.
-static int wind_angle_check(Handle *h, const double simtime)
-{
-  for (size_t s = 0; s < h->wsrc.size(); s++) {
-    const WindSource &W = h->wsrc[s];
-    double Tw, omega;
-    if (W.type != 2 || !angle_values_at(h, W, simtime, &Tw, &omega)) continue;
-    if (!(omega > h->angle.omega[0]) || !(Tw > h->angle.Teff[0])) {
-      h->err = "rotating wind source: omega <= 0 or Tw <= 1000 K (stellar_wind_angle look-up out of range)";
-      return PION_GPU_EINVAL;
-    }
-  }
-  return 0;
-}
-
-// k_wind_state_angle's launch for rotating source W: the parts of fn_density_interp that do not depend on the cell
-static void wind_angle_launch(Handle *h, const WindSource &W, const WindStateArgs &a)
-{
-#pragma clang fp contract(off)
-  const AngleTables &T = h->angle;
-  WindAngleArgs g;
-  memset(&g, 0, sizeof g);
-  g.P = a.P;
-  g.Ph = a.Ph;
-  g.states = a.states;
-  g.idx = a.idx;
-  g.dist = a.dist;
-  g.off = a.off;
-  g.theta = h->dws_theta;
-  g.ntot = a.ntot;
-  g.ncell = a.ncell;
-  g.nvar = a.nvar;
-  g.ntracer = a.ntracer;
-  g.ndim = a.ndim;
-  g.eqntype = a.eqntype;
-  g.cooling = a.cooling;
-  g.Tmin = a.Tmin;
-  g.Mu_tot_over_kB = a.Mu_tot_over_kB;
-  WindAngleDev &d = g.s;
-  d.Mdot = W.Mdot_c;
-  d.Vinf = W.Vinf_c;
-  d.v_rot = W.vrot_c;
-  d.Tw = W.Tw_c;
-  d.Rstar = W.Rstar_c;
-  d.Bstar = W.Bstar;
-  d.radius = W.radius;
-  d.xi = T.xi;
-  const double om = angle_omega(W.vrot_c, W.vcrit_c), Tw = W.Tw_c;
-  d.omega = om;
-  d.delta = lgm99::delta_interp(T, om, Tw);
-  // root_find_trilinear_vec's omega and Teff brackets (while (x > x_vec[i]) i++; wind_angle_check keeps i >= 1)
-  int xi = 0, zi = 0;
-  while (xi < PION_ANGLE_NOMEGA - 1 && om > T.omega[xi]) xi++;
-  while (zi < PION_ANGLE_NTEFF - 1 && Tw > T.Teff[zi]) zi++;
-  xi = std::max(xi, 1);
-  zi = std::max(zi, 1);
-  d.dx = (om - T.omega[xi - 1]) / (T.omega[xi] - T.omega[xi - 1]);
-  d.dz = (Tw - T.Teff[zi - 1]) / (T.Teff[zi] - T.Teff[zi - 1]);
-  const int nth = PION_ANGLE_NTHETA, nT = PION_ANGLE_NTEFF;
-  for (int j = 0; j < nth; j++) {
-    d.theta[j] = T.theta[j];
-    d.a[0][j] = T.alpha[((size_t)(xi - 1) * nth + j) * nT + zi - 1];
-    d.a[1][j] = T.alpha[((size_t)(xi - 1) * nth + j) * nT + zi];
-    d.a[2][j] = T.alpha[((size_t)xi * nth + j) * nT + zi - 1];
-    d.a[3][j] = T.alpha[((size_t)xi * nth + j) * nT + zi];
-  }
-  for (int v = 0; v < PION_MAX_NTR; v++) d.tr[v] = (v < h->cfg.ntracer) ? W.tr[v] : 0.0;
-  d.off = W.off;
-  d.n = W.n;
-  hipLaunchKernelGGL(k_wind_state_angle, dim3((unsigned)((W.n + 255) / 256)), dim3(256), 0, h->stream, g);
-}
-
-// stellar_wind_evolution::set_cell_values (stellar_wind_BC.cpp:1334-1372) and update_source (:1250-1330; rotating
-// sources: stellar_wind_angle::update_source, stellar_wind_angle.cpp:941-1019) for every source, then one launch per
-// active source, in id order, that writes the reference states of its cells (no host synchronisation: the
-// parameters are scalars of the host, the launch carries them)
-int wind_sources_update(Handle *h, const double simtime)
-{
-  if (int rc = wind_sources_move(h, simtime)) return rc;
-  WindStateArgs a;
-  memset(&a, 0, sizeof a);
-  for (size_t s = 0; s < h->wsrc.size(); s++) {
-    WindSource &W = h->wsrc[s];
-    if ((W.type == 1 || W.type == 2) && simtime >= W.t_next_update) {
-      // update_source: every step from tstart on (:1266), values clamped after tfinish
-      W.active = true;
-      W.t_next_update = std::min(simtime, W.tfinish);
-      W.Tw_c = root_find_linear_vec(W.t, W.Teff, simtime);
-      W.Mdot_c = root_find_linear_vec(W.t, W.Mdot, simtime);
-      W.vrot_c = root_find_linear_vec(W.t, W.vrot, simtime);
-      W.Vinf_c = root_find_linear_vec(W.t, W.vinf, simtime);
-      W.Rstar_c = root_find_linear_vec(W.t, W.R, simtime);
-      for (int v = 0; v < h->cfg.ntracer; v++)
-        if (W.elem[v] >= 0) W.tr[v] = root_find_linear_vec(W.t, W.X[W.elem[v]], simtime);
-      if (W.type == 2) {
-        // all in cgs already; Tw = std::min(Twind, Teff_vec.back()) (stellar_wind_angle.cpp:972-984)
-        const double Tmax = h->angle.Teff[PION_ANGLE_NTEFF - 1];
-        W.Tw_c = (Tmax < W.Tw_c) ? Tmax : W.Tw_c;
-        W.vcrit_c = root_find_linear_vec(W.t, W.vcrit, simtime);
-      }
-    }
-    WindSrcDev &d = a.s[s];
-    d.Mdot = W.Mdot_c;
-    d.Vinf = W.Vinf_c;
-    d.v_rot = W.vrot_c;
-    d.Tw = W.Tw_c;
-    d.Rstar = W.Rstar_c;
-    d.Bstar = W.Bstar;
-    d.radius = W.radius;
-    for (int v = 0; v < PION_MAX_NTR; v++) d.tr[v] = (v < h->cfg.ntracer) ? W.tr[v] : 0.0;
-    d.off = W.off;
-    d.n = W.n;
-    d.dn = W.moving ? W.dn : nullptr;
-    d.active = W.active ? 1 : 0;
-  }
-  a.P = h->dP;
-  a.Ph = h->dPh;
-  a.states = h->dws_state;
-  a.idx = h->dws_idx;
-  a.dist = h->dws_dist;
-  a.off = h->dws_off;
-  a.ntot = h->nws;
-  a.ncell = h->g.ncell;
-  a.nsrc = (int)h->wsrc.size();
-  a.nvar = h->cfg.nvar;
-  a.ntracer = h->cfg.ntracer;
-  a.ndim = h->cfg.ndim;
-  a.cart2d = (h->cfg.ndim == 2 && h->cfg.coord_sys == 1) ? 1 : 0;
-  a.eqntype = h->cfg.eqntype;
-  a.cooling = (h->cfg.cooling != 0) ? 1 : 0;
-  a.Tmin = h->cfg.min_temp;   // EP.MinTemperature, as handed to the stellar_wind constructor
-  a.Mu_tot_over_kB = h->Mu_tot_over_kB;
-  // stellar_wind_evolution::set_cell_values: an inactive source keeps its cells flagged but does not write them
-  for (int s = 0; s < a.nsrc; s++) {
-    if (!(a.s[s].active && a.s[s].n > 0)) continue;
-    if (h->wsrc[s].type == 2) wind_angle_launch(h, h->wsrc[s], a);
-    else hipLaunchKernelGGL(k_wind_state, dim3((unsigned)((a.s[s].n + 255) / 256)), dim3(256), 0, h->stream, a, s);
-  }
-  return 0;
-}
-
-// BC_assign_STWIND_add_cells2src for a fixed source (orbit_period == 0): every cell, ghosts included, within the
-// radius joins it in cell-id order; then dist, offsets, theta and the flags.  Synchronises.
-static int add_fixed_wind_source(Handle *h, WindSource &W, int *id)
-{
-  // membership: every cell, ghosts included, in cell-id order (a scan: hipcub::DeviceSelect keeps the input order)
-  const GridDesc &g = h->g;
-  const WindMember m = wind_member(h, W);
-  unsigned long long *dcount = nullptr;
-  HCHECK(h, hipMalloc(&dcount, sizeof(unsigned long long)));
-  HCHECK(h, hipMemsetAsync(dcount, 0, sizeof(unsigned long long), h->stream));
-  hipLaunchKernelGGL(k_wind_count, dim3((unsigned)((g.ncell + 255) / 256)), dim3(256), 0, h->stream, m, dcount);
-  unsigned long long cnt = 0;
-  HCHECK(h, hipMemcpyAsync(&cnt, dcount, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
-  HCHECK(h, hipStreamSynchronize(h->stream));
-  hipFree(dcount);
-  const long n = (long)cnt;
-  if (int rc = wind_lists_grow(h, n)) return rc;
-  const long o = h->nws - n, ntot = h->nws;
-  if (n > 0) {
-    hipcub::CountingInputIterator<long> cells(0);
-    long *dsel = nullptr;
-    HCHECK(h, hipMalloc(&dsel, sizeof(long)));
-    size_t tmp_bytes = 0;
-    HCHECK(h, hipcub::DeviceSelect::If(nullptr, tmp_bytes, cells, h->dws_idx + o, dsel, g.ncell, m, h->stream));
-    void *tmp = nullptr;
-    HCHECK(h, hipMalloc(&tmp, tmp_bytes));
-    HCHECK(h, hipcub::DeviceSelect::If(tmp, tmp_bytes, cells, h->dws_idx + o, dsel, g.ncell, m, h->stream));
-    long nsel = 0;
-    HCHECK(h, hipMemcpyAsync(&nsel, dsel, sizeof nsel, hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    hipFree(tmp);
-    hipFree(dsel);
-    if (nsel != n) {
-      h->err = "wind source: membership count and compaction disagree";
-      return PION_GPU_EDEVICE;
-    }
-    hipLaunchKernelGGL(k_wind_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, m, h->dws_idx + o,
-                       n, h->dws_dist + o, h->dws_off + o, h->dws_theta + o, ntot, h->dflags);
-  }
-  HCHECK(h, hipGetLastError());
-  HCHECK(h, hipStreamSynchronize(h->stream));
-  W.off = o;
-  W.n = n;
-  h->wsrc.push_back(W);
-  state_changed(h);   // the ISBD flags decide which cells enter the time-step reduction
-  if (id) *id = (int)h->wsrc.size() - 1;
-  return 0;
-}
-
 // On-grid cells of planes [plane_lo, plane_lo + planes) of the slab axis <-> a contiguous buffer
 // [nvar][planes][rows][nx] (pion_gpu_pack_ongrid / _unpack_ongrid).  A plane of the slab axis is `rows` runs of nx
 // on-grid cells (3-D: the ny rows of an x-y plane; 2-D: one row; 1-D: the one row there is).  A pure copy, bound by
@@ -1135,15 +546,6 @@ int ongrid_go(Handle *h, double *A0, double *A1, int plane_lo, int plane_hi, voi
   HCHECK(h, hipGetLastError());
   return 0;
 }
-
-// device scratch of the test seams: freed on every return path
-struct DevBuf {
-  double *p = nullptr;
-  ~DevBuf()
-  {
-    if (p) (void)hipFree(p);
-  }
-};
 
 }  // namespace
 
@@ -1406,17 +808,7 @@ void pion_gpu_destroy(void *handle)
   hipFree(h->derr);
   hipFree(h->ddt);
   hipFree(h->ddt_init);
-  hipFree(h->dwind_idx);
-  hipFree(h->dwind_state);
-  hipFree(h->dws_idx);
-  hipFree(h->dws_dist);
-  hipFree(h->dws_off);
-  hipFree(h->dws_state);
-  hipFree(h->dws_theta);
-  for (WindSource &W : h->wsrc) {
-    hipFree(W.dn);
-    hipFree(W.dscan);
-  }
+  wind_free(h);
   hipFree(h->djet_idx);
   hipFree(h->djet_state);
   hipFree(h->dcoolT);
@@ -1545,262 +937,6 @@ int pion_gpu_synchronize(void *handle)
   return 0;
 }
 
-int pion_gpu_set_wind_cells(void *handle, long n, const long *idx, const double *states)
-{
-  Handle *h = use(handle);
-  state_changed(h);   // the ISBD flags decide which cells enter the time-step reduction
-  hipFree(h->dwind_idx);
-  hipFree(h->dwind_state);
-  h->dwind_idx = nullptr;
-  h->dwind_state = nullptr;
-  h->nwind = n;
-  if (n > 0) {
-    for (long k = 0; k < n; k++) {
-      if (idx[k] < 0 || idx[k] >= h->g.ncell) {
-        h->nwind = 0;
-        return PION_GPU_EINVAL;
-      }
-    }
-    HCHECK(h, hipMalloc(&h->dwind_idx, sizeof(long) * n));
-    HCHECK(h, hipMalloc(&h->dwind_state, sizeof(double) * n * h->cfg.nvar));
-    HCHECK(h, hipMemcpy(h->dwind_idx, idx, sizeof(long) * n, hipMemcpyHostToDevice));
-    HCHECK(h, hipMemcpy(h->dwind_state, states, sizeof(double) * n * h->cfg.nvar, hipMemcpyHostToDevice));
-    // isbd = true, isdomain = false (stellar_wind_BC.cpp:277-278), on the device: the flags there are the only
-    // current ones once a wind source has moved
-    hipLaunchKernelGGL(k_flag_wind_list, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->dwind_idx, n,
-                       h->dflags);
-    HCHECK(h, hipGetLastError());
-    HCHECK(h, hipStreamSynchronize(h->stream));
-  }
-  return 0;
-}
-
-int pion_gpu_add_wind_source(void *handle, const pion_gpu_wind_source *src, int *id)
-{
-  Handle *h = use(handle);
-  if (!h || !src) return PION_GPU_EINVAL;
-  const pion_gpu_config &cfg = h->cfg;
-  const GridDesc &g = h->g;
-  auto fail = [&](const char *m) {
-    h->err = m;
-    return PION_GPU_EINVAL;
-  };
-  // the reference's rep.error conditions (stellar_wind_BC.cpp:140-217, :331-360, :1140-1145, :517-519)
-  if (h->wsrc.size() >= PION_MAX_WIND_SOURCES) return fail("wind source: at most PION_MAX_WIND_SOURCES sources");
-  if (src->type == 2 || src->type == 3) return fail("wind source: angle / latitude-dependent winds are not supported");
-  if (src->type != 0 && src->type != 1) return fail("What type of source is this?  add a new type?");
-  // a divergence: in the reference's stellar_wind_angle object an evolving source would get LGM99 updates
-  if (src->type == 1)
-    for (const WindSource &o : h->wsrc)
-      if (o.type == 2) return fail("wind source: evolving and rotating sources cannot share a grid");
-  if (!(src->radius > 0.0)) return fail("wind source: radius must be > 0");
-  if (cfg.coord_sys == 3 && !equalD(src->pos[0], 0.0)) return fail("Spherical symmetry but source not at origin!");
-  if (cfg.coord_sys == 2 && cfg.ndim == 2 && !equalD(src->pos[1], 0.0))
-    return fail("Axisymmetry but source not at R=0!");
-  if (cfg.ndim == 1 && cfg.eqntype != PION_EQEUL) return fail("1D spherical but MHD?");
-  // a divergence: the reference would move a source on the axis (cylindrical) or at the origin (spherical) off it
-  if (src->orbit_period != 0 && (cfg.ndim < 2 || cfg.coord_sys != 1))
-    return fail("wind source: orbital motion needs a 2-D or 3-D Cartesian grid");
-  if (src->type == 1) {
-    if (src->npt < 2) return fail("evolving wind source: the table needs at least 2 rows");
-    if (!src->evo_time || !src->evo_Teff || !src->evo_Mdot || !src->evo_vrot || !src->evo_vinf || !src->evo_R)
-      return fail("evolving wind source: missing table column");
-    for (int v = 0; v < cfg.ntracer; v++) {
-      const int e = src->evo_tracer_elem[v];
-      if (e < -1 || e > 6 || (e >= 0 && !src->evo_X[e])) return fail("evolving wind source: bad tracer selector");
-    }
-  }
-  WindSource W;
-  W.type = src->type;
-  for (int a = 0; a < 3; a++) W.pos[a] = (a < cfg.ndim) ? src->pos[a] : 0.0;
-  W.radius = src->radius;
-  W.Bstar = src->Bstar;
-  for (int v = 0; v < PION_MAX_NVAR; v++) {
-    W.tr[v] = (v < cfg.ntracer) ? src->tracers[v] : 0.0;
-    W.elem[v] = (src->type == 1 && v < cfg.ntracer) ? src->evo_tracer_elem[v] : -1;
-  }
-  double mdot = src->mdot, vinf = src->vinf, vrot = src->vrot, Tw = src->Tw, Rstar = src->Rstar;
-  if (src->type == 1) {
-    // add_evolving_source (:1109-1245): the source is active at set-up if it starts within one update interval
-    const int n = src->npt;
-    W.t.assign(src->evo_time, src->evo_time + n);
-    W.Teff.assign(src->evo_Teff, src->evo_Teff + n);
-    W.Mdot.assign(src->evo_Mdot, src->evo_Mdot + n);
-    W.vrot.assign(src->evo_vrot, src->evo_vrot + n);
-    W.vinf.assign(src->evo_vinf, src->evo_vinf + n);
-    W.R.assign(src->evo_R, src->evo_R + n);
-    for (int e = 0; e < 7; e++)
-      if (src->evo_X[e]) W.X[e].assign(src->evo_X[e], src->evo_X[e] + n);
-    W.tstart = W.t[0];
-    W.tfinish = W.t[n - 1];
-    const double t_now = src->t_now;
-    W.t_next_update = std::max(W.tstart, t_now);
-    double x[7] = {0, 0, 0, 0, 0, 0, 0};
-    if (((t_now + src->update_freq) > W.tstart || equalD(W.tstart, t_now)) && t_now < W.tfinish) {
-      W.active = true;
-      Tw = root_find_linear_vec(W.t, W.Teff, t_now);
-      mdot = root_find_linear_vec(W.t, W.Mdot, t_now);
-      vinf = root_find_linear_vec(W.t, W.vinf, t_now);
-      vrot = root_find_linear_vec(W.t, W.vrot, t_now);
-      Rstar = root_find_linear_vec(W.t, W.R, t_now);
-      for (int e = 0; e < 7; e++)
-        if (!W.X[e].empty()) x[e] = root_find_linear_vec(W.t, W.X[e], t_now);
-    }
-    else {
-      W.active = false;
-      mdot = -100.0;
-      vinf = -100.0;
-      Tw = -100.0;
-      vrot = 0.0;
-      Rstar = 0.0;
-    }
-    for (int v = 0; v < cfg.ntracer; v++)
-      if (W.elem[v] >= 0) W.tr[v] = x[W.elem[v]];
-  }
-  // stellar_wind::add_source (:166-176): Msun/yr and km/s to cgs (for an evolving source the table values, already
-  // cgs, pass through this conversion too; update_source overwrites them at the first update)
-  W.Mdot_c = mdot * 1.9891e33 / 3.1558150e7;
-  W.Vinf_c = vinf * 1.0e5;
-  W.vrot_c = vrot * 1.0e5;
-  W.Tw_c = Tw;
-  W.Rstar_c = Rstar;
-
-  if (src->orbit_period != 0) {
-    W.moving = true;
-    W.orbit = *src;
-    for (int a = 0; a < 3; a++) W.orbit.pos[a] = W.pos[a];   // dpos_init
-    return add_moving_wind_source(h, W, id);
-  }
-
-  return add_fixed_wind_source(h, W, id);
-}
-
-int pion_gpu_add_rotating_wind_source(void *handle, const pion_gpu_wind_source *src, const double *evo_vcrit,
-                                      double xi, int *id)
-{
-  Handle *h = use(handle);
-  if (!h || !src) return PION_GPU_EINVAL;
-  const pion_gpu_config &cfg = h->cfg;
-  auto fail = [&](const char *m) {
-    h->err = m;
-    return PION_GPU_EINVAL;
-  };
-  // the reference's rep.error conditions (stellar_wind_angle.cpp:714-716, :912-923; tools/interpolate.cpp:420-440)
-  // and the limits of this path
-  if (h->wsrc.size() >= PION_MAX_WIND_SOURCES) return fail("wind source: at most PION_MAX_WIND_SOURCES sources");
-  if (src->type != 2) return fail("Bad wind type for evolving stellar wind (rotating star)!");
-  if (cfg.ndim < 2) return fail("rotating wind source: needs a 2-D or 3-D grid (theta = 0 in 1-D)");
-  if (cfg.coord_sys == 2 && !equalD(src->pos[1], 0.0)) return fail("Axisymmetry but source not at R=0!");
-  if (src->orbit_period != 0) return fail("rotating wind source: add_rotating_source takes no orbit");
-  if (!(src->radius > 0.0)) return fail("wind source: radius must be > 0");
-  if (src->npt < 2) return fail("evolving wind source: the table needs at least 2 rows");
-  if (!src->evo_time || !src->evo_Teff || !src->evo_Mdot || !src->evo_vrot || !src->evo_vinf || !src->evo_R ||
-      !evo_vcrit)
-    return fail("evolving wind source: missing table column");
-  for (int v = 0; v < cfg.ntracer; v++) {
-    const int e = src->evo_tracer_elem[v];
-    if (e < -1 || e > 6 || (e >= 0 && !src->evo_X[e])) return fail("evolving wind source: bad tracer selector");
-  }
-  for (const WindSource &o : h->wsrc) {
-    if (o.type == 1) return fail("wind source: evolving and rotating sources cannot share a grid");
-    // stellar_wind_angle holds one c_xi (the reference's errorTest on WIND_i_xi)
-    if (o.type == 2 && !(xi == h->angle.xi)) return fail("rotating wind source: xi differs from an earlier source's");
-  }
-  if (!h->have_angle || !(xi == h->angle.xi)) {
-    lgm99::setup_tables(xi, h->angle);
-    h->have_angle = true;
-  }
-  const AngleTables &T = h->angle;
-  WindSource W;
-  W.type = 2;
-  for (int a = 0; a < 3; a++) W.pos[a] = (a < cfg.ndim) ? src->pos[a] : 0.0;
-  W.radius = src->radius;
-  W.Bstar = src->Bstar;
-  for (int v = 0; v < PION_MAX_NVAR; v++) {
-    W.tr[v] = (v < cfg.ntracer) ? src->tracers[v] : 0.0;
-    W.elem[v] = (v < cfg.ntracer) ? src->evo_tracer_elem[v] : -1;
-  }
-  // theta of every member cell within (theta_vec[0], theta_vec[24]], counted on the device before anything changes
-  {
-    const WindMember m = wind_member(h, W);
-    unsigned long long *dcount = nullptr, cnt = 0;
-    HCHECK(h, hipMalloc(&dcount, sizeof(unsigned long long)));
-    HCHECK(h, hipMemsetAsync(dcount, 0, sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(k_wind_theta_bad, dim3((unsigned)((h->g.ncell + 255) / 256)), dim3(256), 0, h->stream, m,
-                       T.theta[0], T.theta[PION_ANGLE_NTHETA - 1], dcount);
-    HCHECK(h, hipGetLastError());
-    HCHECK(h, hipMemcpyAsync(&cnt, dcount, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    hipFree(dcount);
-    if (cnt > 0) return fail("rotating wind source: a member cell's theta lies outside the LGM99 table");
-  }
-  // add_evolving_source (stellar_wind_angle.cpp:700-827) + add_rotating_source (:836-932): all values cgs
-  const int n = src->npt;
-  W.t.assign(src->evo_time, src->evo_time + n);
-  W.Teff.assign(src->evo_Teff, src->evo_Teff + n);
-  W.Mdot.assign(src->evo_Mdot, src->evo_Mdot + n);
-  W.vrot.assign(src->evo_vrot, src->evo_vrot + n);
-  W.vinf.assign(src->evo_vinf, src->evo_vinf + n);
-  W.vcrit.assign(evo_vcrit, evo_vcrit + n);
-  W.R.assign(src->evo_R, src->evo_R + n);
-  for (int e = 0; e < 7; e++)
-    if (src->evo_X[e]) W.X[e].assign(src->evo_X[e], src->evo_X[e] + n);
-  W.tstart = W.t[0];
-  W.tfinish = W.t[n - 1];
-  const double t_now = src->t_now;
-  W.t_next_update = std::max(W.tstart, t_now);
-  double mdot = 0.0, vinf = 0.0, Twind = 0.0, vrot = 0.0, rstar = 0.0, vcrt = 0.0;
-  double x[7] = {0, 0, 0, 0, 0, 0, 0};
-  if (((t_now + src->update_freq) > W.tstart || equalD(W.tstart, t_now)) && t_now < W.tfinish) {
-    W.active = true;
-    Twind = root_find_linear_vec(W.t, W.Teff, t_now);
-    mdot = root_find_linear_vec(W.t, W.Mdot, t_now);
-    vinf = root_find_linear_vec(W.t, W.vinf, t_now);
-    vrot = root_find_linear_vec(W.t, W.vrot, t_now);
-    vcrt = root_find_linear_vec(W.t, W.vcrit, t_now);
-    rstar = root_find_linear_vec(W.t, W.R, t_now);
-    for (int e = 0; e < 7; e++)
-      if (!W.X[e].empty()) x[e] = root_find_linear_vec(W.t, W.X[e], t_now);
-  }
-  else {
-    W.active = false;
-    mdot = -100.0;
-    vinf = -100.0;
-    vrot = -100.0;
-    Twind = -100.0;
-  }
-  for (int v = 0; v < cfg.ntracer; v++)
-    if (W.elem[v] >= 0) W.tr[v] = x[W.elem[v]];
-  const double Tmax = T.Teff[PION_ANGLE_NTEFF - 1];
-  W.Mdot_c = mdot;
-  W.Vinf_c = vinf;
-  W.vrot_c = vrot;
-  W.vcrit_c = vcrt;
-  W.Tw_c = (Tmax < Twind) ? Tmax : Twind;   // std::min(Twind, Teff_vec.back())
-  W.Rstar_c = rstar;
-  return add_fixed_wind_source(h, W, id);
-}
-
-int pion_gpu_wind_angle_tables(double xi, double *theta, double *omega, double *Teff, double *delta, double *alpha)
-{
-  AngleTables T;
-  lgm99::setup_tables(xi, T);
-  if (theta) memcpy(theta, T.theta, sizeof T.theta);
-  if (omega) memcpy(omega, T.omega, sizeof T.omega);
-  if (Teff) memcpy(Teff, T.Teff, sizeof T.Teff);
-  if (delta) memcpy(delta, T.delta.data(), sizeof(double) * T.delta.size());
-  if (alpha) memcpy(alpha, T.alpha.data(), sizeof(double) * T.alpha.size());
-  return 0;
-}
-
-int pion_gpu_get_wind_source_pos(void *handle, int id, double *pos)
-{
-  Handle *h = use(handle);
-  if (!h || !pos || id < 0 || id >= (int)h->wsrc.size()) return PION_GPU_EINVAL;
-  for (int a = 0; a < PION_MAX_DIM; a++) pos[a] = (a < 3) ? h->wsrc[id].pos[a] : 0.0;
-  return 0;
-}
-
 int pion_gpu_get_flags(void *handle, unsigned char *out)
 {
   Handle *h = use(handle);
@@ -1829,40 +965,6 @@ int pion_gpu_get_hll_screen_counts(void *handle, int *active, int *total)
   HCHECK(h, hipMemcpyAsync(active, h->dscr_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HCHECK(h, hipStreamSynchronize(h->stream));
   *total = (int)scr_total(h->scr);
-  return 0;
-}
-
-int pion_gpu_wind_orbit_position(const pion_gpu_wind_source *src, int ndim, double simtime, double *pos)
-{
-  if (!src || !pos || ndim < 2 || ndim > 3) return PION_GPU_EINVAL;
-  double p[3];
-  wind_orbit_position(*src, ndim, simtime, p);
-  for (int a = 0; a < PION_MAX_DIM; a++) pos[a] = (a < 3) ? p[a] : 0.0;
-  return 0;
-}
-
-int pion_gpu_get_wind_cells(void *handle, int id, long *n, long *idx, double *states)
-{
-  Handle *h = use(handle);
-  if (!h || !n || id < 0 || id >= (int)h->wsrc.size()) return PION_GPU_EINVAL;
-  const WindSource &W = h->wsrc[id];
-  long cnt = W.n;
-  if (W.moving) {
-    // the count the last move left on the device
-    HCHECK(h, hipMemcpyAsync(&cnt, W.dn, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    if (cnt < 0 || cnt > W.n) {
-      h->err = "wind source: device cell count out of range";
-      return PION_GPU_EDEVICE;
-    }
-  }
-  *n = cnt;
-  if (!idx || cnt == 0) return 0;
-  HCHECK(h, hipMemcpyAsync(idx, h->dws_idx + W.off, sizeof(long) * cnt, hipMemcpyDeviceToHost, h->stream));
-  if (states)
-    HCHECK(h, hipMemcpyAsync(states, h->dws_state + W.off * h->cfg.nvar, sizeof(double) * cnt * h->cfg.nvar,
-                             hipMemcpyDeviceToHost, h->stream));
-  HCHECK(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -2134,7 +1236,7 @@ int pion_gpu_interface_flux(void *handle, int n, int axis, double dt, const doub
 {
   Handle *h = use(handle);
   const int nv = h->cfg.nvar;
-  DevBuf bl, br, ba, bf, bp;
+  DevBuf<double> bl, br, ba, bf, bp;
   const size_t nb = sizeof(double) * (size_t)n * nv;
   HCHECK(h, hipMalloc(&bl.p, nb));
   HCHECK(h, hipMalloc(&br.p, nb));
@@ -2187,7 +1289,7 @@ static int cool_go(Handle *h, int n, double dt, const double *Pin, double *Pout,
   a.gamma = h->cfg.gamma;
   a.errword = h->derr;
   a.cool = h->cool;
-  DevBuf b0, b1, b2;
+  DevBuf<double> b0, b1, b2;
   double *&d0 = b0.p, *&d1 = b1.p, *&d2 = b2.p;
   int rc;
   if (Pin) {

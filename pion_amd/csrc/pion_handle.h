@@ -1,5 +1,6 @@
 // pion_handle.h -- shared by the translation units of the C-ABI layer: the handle behind include/pion_gpu.h's opaque
-// pointer and the helpers every entry point uses (defined in pion_gpu.hip, used there and in pion_step.hip).
+// pointer and the helpers every entry point uses (defined in pion_gpu.hip, used there, in pion_step.hip and in
+// pion_wind.hip).
 #ifndef PION_HANDLE_H
 #define PION_HANDLE_H
 
@@ -8,45 +9,9 @@
 
 #include "../../include/pion_gpu.h"
 #include "kernels.h"
+#include "wind_host.h"
 
 namespace pion::impl {
-
-// The knots of the LGM99 tables: dev_wind.h's PION_ANGLE_*.  That header defines kernels, so only pion_gpu.hip includes
-// it, and asserts there that these are its values.
-constexpr int ANGLE_NTHETA = 25, ANGLE_NOMEGA = 25, ANGLE_NTEFF = 22;
-
-// stellar_wind_angle's look-up tables for one xi (setup_tables, grid/stellar_wind_angle.cpp:92-212)
-struct AngleTables {
-  double xi = 0.0;
-  double theta[ANGLE_NTHETA], omega[ANGLE_NOMEGA], Teff[ANGLE_NTEFF];
-  std::vector<double> delta;   // [omega][Teff]
-  std::vector<double> alpha;   // [omega][theta][Teff]
-};
-
-// one pion_gpu_add_wind_source source: its table, the parameters the next boundary update writes with, and the
-// activity bookkeeping of stellar_wind_evolution (evolving_wind_data: tstart, tfinish, t_next_update, is_active)
-struct WindSource {
-  int type = 0;
-  double pos[3] = {0.0, 0.0, 0.0};
-  double radius = 0.0, Bstar = 0.0;
-  std::vector<double> t, Teff, Mdot, vrot, vinf, R, X[7];
-  std::vector<double> vcrit;   // rotating source (type 2): the vcrit column
-  int elem[PION_MAX_NVAR];
-  double Mdot_c = 0.0, Vinf_c = 0.0, vrot_c = 0.0, Tw_c = 0.0, Rstar_c = 0.0;   // wind_source members, cgs
-  double vcrit_c = 0.0;
-  double tr[PION_MAX_NVAR];
-  bool active = true;
-  double tstart = 0.0, tfinish = 0.0, t_next_update = 1.0e99;
-  long off = 0, n = 0;   // range in the concatenated cell list (moving source: n = its capacity, the box size)
-  // orbital motion (orbit_period != 0): the position at set-up (dpos_init), the orbit, the box the cells are found
-  // in, the device count the compaction writes, and the compaction's scratch (all sized at set-up)
-  bool moving = false;
-  pion_gpu_wind_source orbit;   // pos = dpos_init, orbit_* (the pointers are not used)
-  int box_w[3] = {1, 1, 1};
-  long *dn = nullptr;
-  void *dscan = nullptr;
-  size_t scan_bytes = 0;
-};
 
 struct Handle {
   pion_gpu_config cfg;
@@ -178,6 +143,19 @@ static inline bool mp_dt_limited(const pion_gpu_config &cfg)
 {
   return cfg.cooling != 0 && cfg.mp_timestep_limit >= 1 && cfg.mp_timestep_limit <= 3;
 }
+
+// device scratch of one call: freed on every return path
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// The wind sources (pion_wind.hip) as pion_gpu_update_bcs and pion_gpu_destroy need them: EINVAL if a rotating source
+// cannot be evaluated at simtime (before anything is written), the sources' part of the update, their memory freed
+int wind_angle_check(Handle *h, double simtime);
+int wind_sources_update(Handle *h, double simtime);
+void wind_free(Handle *h);
 
 // legacy wind list or wind sources present: the stage kernels read the cell flags, and the periodic ghost images
 // are not fused into one launch

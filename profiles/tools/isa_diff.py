@@ -2,12 +2,15 @@
 """Device ISA of kernels_fp.hip at a git revision against the working tree, both floating-point builds and every
 equation set (no GPU needed):  profiles/tools/isa_diff.py [REV=HEAD] [-j JOBS]
 Compiles with the library's flags plus --cuda-device-only -S (as probe_regs.sh does) and compares every function body
-and kernel descriptor with labels and symbol names stripped.  Exit status 1 if any function differs."""
+and kernel descriptor with labels and symbol names stripped.  Exit status 1 if any function differs.
+--abi: the C-ABI layer instead, every pion_*.hip each tree has, its functions pooled and matched by demangled name
+(a kernel may have moved to another file; those of an anonymous namespace then change their mangled name)."""
 import argparse
 import os
 import re
 import subprocess
 import sys
+import glob
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
@@ -38,16 +41,50 @@ def functions(path):
     return out
 
 
+def abi_layer(trees, tmp, jobs_n):
+    """{tag: {demangled name: body or descriptor}} over the pion_*.hip of each tree; then the comparison"""
+    jobs, outs = [], {}
+    for tag, tree in trees:
+        for src in sorted(glob.glob(os.path.join(tree, "pion_amd", "csrc", "pion_*.hip"))):
+            out = os.path.join(tmp, "%s_%s.s" % (tag, os.path.basename(src)))
+            outs.setdefault(tag, []).append(out)
+            jobs.append([HIPCC] + COMMON + [src, "-o", out])
+    with ThreadPoolExecutor(jobs_n) as ex:
+        if any(ex.map(lambda c: subprocess.run(c).returncode, jobs)):
+            sys.exit("compile failed")
+    pooled = {}
+    for tag, files in outs.items():
+        fns = {}
+        for f in files:
+            fns.update(functions(f))
+        names = sorted(fns)
+        plain = subprocess.run(["c++filt"], input="\n".join(n.split("#")[0] for n in names), capture_output=True,
+                               text=True, check=True).stdout.split("\n")
+        pooled[tag] = {d + ("#descriptor" if n.endswith("#descriptor") else ""): fns[n] for n, d in zip(names, plain)}
+        assert len(pooled[tag]) == len(names), "two functions of one demangled name"
+    a, b = pooled["base"], pooled["tree"]
+    diff = [k for k in sorted(set(a) | set(b)) if a.get(k) != b.get(k)]
+    print("C-ABI layer, %s -> %s: functions and descriptors compared: %d, different: %d" % (
+        [os.path.basename(f)[5:-2] for f in outs["base"]], [os.path.basename(f)[5:-2] for f in outs["tree"]],
+        len(set(a) | set(b)), len(diff)))
+    for d in diff:
+        print("DIFF", d, "(only in %s)" % ("tree" if d not in a else "base") if (d in a) != (d in b) else "")
+    return 1 if diff else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("rev", nargs="?", default="HEAD")
     ap.add_argument("-j", type=int, default=8)
+    ap.add_argument("--abi", action="store_true")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         base = os.path.join(tmp, "base")
         os.makedirs(base)
         tar = subprocess.check_output(["git", "-C", HERE, "archive", args.rev, "pion_amd/csrc", "include"])
         subprocess.run(["tar", "-x", "-C", base], input=tar, check=True)
+        if args.abi:
+            return abi_layer((("base", base), ("tree", HERE)), tmp, args.j)
         jobs = []
         for tree, tag in ((base, "base"), (HERE, "tree")):
             for mode, flags in MODES.items():
