@@ -1,4 +1,4 @@
-// kernels.h -- launch interface between the C-ABI layer (pion_gpu.hip, pion_step.hip) and the
+// kernels.h -- launch interface between the C-ABI layer (pion_gpu.hip, pion_step.hip, pion_bc.hip) and the
 // floating-point kernels (kernels_fp.hip).  kernels_fp.hip is compiled twice,
 // once per floating-point mode, into namespaces pion::fp_strict (-ffp-contract=off:
 // bit-parity with the reference's x86-64 -O3 build) and pion::fp_fast (FMA
@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "dev_riemann.h"
+#include "grid_desc.h"
 #include "rows_tiling.h"
 #include "hll_screen.h"
 
@@ -17,17 +18,6 @@ namespace pion {
 
 #define PION_MAX_NTR 2
 #define PION_COOL_NT_MAX 256
-
-struct GridDesc {
-  int ndim;
-  int ng[3], nbc[3], nga[3];
-  long ncell;   // cells incl. ghosts
-  long sy, sz;  // strides of y and z in cells
-  double dx;
-  double xmin[3];
-  int cyl;      // 1: cylindrical (z,R) axisymmetry, axis 1 = R (2-D only); 2: spherical symmetry, axis 0 = R (1-D)
-  const double *sph_vol;  // spherical: (rp^3 - rn^3)/3 per all-cell x index, evaluated on the host (libm pow)
-};
 
 struct CoolDev {
   int NT;

@@ -1,9 +1,9 @@
 // pion_gpu.hip -- implementation of the C-ABI declared in include/pion_gpu.h.
 //
-// Host side of the boundary: owns device memory behind an opaque handle (pion_handle.h): set-up and tear-down,
-// uploads, jet, cooling tables, the test seams and timing, and the data-movement kernels of the boundary update, which
-// have no arithmetic: ghost-cell fills (boundaries/*.cpp of the reference), the cell reset of the legacy wind list and
-// the jet.  What a time step calls is pion_step.hip; the stellar-wind sources are pion_wind.hip and wind_host.cpp.
+// Owns device memory behind an opaque handle (pion_handle.h): set-up and tear-down, uploads and the on-grid pack
+// kernels, cooling tables, the test seams and timing.  What a time step calls is pion_step.hip; the boundary update
+// (ghost-cell fills, jet) is pion_bc.hip with the rules in dev_bc.h; the stellar-wind sources are pion_wind.hip and
+// wind_host.cpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -80,386 +80,6 @@ int impl::check_errword(Handle *h)
 }
 
 namespace {
-
-struct BCArgs {
-  GridDesc g;
-  double *T;        // array whose ghosts are filled (sources are read from the same array)
-  int nvar, dir, type, eqntype, ntracer;
-  double refval[PION_MAX_NVAR];
-  double dmr_a0, dmr_t3;  // 10*simtime/sin(pi/3), tan(pi/3)  (host libm, as the reference)
-};
-
-// All periodic faces of a grid in ONE launch (the bench configuration).  The X -> Y -> Z sequence of
-// periodic copies (periodic_boundaries.cpp:42-50, corner cells through already filled ghosts) ends with
-// every ghost cell holding the on-grid cell at its coordinates wrapped axis by axis, so the wrapped
-// cell can be read directly: the same values, one launch instead of six.  z faces of kind SLAB
-// (neighbour rank) are left alone: then only ghosts on on-grid z planes are filled.  (A 2-D grid with SLAB y faces
-// goes through k_bc_all.)
-__global__ __launch_bounds__(256) void k_bc_periodic_all(double *T, const GridDesc g, const int nvar, const int zwrap,
-                                                         const int skipx)
-{
-  // ghost cells as three disjoint slabs: A = z ghosts (all x,y), B = y ghosts on on-grid z (all x),
-  // C = x ghosts on on-grid y and z
-  const long nA = zwrap ? (long)2 * g.nbc[2] * g.nga[0] * g.nga[1] : 0;
-  const long nB = (long)g.ng[2] * 2 * g.nbc[1] * g.nga[0];
-  // (skipx: the stage kernel has already written the x ghosts of the on-grid rows, slab C)
-  const long nC = skipx ? 0 : (long)g.ng[2] * g.ng[1] * 2 * g.nbc[0];
-  long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nA + nB + nC) return;
-  int i0, i1, i2;  // all-cell coordinates (ghosts included)
-  if (t < nA) {
-    i0 = (int)(t % g.nga[0]);
-    i1 = (int)((t / g.nga[0]) % g.nga[1]);
-    const int kz = (int)(t / ((long)g.nga[0] * g.nga[1]));
-    i2 = (kz < g.nbc[2]) ? kz : g.ng[2] + kz;
-  }
-  else if (t < nA + nB) {
-    t -= nA;
-    i0 = (int)(t % g.nga[0]);
-    const int ky = (int)((t / g.nga[0]) % (2 * g.nbc[1]));
-    i1 = (ky < g.nbc[1]) ? ky : g.ng[1] + ky;
-    i2 = (int)(t / ((long)g.nga[0] * 2 * g.nbc[1])) + g.nbc[2];
-  }
-  else {
-    t -= nA + nB;
-    const int kx = (int)(t % (2 * g.nbc[0]));
-    i0 = (kx < g.nbc[0]) ? kx : g.ng[0] + kx;
-    i1 = (int)((t / (2 * g.nbc[0])) % g.ng[1]) + g.nbc[1];
-    i2 = (int)(t / ((long)2 * g.nbc[0] * g.ng[1])) + g.nbc[2];
-  }
-  // wrap each coordinate back onto the grid
-  int s0 = i0, s1 = i1, s2 = i2;
-  if (s0 < g.nbc[0]) s0 += g.ng[0];
-  else if (s0 >= g.nbc[0] + g.ng[0]) s0 -= g.ng[0];
-  if (s1 < g.nbc[1]) s1 += g.ng[1];
-  else if (s1 >= g.nbc[1] + g.ng[1]) s1 -= g.ng[1];
-  if (zwrap) {
-    if (s2 < g.nbc[2]) s2 += g.ng[2];
-    else if (s2 >= g.nbc[2] + g.ng[2]) s2 -= g.ng[2];
-  }
-  const long c = (long)i0 + g.sy * i1 + g.sz * i2, sc = (long)s0 + g.sy * s1 + g.sz * s2;
-  for (int v = 0; v < nvar; v++) T[v * g.ncell + c] = T[v * g.ncell + sc];
-}
-
-// Every external face of a grid in ONE launch, any mix of boundary types (what k_bc_periodic_all does for the
-// all-periodic case).  The reference updates the faces one after the other in list order XN, XP, YN, YP, ZN, ZP
-// (assign_update_bcs.cpp:185-252); a ghost cell belongs to the list of the HIGHEST axis along which it is a
-// ghost (X lists hold on-grid (y,z) rows, Y lists the full x extent, Z lists the full x-y extent,
-// uniform_grid.cpp:1009-1216), and a corner ghost takes its value from a ghost cell that a lower axis's update has
-// just filled.  That chain of copies always ends on an on-grid cell (or on a constant state), which no boundary
-// update writes: so each thread walks the chain of ITS ghost cell down the axes, reads the terminal cell, and
-// applies the per-face operations (sign flips, one-way clamp, psi rule) on the way back up, lowest axis first --
-// the same values as the six launches, without their ordering.  psi of GLM-MHD follows its own chain: outflow
-// and one-way faces take -psi of the MIRROR cell (outflow_boundaries.cpp:140-152), everything else of the copy
-// source.  Then the internal DMR2 boundary, which the reference applies last (double_Mach_ref_boundaries.cpp:98-147).
-// Faces of kind SLAB (neighbour rank; the faces of the slab axis, z in 3-D and y in 2-D) are left alone: the x (and, in
-// 3-D, y) ghosts are still filled over the rows / planes the rank owns, so that what it sends carries them.
-struct BCAllArgs {
-  GridDesc g;
-  double *T;
-  int nvar, eqntype, ntracer, ndim;
-  int type[6];
-  double refval[6][PION_MAX_NVAR];
-  double dmr_a0, dmr_t3;
-  int dmr2_cols;              // > 0: internal DMR2 boundary over the first dmr2_cols on-grid columns
-  double dmr2_val[PION_MAX_NVAR];
-};
-
-__global__ __launch_bounds__(256) void k_bc_all(const BCAllArgs a)
-{
-  const GridDesc &g = a.g;
-  const int nd = a.ndim;
-  // ghost cells as three disjoint slabs: A = z ghosts (all x,y), B = y ghosts on on-grid z (all x),
-  // C = x ghosts on on-grid y and z
-  const long nA = (nd == 3) ? (long)2 * g.nbc[2] * g.nga[0] * g.nga[1] : 0;
-  const long nB = (nd >= 2) ? (long)g.ng[2] * 2 * g.nbc[1] * g.nga[0] : 0;
-  const long nC = (long)g.ng[2] * g.ng[1] * 2 * g.nbc[0];
-  long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nA + nB + nC) return;
-  int i[3];   // all-cell coordinates (ghosts included)
-  if (t < nA) {
-    i[0] = (int)(t % g.nga[0]);
-    i[1] = (int)((t / g.nga[0]) % g.nga[1]);
-    const int kz = (int)(t / ((long)g.nga[0] * g.nga[1]));
-    i[2] = (kz < g.nbc[2]) ? kz : g.ng[2] + kz;
-  }
-  else if (t < nA + nB) {
-    t -= nA;
-    i[0] = (int)(t % g.nga[0]);
-    const int ky = (int)((t / g.nga[0]) % (2 * g.nbc[1]));
-    i[1] = (ky < g.nbc[1]) ? ky : g.ng[1] + ky;
-    i[2] = (int)(t / ((long)g.nga[0] * 2 * g.nbc[1])) + g.nbc[2];
-  }
-  else {
-    t -= nA + nB;
-    const int kx = (int)(t % (2 * g.nbc[0]));
-    i[0] = (kx < g.nbc[0]) ? kx : g.ng[0] + kx;
-    i[1] = (int)((t / (2 * g.nbc[0])) % g.ng[1]) + g.nbc[1];
-    i[2] = (int)(t / ((long)2 * g.nbc[0] * g.ng[1])) + g.nbc[2];
-  }
-  const long nc = g.ncell;
-  const long c = (long)i[0] + g.sy * i[1] + g.sz * i[2];
-  const bool mhd = (a.eqntype == EQMHD || a.eqntype == EQGLM);
-  const bool glm = (a.eqntype == EQGLM);
-
-  // ---- down the axes: the chain of source cells (s: all variables but psi; p: psi)
-  int s[3] = {i[0], i[1], i[2]}, p[3] = {i[0], i[1], i[2]};
-  int op_type[3] = {0, 0, 0}, op_pos[3] = {0, 0, 0};
-  int const_ax = -1;   // axis whose face gives a constant / analytic state: the chain ends there
-  bool owned = false;
-  for (int ax = nd - 1; ax >= 0; ax--) {
-    const int lo = g.nbc[ax], hi = g.nbc[ax] + g.ng[ax];
-    if (s[ax] >= lo && s[ax] < hi) continue;   // on-grid along this axis
-    const bool pos = (s[ax] >= hi);
-    const int type = a.type[2 * ax + (pos ? 1 : 0)];
-    // the first ghost axis met is the list this cell belongs to: a SLAB (neighbour rank) or unset face there
-    // means the cell is not ours to fill
-    if (!owned && (type == 0 || type == PION_BC_SLAB)) return;
-    owned = true;
-    op_type[ax] = type;
-    op_pos[ax] = pos ? 1 : 0;
-    const int depth = pos ? s[ax] - hi + 1 : lo - s[ax];   // distance from the grid = -isedge
-    if (type == PION_BC_PERIODIC) {
-      s[ax] += pos ? -g.ng[ax] : g.ng[ax];
-      p[ax] = s[ax];
-    }
-    else if (type == PION_BC_INFLOW || type == PION_BC_FIXED || type == PION_BC_DMACH) {
-      const_ax = ax;
-      break;
-    }
-    else if (type == 0 || type == PION_BC_SLAB) {
-      // (an unset face below the owning axis: the source is that ghost cell as it stands)
-      op_type[ax] = 0;
-      break;
-    }
-    else {
-      // outflow, one-way, reflecting, axisymmetric, jet-reflect: every ghost layer copies the FIRST on-grid cell
-      // of the row (outflow_boundaries.cpp:50-59); psi of an outflow / one-way face: the mirror cell
-      s[ax] = pos ? hi - 1 : lo;
-      if (glm && (type == PION_BC_OUTFLOW || type == PION_BC_ONEWAY_OUT)) p[ax] = pos ? hi - depth : lo + depth - 1;
-      else p[ax] = s[ax];
-    }
-  }
-
-  // ---- the terminal state
-  double val[PION_MAX_NVAR];
-  int from = 0;   // first axis whose operation is applied on the way up
-  if (const_ax >= 0) {
-    const int d = 2 * const_ax + op_pos[const_ax];
-    if (op_type[const_ax] == PION_BC_DMACH) {
-      // double_Mach_ref_boundaries.cpp:168-204, position of the ghost cell of the Y list (x may be a ghost)
-      const int ix = s[0] - g.nbc[0], iy = s[1] - g.nbc[1];
-      const double x = g.xmin[0] + (2 * ix + 1) * (0.5 * g.dx);
-      const double y = g.xmin[1] + (2 * iy + 1) * (0.5 * g.dx);
-      const double bpos = a.dmr_a0 + 1.0 / 6.0 + y / a.dmr_t3;
-      if (x <= bpos) {
-        val[0] = 8.0;
-        val[1] = 116.5;
-        val[2] = 7.14470958;
-        val[3] = -4.125;
-        val[4] = 0.0;
-        for (int v = 5; v < a.nvar; v++) val[v] = 0.0;
-        for (int v = a.nvar - a.ntracer; v < a.nvar; v++) val[v] = 1.0;
-      }
-      else {
-        for (int v = 0; v < a.nvar; v++) val[v] = a.refval[d][v];
-      }
-    }
-    else {
-      for (int v = 0; v < a.nvar; v++) val[v] = a.refval[d][v];
-    }
-    from = const_ax + 1;
-  }
-  else {
-    const long sc = (long)s[0] + g.sy * s[1] + g.sz * s[2];
-    for (int v = 0; v < a.nvar; v++) val[v] = a.T[v * nc + sc];
-    if (glm) {
-      const long pc = (long)p[0] + g.sy * p[1] + g.sz * p[2];
-      if (pc != sc) val[8] = a.T[8 * nc + pc];
-    }
-  }
-
-  // ---- back up: the operations of the faces, lowest axis first (the order the reference applies them in)
-  for (int ax = from; ax < nd; ax++) {
-    const int type = op_type[ax];
-    if (type == PION_BC_REFLECTING) {
-      // reflecting_boundaries.cpp:34-73,131-153: normal velocity (and normal B) flip sign
-      val[2 + ax] = val[2 + ax] * -1.0;
-      if (mhd) val[5 + ax] = val[5 + ax] * -1.0;
-    }
-    else if (type == PION_BC_AXISYMMETRIC) {
-      // axisymmetric_boundaries.cpp:34-52,98-137 (R = 0 axis): the radial and the theta components
-      val[3] = val[3] * -1.0;
-      val[4] = val[4] * -1.0;
-      if (mhd) {
-        val[6] = val[6] * -1.0;
-        val[7] = val[7] * -1.0;
-      }
-    }
-    else if (type == PION_BC_JETREFLECT) {
-      // jetreflect_boundaries.cpp:32-62: v_n and the two tangential field components
-      val[2 + ax] = val[2 + ax] * -1.0;
-      if (mhd)
-        for (int v = 5; v <= 7; v++)
-          if (v != 5 + ax) val[v] = val[v] * -1.0;
-    }
-    else if (type == PION_BC_OUTFLOW || type == PION_BC_ONEWAY_OUT) {
-      if (type == PION_BC_ONEWAY_OUT) {
-        // oneway_out_boundaries.cpp:75-138
-        const double sg = op_pos[ax] ? 1.0 : -1.0;
-        const double x = val[2 + ax] * sg;
-        val[2 + ax] = sg * ((0.0 < x) ? x : 0.0);
-      }
-      if (glm) val[8] = -val[8];   // GLM_NEGATIVE_BOUNDARY (boundaries.h:21)
-    }
-  }
-  // internal DMR2 boundary: y < 0 ghost cells above the first on-grid columns (x <= 1/6) hold a fixed state
-  if (a.dmr2_cols > 0 && i[1] < g.nbc[1] && i[0] >= g.nbc[0] && i[0] < g.nbc[0] + a.dmr2_cols) {
-    for (int v = 0; v < a.nvar; v++) val[v] = a.dmr2_val[v];
-  }
-  for (int v = 0; v < a.nvar; v++) a.T[v * nc + c] = val[v];
-}
-
-// One thread per ghost cell of one face.  List membership follows UniformGrid::SetupBCs
-// (grid/uniform_grid.cpp:1009-1216): X faces hold on-grid (y,z) rows only, Y faces the full x
-// extent, Z faces the full x-y extent, which together with the X->Y->Z launch order fills the
-// corner ghosts as the reference does.
-__global__ __launch_bounds__(256) void k_bc_face(const BCArgs a)
-{
-  const int ax = a.dir / 2;
-  const bool pos = a.dir & 1;
-  int lo[3], n[3];
-  for (int d = 0; d < 3; d++) {
-    if (d == ax) {
-      lo[d] = 0;
-      n[d] = a.g.nbc[ax];
-    }
-    else if (d < ax || d >= a.g.ndim) {
-      lo[d] = -a.g.nbc[d];
-      n[d] = a.g.nga[d];
-    }
-    else {
-      lo[d] = 0;
-      n[d] = a.g.ng[d];
-    }
-  }
-  const long total = (long)n[0] * n[1] * n[2];
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  int i[3];
-  i[0] = (int)(t % n[0]) + lo[0];
-  i[1] = (int)((t / n[0]) % n[1]) + lo[1];
-  i[2] = (int)(t / ((long)n[0] * n[1])) + lo[2];
-  // along the face axis the local index 0..nbc-1 becomes the ghost coordinate
-  const int k = i[ax];
-  const int depth = pos ? k + 1 : a.g.nbc[ax] - k;  // distance from the grid = -isedge
-  i[ax] = pos ? a.g.ng[ax] + k : -a.g.nbc[ax] + k;
-  const long nc = a.g.ncell;
-  const long st = (ax == 0) ? 1 : ((ax == 1) ? a.g.sy : a.g.sz);
-  const long c = (long)(i[0] + a.g.nbc[0]) + a.g.sy * (i[1] + a.g.nbc[1]) + a.g.sz * (i[2] + a.g.nbc[2]);
-  double *T = a.T;
-  switch (a.type) {
-    case PION_BC_PERIODIC: {
-      // periodic_boundaries.cpp:42-50: NG(axis) cells back onto the grid
-      const long s = pos ? c - st * a.g.ng[ax] : c + st * a.g.ng[ax];
-      for (int v = 0; v < a.nvar; v++) T[v * nc + c] = T[v * nc + s];
-      break;
-    }
-    case PION_BC_OUTFLOW:
-    case PION_BC_ONEWAY_OUT:
-    case PION_BC_AXISYMMETRIC:
-    case PION_BC_JETREFLECT:
-    case PION_BC_REFLECTING: {
-      // all ghost layers copy the FIRST on-grid cell of the row (outflow_boundaries.cpp:50-59)
-      const long s = pos ? c - st * depth : c + st * depth;
-      if (a.type == PION_BC_REFLECTING || a.type == PION_BC_AXISYMMETRIC || a.type == PION_BC_JETREFLECT) {
-        // reflecting_boundaries.cpp:34-73,131-153: normal velocity (and normal B) flip sign;
-        // axisymmetric_boundaries.cpp:34-52,98-137 (R = 0 axis): the radial and the theta components do
-        const bool mhd = (a.eqntype == EQMHD || a.eqntype == EQGLM);
-        const bool axi = (a.type == PION_BC_AXISYMMETRIC);
-        for (int v = 0; v < a.nvar; v++) {
-          double r = 1.0;
-          if (axi) {
-            if (v == 3 || v == 4) r = -1.0;
-            if (mhd && (v == 6 || v == 7)) r = -1.0;
-          }
-          else if (a.type == PION_BC_JETREFLECT) {
-            // jetreflect_boundaries.cpp:32-62: v_n and the two tangential field components
-            if (v == 2 + ax) r = -1.0;
-            if (mhd && v >= 5 && v <= 7 && v != 5 + ax) r = -1.0;
-          }
-          else {
-            if (v == 2 + ax) r = -1.0;
-            if (mhd && v == 5 + ax) r = -1.0;
-          }
-          T[v * nc + c] = T[v * nc + s] * r;
-        }
-      }
-      else {
-        for (int v = 0; v < a.nvar; v++) T[v * nc + c] = T[v * nc + s];
-        if (a.type == PION_BC_ONEWAY_OUT) {
-          // oneway_out_boundaries.cpp:75-138
-          const int vn = 2 + ax;
-          const double sg = pos ? 1.0 : -1.0;
-          const double x = T[vn * nc + c] * sg;
-          T[vn * nc + c] = sg * ((0.0 < x) ? x : 0.0);
-        }
-        if (a.eqntype == EQGLM) {
-          // GLM_NEGATIVE_BOUNDARY (boundaries.h:21, outflow_boundaries.cpp:140-152):
-          // psi_ghost(layer d) = -psi(on-grid cell d)
-          const long gsrc = pos ? s - st * (depth - 1) : s + st * (depth - 1);
-          T[8 * nc + c] = -T[8 * nc + gsrc];
-        }
-      }
-      break;
-    }
-    case PION_BC_INFLOW:
-    case PION_BC_FIXED:
-      for (int v = 0; v < a.nvar; v++) T[v * nc + c] = a.refval[v];
-      break;
-    case PION_BC_DMACH: {
-      // double_Mach_ref_boundaries.cpp:168-204
-      const double x = a.g.xmin[0] + (2 * i[0] + 1) * (0.5 * a.g.dx);
-      const double y = a.g.xmin[1] + (2 * i[1] + 1) * (0.5 * a.g.dx);
-      const double bpos = a.dmr_a0 + 1.0 / 6.0 + y / a.dmr_t3;
-      if (x <= bpos) {
-        T[0 * nc + c] = 8.0;
-        T[1 * nc + c] = 116.5;
-        T[2 * nc + c] = 7.14470958;
-        T[3 * nc + c] = -4.125;
-        T[4 * nc + c] = 0.0;
-        for (int v = a.nvar - a.ntracer; v < a.nvar; v++) T[v * nc + c] = 1.0;
-      }
-      else {
-        for (int v = 0; v < a.nvar; v++) T[v * nc + c] = a.refval[v];
-      }
-      break;
-    }
-    default:
-      break;
-  }
-}
-
-// internal DMR2 boundary: y<0 ghost cells above on-grid columns with x<=1/6 get a fixed state
-__global__ void k_bc_dmr2(const BCArgs a, const int ncols)
-{
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const int nb = a.g.nbc[1];
-  if (t >= ncols * nb) return;
-  const int ix = t % ncols, iy = -1 - (t / ncols);
-  const long nc = a.g.ncell;
-  const long c = (long)(ix + a.g.nbc[0]) + a.g.sy * (iy + a.g.nbc[1]);
-  for (int v = 0; v < a.nvar; v++) a.T[v * nc + c] = a.refval[v];
-}
-
-__global__ void k_wind(double *T, const long *idx, const double *states, const long n, const int nvar,
-                       const long nc)
-{
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const long c = idx[t];
-  for (int v = 0; v < nvar; v++) T[v * nc + c] = states[t * nvar + v];
-}
 
 // On-grid cells of planes [plane_lo, plane_lo + planes) of the slab axis <-> a contiguous buffer
 // [nvar][planes][rows][nx] (pion_gpu_pack_ongrid / _unpack_ongrid).  A plane of the slab axis is `rows` runs of nx
@@ -766,19 +386,7 @@ int pion_gpu_create(const pion_gpu_config *cfg, int device, void **handle)
     rv[2] = rv[3] = rv[4] = 0.1 * refvel;
     rv[5] = rv[6] = rv[7] = refB;
   }
-  for (int d = 0; d < 6; d++)
-    for (int v = 0; v < PION_MAX_NVAR; v++) h->refval[d][v] = 0.0;
-
-  // DMR2: on-grid columns with x <= 1/6
-  if (cfg->bc_dmach2) {
-    int n = 0;
-    for (int ix = 0; ix < g.ng[0]; ix++) {
-      const double x = g.xmin[0] + (2 * ix + 1) * (0.5 * g.dx);
-      if (x <= 1. / 6.) n++;
-      else break;
-    }
-    h->dmr2_cols = n;
-  }
+  bc_init(h);
   return PION_GPU_OK;
 }
 
@@ -968,64 +576,6 @@ int pion_gpu_get_hll_screen_counts(void *handle, int *active, int *total)
   return 0;
 }
 
-int pion_gpu_set_jet(void *handle, int jetradius, const double *jetstate)
-{
-  Handle *h = use(handle);
-  state_changed(h);   // (cell flags change)
-  const pion_gpu_config &cfg = h->cfg;
-  const GridDesc &g = h->g;
-  const bool cart3d = (cfg.ndim == 3 && cfg.coord_sys == 1 && cfg.eqntype == PION_EQEUL);
-  const bool cyl2d = (cfg.ndim == 2 && cfg.coord_sys == 2);
-  if ((!cart3d && !cyl2d) || !jetstate) {
-    h->err = "jet boundary: 3-D Cartesian Euler or 2-D cylindrical only (jet_boundaries.cpp:88-91,203-206)";
-    return PION_GPU_EINVAL;
-  }
-  std::vector<long> idx;
-  if (cart3d) {
-    // BC_assign_JETBC, 3-D Cartesian (jet_boundaries.cpp:170-201)
-    const double jr = jetradius * g.dx;
-    for (int iz = 0; iz < g.ng[2]; iz++)
-      for (int iy = 0; iy < g.ng[1]; iy++) {
-        const double y = g.xmin[1] + (2 * iy + 1) * (0.5 * g.dx), z = g.xmin[2] + (2 * iz + 1) * (0.5 * g.dx);
-        if (sqrt(y * y + z * z) <= jr)
-          for (int k = 1; k <= g.nbc[0]; k++) idx.push_back(cell_id(g, -k, iy, iz));
-      }
-  }
-  else {
-    // 2-D axisymmetric (:96-168): the first jetradius rows above the axis; the profile written at
-    // assignment does not survive the first update (:212-262), so the uniform state is all there is
-    if (jetradius > g.ng[1]) {
-      h->err = "Not enough cells for jet";
-      return PION_GPU_EINVAL;
-    }
-    for (int iy = 0; iy < jetradius; iy++)
-      for (int k = 1; k <= g.nbc[0]; k++) idx.push_back(cell_id(g, -k, iy, 0));
-  }
-  // refval (jet_boundaries.cpp:60-93): 2-D MHD keeps B along the axis and the toroidal component
-  std::vector<double> rv(jetstate, jetstate + cfg.nvar);
-  if (cfg.eqntype != PION_EQEUL) {
-    rv[5] = jetstate[5];
-    rv[6] = 0.0;
-    rv[7] = jetstate[6];
-  }
-  hipFree(h->djet_idx);
-  hipFree(h->djet_state);
-  h->djet_idx = nullptr;
-  h->djet_state = nullptr;
-  h->njet = (long)idx.size();
-  // k_wind takes one state per cell
-  std::vector<double> st((size_t)h->njet * cfg.nvar);
-  for (long k = 0; k < h->njet; k++)
-    for (int v = 0; v < cfg.nvar; v++) st[(size_t)k * cfg.nvar + v] = rv[v];
-  if (h->njet > 0) {
-    HCHECK(h, hipMalloc(&h->djet_idx, sizeof(long) * h->njet));
-    HCHECK(h, hipMalloc(&h->djet_state, sizeof(double) * st.size()));
-    HCHECK(h, hipMemcpy(h->djet_idx, idx.data(), sizeof(long) * h->njet, hipMemcpyHostToDevice));
-    HCHECK(h, hipMemcpy(h->djet_state, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice));
-  }
-  return 0;
-}
-
 int pion_gpu_set_cooling_tables(void *handle, int nT, const double *T, const double *tabs, const double *slopes)
 {
   Handle *h = use(handle);
@@ -1069,159 +619,6 @@ int pion_gpu_set_cooling_tables(void *handle, int nT, const double *T, const dou
   h->cool.tab = h->dcooltab;
   h->cool.slope = h->dcoolslope;
   h->have_tables = true;
-  return 0;
-}
-
-int pion_gpu_update_bcs(void *handle, double simtime, int cstep, int maxstep, int assign)
-{
-  Handle *h = use(handle);
-  const pion_gpu_config &cfg = h->cfg;
-  const GridDesc &g = h->g;
-  const bool full = (cstep == maxstep);
-  // after a partial step only Ph's ghosts are refreshed, after the full step P's (and Ph=P)
-  double *T = full ? h->dP : h->dPh;
-  // the pressure summary of T (if any) describes its on-grid cells: this update makes the ghost cells copies of them
-  if (h->sum_arr == T && h->nwind == 0 && h->nws == 0) h->sum_bc = true;
-  else if (h->sum_arr == T) h->sum_arr = nullptr;
-  // a rotating source that cannot be evaluated at simtime: EINVAL before anything is written
-  if (h->nws > 0 && h->have_angle) {
-    if (int rc = wind_angle_check(h, simtime)) return rc;
-  }
-  time_begin(h, 2);
-
-  // TimeUpdateInternalBCs: stellar wind only (assign_update_bcs.cpp:134-183)
-  if (h->nwind > 0) {
-    hipLaunchKernelGGL(k_wind, dim3((unsigned)((h->nwind + 255) / 256)), dim3(256), 0, h->stream, T, h->dwind_idx,
-                       h->dwind_state, h->nwind, cfg.nvar, g.ncell);
-  }
-  // then the wind sources, in id order (assign_update_bcs.cpp:134-183 -> stellar_wind_boundaries.cpp:326-350)
-  if (h->nws > 0) {
-    if (int rc = wind_sources_update(h, simtime)) return rc;
-  }
-  // every face periodic (z possibly handed to the neighbour ranks): one launch fills all ghosts
-  bool all_periodic = (!any_wind(h) && !cfg.bc_dmach2 && h->fuse_bc);
-  for (int d = 0; d < 2 * cfg.ndim && all_periodic; d++) {
-    const bool zface = (d >= 4);
-    if (!(cfg.bc_type[d] == PION_BC_PERIODIC || (zface && cfg.bc_type[d] == PION_BC_SLAB))) all_periodic = false;
-  }
-  if (all_periodic && cfg.ndim == 3 && cfg.bc_type[4] != cfg.bc_type[5]) all_periodic = false;
-  if (all_periodic) {
-    const int zwrap = (cfg.ndim == 3 && cfg.bc_type[4] == PION_BC_PERIODIC) ? 1 : 0;
-    // x ghosts of the on-grid rows: already in place when the stage kernel that wrote T also wrote them
-    const int skipx = (h->xghost_fresh == T) ? 1 : 0;
-    const long n = (zwrap ? (long)2 * g.nbc[2] * g.nga[0] * g.nga[1] : 0) + (long)g.ng[2] * 2 * g.nbc[1] * g.nga[0]
-                   + (skipx ? 0 : (long)g.ng[2] * g.ng[1] * 2 * g.nbc[0]);
-    hipLaunchKernelGGL(k_bc_periodic_all, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, T, g, cfg.nvar,
-                       zwrap, skipx);
-  }
-  h->xghost_fresh = nullptr;
-  // any other mix of face types, once the boundaries are assigned: ONE launch for all external faces and the
-  // internal DMR2 boundary (k_bc_all); the assignment itself (inflow / fixed states are captured face by face,
-  // after the lower faces were filled) keeps the per-face sequence below
-  const bool one_launch = (!all_periodic && !assign && h->fuse_bc);
-  if (one_launch) {
-    BCAllArgs a;
-    a.g = g;
-    a.T = T;
-    a.nvar = cfg.nvar;
-    a.eqntype = cfg.eqntype;
-    a.ntracer = cfg.ntracer;
-    a.ndim = cfg.ndim;
-    for (int d = 0; d < 6; d++) {
-      a.type[d] = (d < 2 * cfg.ndim) ? cfg.bc_type[d] : 0;
-      for (int v = 0; v < PION_MAX_NVAR; v++) a.refval[d][v] = h->refval[d][v];
-    }
-    a.dmr_a0 = 10.0 * simtime / sin(M_PI / 3.0);
-    a.dmr_t3 = tan(M_PI / 3.0);
-    a.dmr2_cols = (cfg.bc_dmach2 && h->dmr2_cols > 0) ? h->dmr2_cols : 0;
-    for (int v = 0; v < PION_MAX_NVAR; v++) a.dmr2_val[v] = 0.0;
-    a.dmr2_val[0] = 8.0;
-    a.dmr2_val[1] = 116.5;
-    a.dmr2_val[2] = 7.14470958;
-    a.dmr2_val[3] = -4.125;
-    for (int v = cfg.nvar - cfg.ntracer; v < cfg.nvar; v++) a.dmr2_val[v] = 1.0;
-    const long n = ((cfg.ndim == 3) ? (long)2 * g.nbc[2] * g.nga[0] * g.nga[1] : 0)
-                   + ((cfg.ndim >= 2) ? (long)g.ng[2] * 2 * g.nbc[1] * g.nga[0] : 0) + (long)g.ng[2] * g.ng[1] * 2 * g.nbc[0];
-    hipLaunchKernelGGL(k_bc_all, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, a);
-  }
-  // TimeUpdateExternalBCs in list order XN,XP,YN,YP,ZN,ZP then DMR2 (assign_update_bcs.cpp:185-252)
-  for (int d = 0; d < 2 * cfg.ndim && !all_periodic && !one_launch; d++) {
-    const int type = cfg.bc_type[d];
-    if (type == 0 || type == PION_BC_SLAB) continue;
-    if (assign) {
-      // BC_assign_INFLOW / BC_assign_FIXED: the constant state is read from P once, when this
-      // boundary is assigned, i.e. after the lower faces have been filled (assign_update_bcs.cpp:58-131;
-      // inflow_boundaries.cpp: source of the LAST list cell; fixed_boundaries.cpp:62-76: of the FIRST)
-      const int ax = d / 2;
-      const bool pos = d & 1;
-      if (type == PION_BC_INFLOW || type == PION_BC_FIXED) {
-        int i[3] = {0, 0, 0};
-        const bool last = (type == PION_BC_INFLOW);
-        for (int a = 0; a < 3; a++) {
-          if (a == ax) i[a] = pos ? g.ng[a] - 1 : 0;
-          else if (a < ax || a >= cfg.ndim) i[a] = last ? g.ng[a] + g.nbc[a] - 1 : -g.nbc[a];
-          else i[a] = last ? g.ng[a] - 1 : 0;
-        }
-        const long c = cell_id(g, i[0], i[1], i[2]);
-        HCHECK(h, hipStreamSynchronize(h->stream));
-        for (int v = 0; v < cfg.nvar; v++)
-          HCHECK(h, hipMemcpy(&h->refval[d][v], h->dP + v * g.ncell + c, sizeof(double), hipMemcpyDeviceToHost));
-      }
-      else if (type == PION_BC_DMACH) {
-        // double_Mach_ref_boundaries.cpp:36-44
-        for (int v = 0; v < PION_MAX_NVAR; v++) h->refval[d][v] = 0.0;
-        h->refval[d][0] = 1.4;
-        h->refval[d][1] = 1.0;
-        for (int v = cfg.nvar - cfg.ntracer; v < cfg.nvar; v++) h->refval[d][v] = -1.0;
-      }
-    }
-    BCArgs a;
-    a.g = g;
-    a.T = T;
-    a.nvar = cfg.nvar;
-    a.dir = d;
-    a.type = type;
-    a.eqntype = cfg.eqntype;
-    a.ntracer = cfg.ntracer;
-    for (int v = 0; v < PION_MAX_NVAR; v++) a.refval[v] = h->refval[d][v];
-    a.dmr_a0 = 10.0 * simtime / sin(M_PI / 3.0);
-    a.dmr_t3 = tan(M_PI / 3.0);
-    const int ax = d / 2;
-    long total = g.nbc[ax];
-    for (int a2 = 0; a2 < 3; a2++) {
-      if (a2 == ax) continue;
-      total *= (a2 < ax || a2 >= cfg.ndim) ? g.nga[a2] : g.ng[a2];
-    }
-    hipLaunchKernelGGL(k_bc_face, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a);
-  }
-  if (cfg.bc_dmach2 && h->dmr2_cols > 0 && !one_launch) {
-    BCArgs a;
-    a.g = g;
-    a.T = T;
-    a.nvar = cfg.nvar;
-    a.dir = -1;
-    a.type = PION_BC_DMACH2;
-    a.eqntype = cfg.eqntype;
-    a.ntracer = cfg.ntracer;
-    for (int v = 0; v < PION_MAX_NVAR; v++) a.refval[v] = 0.0;
-    a.refval[0] = 8.0;
-    a.refval[1] = 116.5;
-    a.refval[2] = 7.14470958;
-    a.refval[3] = -4.125;
-    a.refval[4] = 0.0;
-    for (int v = cfg.nvar - cfg.ntracer; v < cfg.nvar; v++) a.refval[v] = 1.0;
-    a.dmr_a0 = a.dmr_t3 = 0.0;
-    const int n = h->dmr2_cols * g.nbc[1];
-    hipLaunchKernelGGL(k_bc_dmr2, dim3((n + 255) / 256), dim3(256), 0, h->stream, a, h->dmr2_cols);
-  }
-  // internal JETBC, listed after the external boundaries (jet_boundaries.cpp:212-262)
-  if (h->njet > 0) {
-    hipLaunchKernelGGL(k_wind, dim3((unsigned)((h->njet + 255) / 256)), dim3(256), 0, h->stream, T, h->djet_idx,
-                       h->djet_state, h->njet, cfg.nvar, g.ncell);
-  }
-  time_end(h, 2);
-  HCHECK(h, hipGetLastError());
-  if (full) h->ph_valid = false;
   return 0;
 }
 

@@ -1,6 +1,6 @@
 // pion_handle.h -- shared by the translation units of the C-ABI layer: the handle behind include/pion_gpu.h's opaque
-// pointer and the helpers every entry point uses (defined in pion_gpu.hip, used there, in pion_step.hip and in
-// pion_wind.hip).
+// pointer and the helpers every entry point uses (defined in pion_gpu.hip, used there, in pion_step.hip, in
+// pion_bc.hip and in pion_wind.hip).
 #ifndef PION_HANDLE_H
 #define PION_HANDLE_H
 
@@ -156,6 +156,9 @@ struct DevBuf {
 int wind_angle_check(Handle *h, double simtime);
 int wind_sources_update(Handle *h, double simtime);
 void wind_free(Handle *h);
+
+// The boundary part of pion_gpu_create (pion_bc.hip): no face holds a state yet, the columns of the DMR2 boundary
+void bc_init(Handle *h);
 
 // legacy wind list or wind sources present: the stage kernels read the cell flags, and the periodic ghost images
 // are not fused into one launch
