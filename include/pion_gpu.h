@@ -161,6 +161,23 @@ int pion_gpu_download(void *handle, int which, double *P_soa);
 long pion_gpu_ongrid_count(void *handle, int planes);
 int pion_gpu_pack_ongrid(void *handle, int which, int plane_lo, int plane_hi, void *dbuf);
 int pion_gpu_unpack_ongrid(void *handle, int plane_lo, int plane_hi, void *dbuf);
+/* FITS output (pion_amd/csrc/dev_output.h states the rules; the reference's dataio_fits::OutputData,
+ * dataIO/dataio_fits.cpp:147-320): the images of planes [plane_lo, plane_hi) as a contiguous DEVICE buffer
+ * [nimage][planes][ny][nx] (2-D: [nimage][planes][nx]; 1-D: [nimage][nx]) of pion_gpu_fits_count(handle, planes)
+ * elements.  Images: the primitive variables in state order (GasDens GasPres GasVX GasVY GasVZ [Bx By Bz [psi]] TR0 ..),
+ * then Eint = p/(gamma-1)/rho (no microphysics) or Temp = p Mu_tot_over_kB / rho (cooling != 0), then for MHD and GLM
+ * divB (centred differences; d(R B_R)/(R dR) between the neighbours' centres of mass on a cylindrical grid) and
+ * Ptot = p + 0.5 B^2.  Bx, By, Bz and divB are multiplied by sqrt(4 pi) (the reference's NEW_B_NORM); psi and Ptot
+ * are not.  Every element is the IEEE-754 double ALREADY BYTE-SWAPPED to big-endian: a FITS writer stores the bytes
+ * as they arrive.  Both floating-point builds give the same bits.
+ *   pion_gpu_pack_fits    packs from array P only; enqueued on the compute stream, returns at once.  divB reads the
+ *                         2 ndim neighbours of B, ghost cells and ghost planes included: they hold whatever the last
+ *                         pion_gpu_update_bcs (and halo exchange) left, so call it after the boundary update.
+ *   pion_gpu_fits_images  the image list (names: NUL-padded, may be NULL) without a device call.
+ * EINVAL: more than five tracers (as the reference), a plane range outside the grid or empty, NULL dbuf. */
+int pion_gpu_fits_images(void *handle, char names[][16], int *n);
+long pion_gpu_fits_count(void *handle, int planes);
+int pion_gpu_pack_fits(void *handle, int plane_lo, int plane_hi, void *dbuf);
 /* adopt caller-owned device buffers (e.g. torch tensors) instead of internal ones;
  * both must hold nvar*ncell_all doubles */
 int pion_gpu_bind_device_state(void *handle, void *dP, void *dPh);

@@ -73,6 +73,24 @@ int pion_host_sim_set_slab_extent(void *sim, int global_planes, int plane_lo, in
  * problem), then fp64 little-endian [nvar][slab_n][ny][nx] at pion_data_offset, code units, no ghost cells.  The
  * planes leave the device a chunk at a time (pion_gpu_pack_ongrid): host memory is two chunks whatever the grid. */
 int pion_host_sim_write_snapshot(void *sim, const char *path);
+/* The FITS file of this sim's on-grid cells (pion_amd/host/fits_io.h; FITS standard 4.0, after the reference's
+ * dataio_fits::OutputData): a primary HDU without data whose header carries every parameter of the PIONRAW2 header
+ * (pion_data_offset excepted) as "HIERARCH <name> = <value>" cards under the same names (arrays element-numbered:
+ * NGrid0..2, Xmin0..2, Xmax0..2, Ref_Vector0..; doubles %.17G), then one double-precision IMAGE extension per image
+ * of pion_gpu_fits_images -- the primitive variables, Eint or Temp, and for MHD / GLM divB and Ptot --, NAXIS1 = nx,
+ * the rank's own extent, EXTNAME = the image's name.  Bx, By, Bz and divB carry the reference's sqrt(4 pi); psi and
+ * Ptot do not.  The images are packed on the device, derived fields and byte order included (pion_gpu_pack_fits), and
+ * leave it a chunk of planes at a time: host memory is two chunks.  divB reads the ghost cells the last boundary
+ * update and halo exchange left.  Every rank writes its own file.  EINVAL and a text: more than five tracers, a path
+ * that cannot be created.  Never exits.  Not read back: a restart reads PIONRAW2. */
+int pion_host_sim_write_fits(void *sim, const char *path);
+/* File type of the regular outputs of pion_host_sim_time_int (step 0, every output step or time, the final state):
+ * PION_HOST_FILE_PIONRAW (the default) or PION_HOST_FILE_FITS, <base>_<rank, 4 digits>.<step, 8 digits>.fits.  The
+ * checkpoints stay PIONRAW2: they are what a restart reads.  Cadence, the time-step clip and every dt are untouched.
+ * EINVAL and a text: any other value. */
+#define PION_HOST_FILE_PIONRAW 0
+#define PION_HOST_FILE_FITS 1
+int pion_host_sim_set_output_filetype(void *sim, int type);
 typedef struct pion_host_snapshot_info {
   double t_start, t_finish, t_sim, min_timestep, last_dt;   /* SimPM.starttime, finishtime, simtime, min_timestep, last_dt */
   double opfreq_time, next_optime;

@@ -59,6 +59,14 @@ typedef struct pion_backend {
   int (*ongrid_to_host_end)(void *handle, int slot, const double **host);
   int (*ongrid_from_host)(void *handle, int plane_lo, int plane_hi, int slot, int (*fill)(void *ctx, double *host),
                           void *ctx);
+  /* FITS output (fits_io.h): the images of planes [plane_lo, plane_hi) as [nimage][planes][ny][nx], every element
+   * already big-endian (pion_gpu_pack_fits' layout), through the same two staging slots.  Both NULL (a table
+   * initialised before they existed): the writer takes array 0 through download and evaluates the images on the host.
+   *   fits_count:         elements (8 bytes each) of a chunk of `planes` planes
+   *   fits_to_host_begin: start packing and copying the planes into staging slot `slot`; returns at once.  Arrival
+   *                       is ongrid_to_host_end's */
+  long (*fits_count)(void *handle, int planes);
+  int (*fits_to_host_begin)(void *handle, int plane_lo, int plane_hi, int slot);
 } pion_backend;
 
 /* the product's backend: libpion_gpu.so */

@@ -111,18 +111,29 @@ int staging_slot(void *h, int slot, long n, Staging **out)
 }
 hipStream_t compute_stream_of(void *h) { return (hipStream_t)pion_gpu_get_stream(h, 0); }
 
-int gpu_ongrid_to_host_begin(void *h, int which, int plane_lo, int plane_hi, int slot)
+// pack (the variables of array `which`, or the FITS images of P) into the slot's device buffer, then copy
+int gpu_to_host_begin(void *h, bool fits, int which, int plane_lo, int plane_hi, int slot)
 {
-  const long n = pion_gpu_ongrid_count(h, plane_hi - plane_lo);
+  const long n = fits ? pion_gpu_fits_count(h, plane_hi - plane_lo) : pion_gpu_ongrid_count(h, plane_hi - plane_lo);
   Staging *st;
   if (int rc = staging_slot(h, slot, n, &st)) return rc;
-  if (int rc = pion_gpu_pack_ongrid(h, which, plane_lo, plane_hi, st->dev[slot])) return rc;
+  if (int rc = fits ? pion_gpu_pack_fits(h, plane_lo, plane_hi, st->dev[slot])
+                    : pion_gpu_pack_ongrid(h, which, plane_lo, plane_hi, st->dev[slot]))
+    return rc;
   hipStream_t s = compute_stream_of(h);
   if (hipMemcpyAsync(st->host[slot], st->dev[slot], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
     return PION_GPU_EDEVICE;
   if (hipEventRecord(st->ev[slot], s) != hipSuccess) return PION_GPU_EDEVICE;
   st->busy[slot] = true;
   return 0;
+}
+int gpu_ongrid_to_host_begin(void *h, int which, int plane_lo, int plane_hi, int slot)
+{
+  return gpu_to_host_begin(h, false, which, plane_lo, plane_hi, slot);
+}
+int gpu_fits_to_host_begin(void *h, int plane_lo, int plane_hi, int slot)
+{
+  return gpu_to_host_begin(h, true, 0, plane_lo, plane_hi, slot);
 }
 int gpu_ongrid_to_host_end(void *h, int slot, const double **host)
 {
@@ -197,6 +208,8 @@ const pion_backend k_gpu = {
     gpu_ongrid_to_host_begin,
     gpu_ongrid_to_host_end,
     gpu_ongrid_from_host,
+    pion_gpu_fits_count,
+    gpu_fits_to_host_begin,
 };
 
 }  // namespace

@@ -197,6 +197,29 @@ std::string sim_control_gpu::snapshot_name(long id) const
   return T.outfile + b;
 }
 
+int sim_control_gpu::set_output_filetype(int type)
+{
+  if (type != PION_HOST_FILE_PIONRAW && type != PION_HOST_FILE_FITS) {
+    io_error_ = "set_output_filetype: unknown file type " + std::to_string(type) + " (PION_HOST_FILE_PIONRAW or PION_HOST_FILE_FITS)";
+    return PION_GPU_EINVAL;
+  }
+  filetype_ = type;
+  return 0;
+}
+
+std::string sim_control_gpu::output_name(long step) const
+{
+  if (filetype_ != PION_HOST_FILE_FITS) return snapshot_name(step);
+  char b[64];
+  snprintf(b, sizeof b, "_%04d.%08ld.fits", comm_ ? comm_->rank() : 0, step);
+  return T.outfile + b;
+}
+
+int sim_control_gpu::write_output(const char *path)
+{
+  return (filetype_ == PION_HOST_FILE_FITS) ? write_fits(path) : write_snapshot(path);
+}
+
 // sim_init::output_data (sim_init.cpp:671-760)
 int sim_control_gpu::output_data()
 {
@@ -225,7 +248,7 @@ int sim_control_gpu::output_data()
   }
   // (the reference writes a final state that is also a regular output twice, from Time_Int and from Finalise; once here)
   if (last_output_step_ == T.timestep) return 0;
-  if (int rc = write_snapshot(snapshot_name(T.timestep).c_str())) return rc;
+  if (int rc = write_output(output_name(T.timestep).c_str())) return rc;
   last_output_step_ = T.timestep;
   return 0;
 }
@@ -365,6 +388,24 @@ int pion_host_sim_write_snapshot(void *s, const char *path)
     g_last_exception = e.what();
     return PION_GPU_EINVAL;
   }
+}
+int pion_host_sim_write_fits(void *s, const char *path)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  try {
+    return io_result(c, c->write_fits(path));
+  }
+  catch (const std::exception &e) {
+    g_last_exception = e.what();
+    return PION_GPU_EINVAL;
+  }
+}
+int pion_host_sim_set_output_filetype(void *s, int type)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  return io_result(c, c->set_output_filetype(type));
 }
 int pion_host_sim_read_snapshot(void *s, const char *const *paths, int npaths)
 {

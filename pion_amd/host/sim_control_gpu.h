@@ -16,12 +16,14 @@
 #define PION_SIM_CONTROL_GPU_H
 
 #include <string>
+#include <vector>
 
 #include "../../include/pion_gpu.h"
 #include "pion_backend.h"
 
 namespace pion_host {
 
+struct snapshot_param;   // snapshot_io.h
 class slab_comm;   // slab_comm.h: slab_comm_rccl (RCCL over xGMI) or slab_comm_shm (host-staged)
 
 // the slice of SimParams (sim_params.h:200-285) the time loop itself reads/writes
@@ -80,6 +82,15 @@ class sim_control_gpu {
   int output_data();
   // <base>_<rank, 4 digits>.<id, 8 digits>.pionraw
   std::string snapshot_name(long id) const;
+  // SimPM.typeofop for the regular outputs of output_data(): PION_HOST_FILE_PIONRAW (the default) or
+  // PION_HOST_FILE_FITS (<base>_<rank, 4 digits>.<step, 8 digits>.fits).  Checkpoints stay PIONRAW2: they are what a
+  // restart reads.  EINVAL: any other value
+  int set_output_filetype(int type);
+  // the regular output of step `step`: its name and the writer the file type selects
+  std::string output_name(long step) const;
+  int write_output(const char *path);
+  // the FITS file (fits_io.h) of this sim's on-grid cells, derived images included; streamed like write_snapshot
+  int write_fits(const char *path);
   // the PIONRAW2 file (snapshot_io.h) of this sim's on-grid cells; completes a halo exchange in flight first
   int write_snapshot(const char *path);
   // restart from the files that hold this sim's planes (written by any number of ranks); sets P, Ph, simtime,
@@ -119,6 +130,10 @@ class sim_control_gpu {
   int n_wind_sources_ = 0;
   long last_output_step_ = -1;   // step whose regular output has been written
   std::string io_error_;
+  int filetype_ = 0;             // PION_HOST_FILE_*
+  // snapshot_io.cpp: what both writers share
+  int snapshot_params(std::vector<snapshot_param> &out, long &slab_n);
+  int stream_runs(int fd, bool fits, int nrun, long nloc, long plane, long off, long stride, const char *who);
 };
 
 }  // namespace pion_host

@@ -70,17 +70,6 @@ Shape shape_of(const pion_gpu_config &c)
   return s;
 }
 
-int full_pwrite(int fd, const void *p, size_t n, off_t off)
-{
-  const char *c = (const char *)p;
-  while (n > 0) {
-    const ssize_t w = pwrite(fd, c, n, off);
-    if (w < 0 && errno == EINTR) continue;
-    if (w <= 0) return -1;
-    c += w, off += w, n -= (size_t)w;
-  }
-  return 0;
-}
 int full_pread(int fd, void *p, size_t n, off_t off)
 {
   char *c = (char *)p;
@@ -163,6 +152,18 @@ bool get_int(const snapshot_header &hd, const char *key, int &out, std::string &
 }
 
 }  // namespace
+
+int full_pwrite(int fd, const void *p, size_t n, off_t off)
+{
+  const char *c = (const char *)p;
+  while (n > 0) {
+    const ssize_t w = pwrite(fd, c, n, off);
+    if (w < 0 && errno == EINTR) continue;
+    if (w <= 0) return -1;
+    c += w, off += w, n -= (size_t)w;
+  }
+  return 0;
+}
 
 bool equalD(const double a, const double b)
 {
@@ -318,6 +319,82 @@ int global_view(const sim_control_gpu &sim, Global &G, std::string &err)
 }
 }  // namespace
 
+// every parameter a file of this sim carries, in snapshot_header_keys() order (pion_data_offset, the PIONRAW2 file's
+// own, excepted): the one list both writers use
+int sim_control_gpu::snapshot_params(std::vector<snapshot_param> &out, long &slab_n)
+{
+  Global G;
+  if (int rc = global_view(*this, G, io_error_)) return rc;
+  slab_n = G.slab_n;
+  out.clear();
+  auto I = [&](const char *k, long v) { out.push_back({k, std::to_string(v), 'i'}); };
+  auto D = [&](const char *k, double v) { out.push_back({k, fmt_d(v), 'd'}); };
+  auto S = [&](const char *k, const std::string &v) { out.push_back({k, v, 's'}); };
+  I("gridndim", cfg.ndim);
+  out.push_back({"NGrid", std::to_string(G.ng[0]) + " " + std::to_string(G.ng[1]) + " " + std::to_string(G.ng[2]), 'i'});
+  I("Ncell", (long)G.ng[0] * G.ng[1] * G.ng[2]);
+  out.push_back({"Xmin", fmt_d(G.xmin[0]) + " " + fmt_d(G.xmin[1]) + " " + fmt_d(G.xmin[2]), 'd'});
+  out.push_back({"Xmax", fmt_d(G.xmax[0]) + " " + fmt_d(G.xmax[1]) + " " + fmt_d(G.xmax[2]), 'd'});
+  I("eqn_type", cfg.eqntype), I("eqn_nvar", cfg.nvar), I("num_tracer", cfg.ntracer);
+  I("solver", cfg.solver), I("coord_sys", cfg.coord_sys);
+  I("Space_OOA", cfg.sp_ooa), I("Time_OOA", cfg.tm_ooa);
+  D("Gamma", cfg.gamma), D("CFL", cfg.cfl);
+  I("art_visc", cfg.artvisc), D("eta_visc", cfg.etav);
+  std::string rv;
+  for (int v = 0; v < cfg.nvar; v++) rv += (v ? " " : "") + fmt_d(cfg.refvec[v]);
+  out.push_back({"Ref_Vector", rv, 'd'});
+  I("EP_cooling", cfg.cooling), I("EP_MP_timestep_limit", cfg.mp_timestep_limit);
+  D("EP_Min_Temperature", cfg.min_temp), D("EP_Max_Temperature", cfg.max_temp);
+  D("t_start", T.starttime), D("t_finish", T.finishtime);
+  I("t_step", T.timestep), D("t_sim", T.simtime);
+  D("min_timestep", T.min_timestep), D("last_dt", T.last_dt);
+  I("op_freq", T.opfreq), D("opfreq_time", T.opfreq_time);
+  I("op_criterion", T.op_criterion);
+  S("outfile", T.outfile.empty() ? "NONE" : T.outfile);
+  for (int f = 0; f < 6; f++) S(BC_KEYS[f], bc_name(G.bc[f]));
+  // internal boundaries and sources are set up by the caller before a restart: the header only counts them
+  I("BC_Ninternal", (cfg.bc_dmach2 ? 1 : 0) + (n_wind_sources_ > 0 ? 1 : 0));
+  I("JetSim", 0);
+  I("WIND_Nsources", n_wind_sources_);
+  I("pion_nbc", cfg.nbc), I("pion_strict_fp", cfg.strict_fp), I("pion_bc_dmach2", cfg.bc_dmach2);
+  D("pion_dx", cfg.dx);
+  D("pion_next_optime", T.next_optime);
+  I("pion_rank", comm_ ? comm_->rank() : 0), I("pion_world", comm_ ? comm_->world() : 1);
+  I("pion_slab_lo", G.slab_lo), I("pion_slab_n", G.slab_n);
+  return 0;
+}
+
+// The streamed write loop of both files.  The planes [0, nloc) leave the backend a chunk of whole planes at a time:
+// pack and copy of chunk i+1 are enqueued while chunk i is pwrite()n, one run per variable (PIONRAW2) or image (FITS),
+// run r of a chunk at off + r * stride + (its first plane's byte offset inside a run).  A chunk is the largest number
+// of planes whose runs fit one staging slot.
+int sim_control_gpu::stream_runs(int fd, bool fits, int nrun, long nloc, long plane, long off, long stride, const char *who)
+{
+  long (*const count)(void *, int) = fits ? be_->fits_count : be_->ongrid_count;
+  auto begin = [&](long lo, long hi, int slot) {
+    return fits ? be_->fits_to_host_begin(h_, (int)lo, (int)hi, slot) : be_->ongrid_to_host_begin(h_, 0, (int)lo, (int)hi, slot);
+  };
+  const long cp = chunk_planes(count(h_, 1), nloc);
+  const long nchunk = (nloc + cp - 1) / cp;
+  int rc = begin(0, std::min(cp, nloc), 0);
+  for (long i = 0; i < nchunk && !rc; i++) {
+    const long a = i * cp, b = std::min(nloc, a + cp);
+    if (i + 1 < nchunk) rc = begin(b, std::min(nloc, b + cp), (int)((i + 1) & 1));
+    const double *src = nullptr;
+    if (!rc) rc = be_->ongrid_to_host_end(h_, (int)(i & 1), &src);
+    if (rc) {
+      io_error_ = std::string(who) + ": staging the planes failed: " + last_error();
+      break;
+    }
+    const size_t n = (size_t)(b - a) * plane;
+    for (int v = 0; v < nrun && !rc; v++)
+      if (full_pwrite(fd, src + (size_t)v * n, n * sizeof(double), (off_t)(off + (long)v * stride + a * plane * (long)sizeof(double))))
+        rc = PION_GPU_EINVAL;
+  }
+  if (rc && io_error_.empty()) io_error_ = std::string(who) + ": staging the planes failed: " + last_error();
+  return rc;
+}
+
 int sim_control_gpu::write_snapshot(const char *path)
 {
   io_error_.clear();
@@ -325,48 +402,18 @@ int sim_control_gpu::write_snapshot(const char *path)
     io_error_ = "write_snapshot: no path";
     return PION_GPU_EINVAL;
   }
-  Global G;
-  if (int rc = global_view(*this, G, io_error_)) return rc;
+  std::vector<snapshot_param> params;
+  long nloc = 0;
+  if (int rc = snapshot_params(params, nloc)) return rc;
   if (int rc = finish_halo()) {
     io_error_ = "write_snapshot: finish_halo failed";
     return rc;
   }
   const Shape s = shape_of(cfg);
-  const long nloc = G.slab_n, plane = s.plane();
+  const long plane = s.plane();
 
-  std::ostringstream h;
-  h << "gridndim " << cfg.ndim << "\n";
-  h << "NGrid " << G.ng[0] << " " << G.ng[1] << " " << G.ng[2] << "\n";
-  h << "Ncell " << (long)G.ng[0] * G.ng[1] * G.ng[2] << "\n";
-  h << "Xmin " << fmt_d(G.xmin[0]) << " " << fmt_d(G.xmin[1]) << " " << fmt_d(G.xmin[2]) << "\n";
-  h << "Xmax " << fmt_d(G.xmax[0]) << " " << fmt_d(G.xmax[1]) << " " << fmt_d(G.xmax[2]) << "\n";
-  h << "eqn_type " << cfg.eqntype << "\neqn_nvar " << cfg.nvar << "\nnum_tracer " << cfg.ntracer << "\n";
-  h << "solver " << cfg.solver << "\ncoord_sys " << cfg.coord_sys << "\n";
-  h << "Space_OOA " << cfg.sp_ooa << "\nTime_OOA " << cfg.tm_ooa << "\n";
-  h << "Gamma " << fmt_d(cfg.gamma) << "\nCFL " << fmt_d(cfg.cfl) << "\n";
-  h << "art_visc " << cfg.artvisc << "\neta_visc " << fmt_d(cfg.etav) << "\n";
-  h << "Ref_Vector";
-  for (int v = 0; v < cfg.nvar; v++) h << " " << fmt_d(cfg.refvec[v]);
-  h << "\n";
-  h << "EP_cooling " << cfg.cooling << "\nEP_MP_timestep_limit " << cfg.mp_timestep_limit << "\n";
-  h << "EP_Min_Temperature " << fmt_d(cfg.min_temp) << "\nEP_Max_Temperature " << fmt_d(cfg.max_temp) << "\n";
-  h << "t_start " << fmt_d(T.starttime) << "\nt_finish " << fmt_d(T.finishtime) << "\n";
-  h << "t_step " << T.timestep << "\nt_sim " << fmt_d(T.simtime) << "\n";
-  h << "min_timestep " << fmt_d(T.min_timestep) << "\nlast_dt " << fmt_d(T.last_dt) << "\n";
-  h << "op_freq " << T.opfreq << "\nopfreq_time " << fmt_d(T.opfreq_time) << "\n";
-  h << "op_criterion " << T.op_criterion << "\n";
-  h << "outfile " << (T.outfile.empty() ? "NONE" : T.outfile) << "\n";
-  for (int f = 0; f < 6; f++) h << BC_KEYS[f] << " " << bc_name(G.bc[f]) << "\n";
-  // internal boundaries and sources are set up by the caller before a restart: the header only counts them
-  h << "BC_Ninternal " << (cfg.bc_dmach2 ? 1 : 0) + (n_wind_sources_ > 0 ? 1 : 0) << "\n";
-  h << "JetSim 0\n";
-  h << "WIND_Nsources " << n_wind_sources_ << "\n";
-  h << "pion_nbc " << cfg.nbc << "\npion_strict_fp " << cfg.strict_fp << "\npion_bc_dmach2 " << cfg.bc_dmach2 << "\n";
-  h << "pion_dx " << fmt_d(cfg.dx) << "\n";
-  h << "pion_next_optime " << fmt_d(T.next_optime) << "\n";
-  h << "pion_rank " << (comm_ ? comm_->rank() : 0) << "\npion_world " << (comm_ ? comm_->world() : 1) << "\n";
-  h << "pion_slab_lo " << G.slab_lo << "\npion_slab_n " << nloc << "\n";
-  std::string head = std::string(MAGIC, 8) + h.str();
+  std::string head = std::string(MAGIC, 8);
+  for (const snapshot_param &p : params) head += p.key + " " + p.value + "\n";
   // the data start at a multiple of 4096 bytes
   long off = ((long)head.size() + 64 + 4095) / 4096 * 4096;
   head += "pion_data_offset " + std::to_string(off) + "\n";
@@ -383,26 +430,8 @@ int sim_control_gpu::write_snapshot(const char *path)
   int rc = 0;
   if (full_pwrite(f.fd, head.data(), head.size(), 0)) rc = PION_GPU_EINVAL;
   const size_t run = (size_t)nloc * plane;   // doubles of one variable in the file
-  if (!rc && be_->ongrid_to_host_begin && be_->ongrid_to_host_end && be_->ongrid_count) {
-    const long cp = chunk_planes(be_->ongrid_count(h_, 1), nloc);
-    const long nchunk = (nloc + cp - 1) / cp;
-    rc = be_->ongrid_to_host_begin(h_, 0, 0, (int)std::min(cp, nloc), 0);
-    for (long i = 0; i < nchunk && !rc; i++) {
-      const long a = i * cp, b = std::min(nloc, a + cp);
-      if (i + 1 < nchunk) rc = be_->ongrid_to_host_begin(h_, 0, (int)b, (int)std::min(nloc, b + cp), (int)((i + 1) & 1));
-      const double *src = nullptr;
-      if (!rc) rc = be_->ongrid_to_host_end(h_, (int)(i & 1), &src);
-      if (rc) {
-        io_error_ = "write_snapshot: staging the planes failed: " + last_error();
-        break;
-      }
-      const size_t n = (size_t)(b - a) * plane;
-      for (int v = 0; v < cfg.nvar && !rc; v++)
-        if (full_pwrite(f.fd, src + (size_t)v * n, n * sizeof(double), off + (off_t)(((size_t)v * run + (size_t)a * plane) * sizeof(double))))
-          rc = PION_GPU_EINVAL;
-    }
-    if (rc && io_error_.empty()) io_error_ = "write_snapshot: staging the planes failed: " + last_error();
-  }
+  if (!rc && be_->ongrid_to_host_begin && be_->ongrid_to_host_end && be_->ongrid_count)
+    rc = stream_runs(f.fd, false, cfg.nvar, nloc, plane, off, (long)(run * sizeof(double)), "write_snapshot");
   else if (!rc) {
     // no streaming entries: the whole array with its ghosts, stripped here
     const long nb = cfg.nbc, nxa = cfg.ng[0] + 2 * nb, nya = (cfg.ndim >= 2) ? cfg.ng[1] + 2 * nb : 1,

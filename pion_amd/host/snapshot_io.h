@@ -20,9 +20,12 @@
 // one run per variable at its file offset; the read path mirrors it.  A backend without those entries (the test
 // oracle's table) goes through its whole-array download / upload, ghosts stripped / embedded here.
 //
-// The members sim_control_gpu::write_snapshot / read_snapshot are defined in snapshot_io.cpp.
+// The members sim_control_gpu::write_snapshot / read_snapshot are defined in snapshot_io.cpp, and with them what the
+// FITS writer (fits_io.h) shares: the list of parameters (snapshot_params) and the streamed write loop (stream_runs).
 #ifndef PION_SNAPSHOT_IO_H
 #define PION_SNAPSHOT_IO_H
+
+#include <sys/types.h>
 
 #include <map>
 #include <string>
@@ -45,6 +48,16 @@ struct snapshot_header {
 int snapshot_read_header(const char *path, snapshot_header &hd, std::string &err);
 // the header names every file carries, in file order
 const std::vector<std::string> &snapshot_header_keys();
+
+// one parameter of a file as sim_control_gpu::snapshot_params lists it: the PIONRAW2 line is "key value"; type 'i'
+// (integers), 'd' (doubles, %.17g) or 's' (a string); an array is its elements separated by one blank
+struct snapshot_param {
+  std::string key, value;
+  char type;
+};
+
+// all n bytes at offset off, or -1
+int full_pwrite(int fd, const void *p, size_t n, off_t off);
 
 }  // namespace pion_host
 #endif

@@ -17,6 +17,7 @@ _dp = C.POINTER(C.c_double)
 _host = None
 
 UNIQUE_ID_BYTES = 128
+FILE_PIONRAW, FILE_FITS = 0, 1   # PION_HOST_FILE_* (include/pion_host.h)
 
 
 class SnapshotInfo(C.Structure):
@@ -77,6 +78,9 @@ def load_host_library():
         h.pion_host_sim_read_snapshot.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int]
         h.pion_host_snapshot_read_header.argtypes = [C.c_char_p, C.POINTER(abi.PionGpuConfig), C.POINTER(SnapshotInfo)]
         h.pion_host_sim_get_time.argtypes = [C.c_void_p, _dp]
+    if hasattr(h, "pion_host_sim_write_fits"):   # (likewise)
+        h.pion_host_sim_write_fits.argtypes = [C.c_void_p, C.c_char_p]
+        h.pion_host_sim_set_output_filetype.argtypes = [C.c_void_p, C.c_int]
     h.pion_host_comm_unique_id.argtypes = [C.c_void_p]
     h.pion_host_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     h.pion_host_comm_destroy.argtypes = [C.c_void_p]
@@ -206,6 +210,20 @@ class HostSim:
         rc = self.lib.pion_host_sim_write_snapshot(self.s, os.fsencode(path))
         if rc != 0:
             raise RuntimeError("pion_host_sim_write_snapshot rc=%d: %s" % (rc, self.last_error()))
+
+    def write_fits(self, path):
+        """the FITS file of this sim's on-grid cells, derived images included (pion_host_sim_write_fits);
+        pion_amd.fits.read loads it"""
+        rc = self.lib.pion_host_sim_write_fits(self.s, os.fsencode(path))
+        if rc != 0:
+            raise RuntimeError("pion_host_sim_write_fits rc=%d: %s" % (rc, self.last_error()))
+
+    def set_output_filetype(self, filetype):
+        """FILE_PIONRAW (the default) or FILE_FITS for the regular outputs of time_int; checkpoints stay PIONRAW2
+        (pion_host_sim_set_output_filetype)"""
+        rc = self.lib.pion_host_sim_set_output_filetype(self.s, int(filetype))
+        if rc != 0:
+            raise ValueError("pion_host_sim_set_output_filetype rc=%d: %s" % (rc, self.last_error()))
 
     def restart(self, paths):
         """pion_host_sim_read_snapshot: restart from the file(s) that hold this sim's planes (one path or a list)"""

@@ -82,6 +82,11 @@ def load_library():
         lib.pion_gpu_ongrid_count.restype = C.c_long
         lib.pion_gpu_pack_ongrid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         lib.pion_gpu_unpack_ongrid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(lib, "pion_gpu_pack_fits"):   # (likewise)
+        lib.pion_gpu_fits_images.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        lib.pion_gpu_fits_count.argtypes = [C.c_void_p, C.c_int]
+        lib.pion_gpu_fits_count.restype = C.c_long
+        lib.pion_gpu_pack_fits.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     lib.pion_gpu_interface_flux.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pion_gpu_cooling_update.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp]
     lib.pion_gpu_cooling_edot.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
@@ -109,6 +114,7 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_wind_angle_tables", "pion_gpu_get_hll_switch", "pion_gpu_get_hll_screen_counts",
     "pion_gpu_rows_windows", "pion_gpu_get_rows_windows",
     "pion_gpu_ongrid_count", "pion_gpu_pack_ongrid", "pion_gpu_unpack_ongrid",
+    "pion_gpu_fits_images", "pion_gpu_fits_count", "pion_gpu_pack_fits",
 ]
 
 
@@ -346,6 +352,24 @@ class GpuSim:
         """pion_gpu_pack_ongrid: on-grid cells of planes [plane_lo, plane_hi) of array `which` into the device buffer
         at dbuf_ptr, [nvar][planes][ny][nx]; enqueued on the handle's stream (synchronize() before reading it)"""
         self._chk(self.lib.pion_gpu_pack_ongrid(self.h, which, plane_lo, plane_hi, C.c_void_p(dbuf_ptr)), "pack_ongrid")
+
+    def fits_images(self):
+        """pion_gpu_fits_images: the names of the images a FITS file of this handle holds, in file order (no device
+        call)"""
+        n = C.c_int(0)
+        names = ((C.c_char * 16) * (abi.PION_MAX_NVAR + 3))()
+        self._chk(self.lib.pion_gpu_fits_images(self.h, names, C.byref(n)), "fits_images")
+        return [names[i].value.decode() for i in range(n.value)]
+
+    def fits_count(self, planes):
+        """pion_gpu_fits_count: elements (8 bytes each) in a buffer of `planes` planes, all images"""
+        return self.lib.pion_gpu_fits_count(self.h, int(planes))
+
+    def pack_fits(self, plane_lo, plane_hi, dbuf_ptr):
+        """pion_gpu_pack_fits: the images of planes [plane_lo, plane_hi) of P into the device buffer at dbuf_ptr,
+        [nimage][planes][ny][nx], every element a big-endian double (view it as dtype '>f8'), B and divB times
+        sqrt(4 pi); enqueued on the compute stream.  Call it after update_bcs: divB reads ghost cells."""
+        self._chk(self.lib.pion_gpu_pack_fits(self.h, plane_lo, plane_hi, C.c_void_p(dbuf_ptr)), "pack_fits")
 
     def unpack_ongrid(self, plane_lo, plane_hi, dbuf_ptr):
         """pion_gpu_unpack_ongrid: the reverse, into P and Ph; ghost cells and other planes are left alone"""
