@@ -1,5 +1,6 @@
-// dev_addr.h -- "uniform base + 32-bit per-lane offset" addressing helpers shared by k_stage_rows2 and the
-// marching prepass (included by kernels_fp.hip inside namespace pion::PION_FPNS).
+// dev_addr.h -- "uniform base + 32-bit per-lane offset" addressing helpers and neighbour-lane shifts shared by
+// k_stage_rows2 and the marching prepass, and the wavefront minimum / maximum of the reductions (included by
+// dev_sweep.h, and so by every kernels_*.hip, inside namespace pion::PION_FPNS).
 #ifndef PION_DEV_ADDR_H
 #define PION_DEV_ADDR_H
 
@@ -86,5 +87,24 @@ PDEV double lane_prev(const double x)
 #else
   return __shfl_up(x, 1, 64);
 #endif
+}
+// minimum / maximum over the 64 lanes of a wavefront, left in every lane
+PDEV double wave_min64(double v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double w = __shfl_xor(v, o, 64);
+    v = (w < v) ? w : v;
+  }
+  return v;
+}
+PDEV double wave_max64(double v)
+{
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double w = __shfl_xor(v, o, 64);
+    v = (w > v) ? w : v;
+  }
+  return v;
 }
 #endif

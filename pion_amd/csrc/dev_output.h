@@ -13,7 +13,7 @@
 // The ghost cells the divB stencil reads hold whatever the last boundary update (and, for a slab, the last halo
 // exchange) left: the loop writes its outputs after update_bcs, and a caller of pion_gpu_pack_fits must do the same.
 //
-// The divergence is NOT shared with the HLL-switch prepass (prepass_hlld_cell, kernels_fp.hip): that one is compiled
+// The divergence is NOT shared with the HLL-switch prepass (prepass_hlld_cell, kernels_prepass.hip): that one is compiled
 // per floating-point mode (contracted in the fast build), falls back to a one-sided difference where the all-cell
 // array ends, and runs on velocities; this one has both neighbours by construction (an on-grid cell always has them,
 // ghosts included) and must give the same bits in both builds.

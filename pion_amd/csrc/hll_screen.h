@@ -1,7 +1,7 @@
 // hll_screen.h -- the rule that lets the HLLD -> HLL switch prepass skip calm regions of a 3-D grid.
 //
 // The stage kernel (stage_rows2.h) leaves the minimum and the maximum of the pressure it has just written for every
-// BLOCK of on-grid cells; before the next stage a screen kernel (kernels_fp.hip) calls a block QUIET when the range of
+// BLOCK of on-grid cells; before the next stage a screen kernel (kernels_prepass.hip) calls a block QUIET when the range of
 // the block and its 3 x 3 x 3 block neighbourhood satisfies  M - m <= 1.6 m, and the dense switch kernel runs on the
 // other blocks only.  Shared by the producer, the consumer, the C-ABI layer (pion_step.hip) and the tests' host-side
 // probe (tests/native/hll_screen_probe.cpp); it includes nothing, so that the probe compiles it as plain host code.

@@ -1,7 +1,7 @@
 // kernels.h -- launch interface between the C-ABI layer (pion_gpu.hip, pion_step.hip, pion_bc.hip) and the
-// floating-point kernels (kernels_fp.hip).  kernels_fp.hip is compiled twice,
-// once per floating-point mode, into namespaces pion::fp_strict (-ffp-contract=off:
-// bit-parity with the reference's x86-64 -O3 build) and pion::fp_fast (FMA
+// floating-point kernels: kernels_fp.hip (stage, cooling source and flux test, one object per equation set),
+// kernels_prepass.hip and kernels_dt.hip.  Each is compiled twice, once per floating-point mode, into namespaces
+// pion::fp_strict (-ffp-contract=off: bit-parity with the reference's x86-64 -O3 build) and pion::fp_fast (FMA
 // contraction allowed); pion_gpu_config::strict_fp selects at run time.
 #ifndef PION_KERNELS_H
 #define PION_KERNELS_H
@@ -122,18 +122,30 @@ struct CoolTestArgs {
   CoolDev cool;
 };
 
+// a launcher kernels_fp.hip defines once per equation set (-DPION_EQSEL), and its dispatcher on a.eqntype
+#define PION_PER_EQN(FN, ARGS)                        \
+  int FN##_hd(const ARGS &a, hipStream_t s);          \
+  int FN##_mhd(const ARGS &a, hipStream_t s);         \
+  int FN##_glm(const ARGS &a, hipStream_t s);         \
+  inline int FN(const ARGS &a, hipStream_t s)         \
+  {                                                   \
+    if (a.eqntype == EQEUL) return FN##_hd(a, s);     \
+    if (a.eqntype == EQMHD) return FN##_mhd(a, s);    \
+    if (a.eqntype == EQGLM) return FN##_glm(a, s);    \
+    return -1;                                        \
+  }
+
 #define PION_DECLARE_FP(NS)                                        \
   namespace NS {                                                   \
-  int launch_stage(const StageArgs &a, hipStream_t s);             \
-  int launch_cooling_dE(const StageArgs &a, hipStream_t s);        \
+  PION_PER_EQN(launch_stage, StageArgs)                            \
+  PION_PER_EQN(launch_cooling_dE, StageArgs)                       \
+  PION_PER_EQN(launch_flux_test, FluxTestArgs)                     \
   int launch_prepass(const PrepassArgs &a, hipStream_t s);         \
   int launch_dt(const DtArgs &a, hipStream_t s);                   \
   int launch_dt_mp(const DtArgs &a, hipStream_t s);                \
-  int launch_flux_test(const FluxTestArgs &a, hipStream_t s);      \
   int launch_cool_update(const CoolTestArgs &a, hipStream_t s);    \
   int launch_cool_edot(const CoolTestArgs &a, hipStream_t s);      \
   int launch_cool_timescale(const CoolTestArgs &a, hipStream_t s); \
-  const char *stage_kernel_name(int eq, int ntr, int solver);      \
   }
 
 PION_DECLARE_FP(fp_strict)

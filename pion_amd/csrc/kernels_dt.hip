@@ -1,0 +1,156 @@
+// kernels_dt.hip -- the time-step reductions and the cooling test seams; nothing here depends on the equation set.
+//
+//   k_dt       CellTimeStep + cooling-time reduction (calc_timestep.cpp:271-507).
+//   k_dt_mp    the cooling time alone, rate tables in LDS.
+//   k_cool_*   mp_only_cooling on n independent cells (test seams).
+//
+// Compiled twice (Makefile): -DPION_FPNS=fp_strict -ffp-contract=off and -DPION_FPNS=fp_fast -ffp-contract=fast.
+#include "dev_cooling.h"
+#include "kernels.h"
+
+#ifndef PION_FPNS
+#error "PION_FPNS must be defined (fp_strict or fp_fast)"
+#endif
+
+namespace pion {
+namespace PION_FPNS {
+
+#include "dev_sweep.h"
+
+// ---------------------------------------------------------------------------
+// time-step reduction
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_dt(const DtArgs a)
+{
+  const long nc = a.g.ncell;
+  const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
+  double tdyn = 1.e100, tmp = 1.0e99;
+  int err = 0;
+  const bool mhd = (a.eqntype != EQEUL);
+  const double g = a.gamma;
+  for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < non; k += (long)gridDim.x * blockDim.x) {
+    const long c = ongrid_cell(a.g, k);
+    const uint8_t fl = a.flags[c];
+    if ((fl & 8 /*TIMESTEP*/) && !(fl & 2 /*ISBD*/)) {
+      // CellTimeStep: solver_eqn_hydro_adi.cpp:460-502 / solver_eqn_mhd_adi.cpp:516-582
+      double p[8];
+      const int nvs = mhd ? 8 : 5;
+      for (int v = 0; v < 8; v++) p[v] = (v < nvs) ? a.P[v * nc + c] : 0.0;
+      // (the function the stage kernel's fused reduction calls: a restart, which comes through here, continues bit
+      // for bit)
+      const double t = mhd ? cell_dt<EQMHD>(p, a.g.ndim, g, a.g.dx, a.cfl) : cell_dt<EQEUL>(p, a.g.ndim, g, a.g.dx, a.cfl);
+      if (!(t > 0.0)) err |= ERR_BAD_DT;
+      tdyn = (t < tdyn) ? t : tdyn;
+    }
+    if (a.do_mp && !(fl & 2) && (fl & 16)) {
+      const double t = Cooling::timescale(a.cool, a.Ph[0 * nc + c], a.Ph[1 * nc + c], g);
+      tmp = (t < tmp) ? t : tmp;
+    }
+  }
+  tdyn = wave_min64(tdyn);
+  tmp = wave_min64(tmp);
+  if ((threadIdx.x & 63) == 0) {
+    // positive doubles order like their bit patterns
+    atomicMin(&a.result[0], (unsigned long long)__double_as_longlong(tdyn));
+    atomicMin(&a.result[1], (unsigned long long)__double_as_longlong(tmp));
+  }
+  if (err) atomicOr(a.errword, err);
+}
+
+// The cooling time alone (calc_microphysics_dt -> get_mp_timescales_no_radiation, calc_timestep.cpp:405-507;
+// mp_only_cooling::timescales, mp_only_cooling.cpp:333-368), rate tables in LDS as in k_cooling_dE: a time scale is two
+// Edot evaluations = two bisections of eight dependent look-ups each, which through global memory cost the fused
+// reduction of the stage kernel a third of its run time (Wind3D 256^3, second-order instance: 1.58 ms with it, 1.03
+// without; this kernel: see DESIGN.md s4.1).  Min over cells with !isbd && isleaf into result[1].
+__global__ __launch_bounds__(256) void k_dt_mp(const DtArgs a)
+{
+  __shared__ double ctab[11 * PION_COOL_NT_MAX];
+  const int NT = a.cool.NT;
+  for (int i = threadIdx.x; i < NT; i += 256) ctab[i] = a.cool.T[i];
+  for (int i = threadIdx.x; i < 5 * NT; i += 256) {
+    ctab[NT + i] = a.cool.tab[i];
+    ctab[6 * NT + i] = a.cool.slope[i];
+  }
+  __syncthreads();
+  CoolDev cool = a.cool;
+  cool.T = ctab;
+  cool.tab = ctab + NT;
+  cool.slope = ctab + 6 * NT;
+  const long nc = a.g.ncell;
+  const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
+  double tmp = 1.0e99;
+  for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < non; k += (long)gridDim.x * blockDim.x) {
+    const long c = ongrid_cell(a.g, k);
+    const uint8_t fl = a.flags[c];
+    if (!(fl & 2) && (fl & 16)) {
+      const double t = Cooling::timescale(cool, a.Ph[0 * nc + c], a.Ph[1 * nc + c], a.gamma);
+      tmp = (t < tmp) ? t : tmp;
+    }
+  }
+  tmp = wave_min64(tmp);
+  if ((threadIdx.x & 63) == 0) atomicMin(&a.result[1], (unsigned long long)__double_as_longlong(tmp));
+}
+int launch_dt_mp(const DtArgs &a, hipStream_t s)
+{
+  const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
+  long nb = (non + 255) / 256;
+  if (nb > 2048) nb = 2048;   // grid-stride, eight blocks per CU: the tables are staged once per block
+  hipLaunchKernelGGL(k_dt_mp, dim3((unsigned)nb), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+int launch_dt(const DtArgs &a, hipStream_t s)
+{
+  const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
+  long nb = (non + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  hipLaunchKernelGGL(k_dt, dim3((unsigned)nb), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// cooling test seams
+// ---------------------------------------------------------------------------
+__global__ void k_cool_update(const CoolTestArgs a)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  int err = 0;
+  const double *p = a.Pin + (long)i * a.nvar;
+  double *o = a.Pout + (long)i * a.nvar;
+  for (int v = 0; v < a.nvar; v++) o[v] = p[v];
+  o[1] = Cooling::time_update(a.cool, p[0], p[1], a.dt, a.gamma, err);
+  if (err) atomicOr(a.errword, err);
+}
+__global__ void k_cool_edot(const CoolTestArgs a)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  a.edot[i] = Cooling::edot(a.cool, a.rho[i], a.T[i]);
+}
+// mp_only_cooling::timescales (cooling time only) of n independent cells: edot[i] = t_cool
+__global__ void k_cool_timescale(const CoolTestArgs a)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const double *p = a.Pin + (long)i * a.nvar;
+  a.edot[i] = Cooling::timescale(a.cool, p[0], p[1], a.gamma);
+}
+int launch_cool_timescale(const CoolTestArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_cool_timescale, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+int launch_cool_update(const CoolTestArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_cool_update, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+int launch_cool_edot(const CoolTestArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_cool_edot, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+}  // namespace PION_FPNS
+}  // namespace pion

@@ -1,6 +1,7 @@
 // pion_handle.h -- shared by the translation units of the C-ABI layer: the handle behind include/pion_gpu.h's opaque
 // pointer and the helpers every entry point uses (defined in pion_gpu.hip, used there, in pion_step.hip, in
-// pion_bc.hip and in pion_wind.hip).
+// pion_bc.hip, in pion_wind.hip and in pion_output.hip).  The kernels behind kernels.h's launchers are in
+// kernels_fp.hip, kernels_prepass.hip and kernels_dt.hip.
 #ifndef PION_HANDLE_H
 #define PION_HANDLE_H
 

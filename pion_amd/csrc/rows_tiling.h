@@ -57,7 +57,7 @@ __host__ __device__ inline int zchunk_bounds(const int np, const int cmax, const
   return n;
 }
 
-// XCD-aware tile decode of the cell kernels (kernels_fp.hip): workgroups are dealt round-robin to the 8 XCDs (b % 8
+// XCD-aware tile decode of the cell kernels (kernels_fp.hip, kernels_prepass.hip): workgroups are dealt round-robin to the 8 XCDs (b % 8
 // share an XCD); give each XCD a contiguous range of tiles so that the halo re-reads of neighbouring tiles hit the
 // same L2.  Placement only changes speed, never results.  (The caller launches 8 * ceil(ntiles / 8) workgroups and
 // skips the tiles >= ntiles.)

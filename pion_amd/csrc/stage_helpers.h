@@ -1,7 +1,8 @@
 // stage_helpers.h -- helpers shared by the 3-D stage kernel (stage_rows2.h): sweep-frame loads, slopes, the
-// per-axis source + flux-difference update, CellAdvanceTime, CellTimeStep, the wavefront minimum.
+// per-axis source + flux-difference update, CellAdvanceTime.
 //
-// Included by kernels_fp.hip inside namespace pion::PION_FPNS.  (The round-1 kernels k_stage_march -- one
+// Included by kernels_fp.hip inside namespace pion::PION_FPNS, after dev_sweep.h (rotvar, avg_falle; the wavefront
+// minimum is dev_addr.h's).  (The round-1 kernels k_stage_march -- one
 // row per wavefront, z carry in registers, 4 Riemann solves per cell -- and k_stage_rows -- R = 4 rows per
 // wavefront at one wavefront per SIMD, 500 registers -- lived in this file (then stage_march.h) and in stage_rows.h (now rows_tiling.h); k_stage_rows2
 // superseded both, DESIGN.md s4 keeps their measurements.)
@@ -134,25 +135,6 @@ PDEV void cell_update_store(const StageArgs &a, const long c, const double *P0, 
 #pragma unroll
     for (int v = 0; v < NV; v++) Pfout[v] = Pf[v];
   }
-}
-
-PDEV double wave_min64(double v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double w = __shfl_xor(v, o, 64);
-    v = (w < v) ? w : v;
-  }
-  return v;
-}
-PDEV double wave_max64(double v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double w = __shfl_xor(v, o, 64);
-    v = (w > v) ? w : v;
-  }
-  return v;
 }
 
 #endif

@@ -1,8 +1,8 @@
 // stage_rows2.h -- k_stage_rows2: the 3-D production stage kernel, two wavefronts per SIMD (MHD) or three (Euler).
 //
-// Included by kernels_fp.hip inside namespace pion::PION_FPNS (after dev_addr.h, stage_helpers.h and rows_tiling.h,
-// whose helpers uni / ldu / pin_v / opaque_zero, apply_axis / cell_update, rows_tiling it uses; cell_dt is
-// kernels_fp.hip's).
+// Included by kernels_fp.hip inside namespace pion::PION_FPNS (after dev_sweep.h with dev_addr.h, stage_helpers.h and
+// rows_tiling.h, whose helpers cell_dt, uni / ldu / pin_v / opaque_zero / wave_min64, apply_axis / cell_update,
+// rows_tiling it uses).
 //
 // Same decomposition as round 1's k_stage_rows (removed; one wavefront per x-pencil of 64 lanes owning R consecutive
 // y-rows, marching along z; x fluxes shared by wavefront shuffles, the y flux and the next row's y slope

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Device ISA of kernels_fp.hip at a git revision against the working tree, both floating-point builds and every
-equation set (no GPU needed):  profiles/tools/isa_diff.py [REV=HEAD] [-j JOBS]
-Compiles with the library's flags plus --cuda-device-only -S (as probe_regs.sh does) and compares every function body
-and kernel descriptor with labels and symbol names stripped.  Exit status 1 if any function differs.
---abi: the C-ABI layer instead, every pion_*.hip each tree has, its functions pooled and matched by demangled name
-(a kernel may have moved to another file; those of an anonymous namespace then change their mangled name)."""
+"""Device ISA of the floating-point kernels at a git revision against the working tree (no GPU needed):
+    profiles/tools/isa_diff.py [REV=HEAD] [-j JOBS]
+Compiles, for each tree, every kernels_*.hip that tree has, in both floating-point builds (kernels_fp.hip once per equation
+set), with the library's flags plus --cuda-device-only -S (as probe_regs.sh does).  The functions and kernel descriptors
+of each build are pooled and matched by demangled name -- a kernel may have moved to another file; those of an anonymous
+namespace then change their mangled name -- and compared with labels and symbol names stripped.  Exit status 1 if any
+function differs.
+--abi: the C-ABI layer instead, every pion_*.hip each tree has, pooled and compared the same way."""
 import argparse
 import os
 import re
@@ -41,35 +43,50 @@ def functions(path):
     return out
 
 
-def abi_layer(trees, tmp, jobs_n):
-    """{tag: {demangled name: body or descriptor}} over the pion_*.hip of each tree; then the comparison"""
-    jobs, outs = [], {}
+def units(tree, abi):
+    """[(build, source, flags)] of one tree"""
+    csrc = os.path.join(tree, "pion_amd", "csrc")
+    if abi:
+        return [("abi", src, []) for src in sorted(glob.glob(os.path.join(csrc, "pion_*.hip")))]
+    out = []
+    for src in sorted(glob.glob(os.path.join(csrc, "kernels_*.hip"))):
+        eqs = [[]]
+        if os.path.basename(src) == "kernels_fp.hip":
+            # (a tree without kernels_prepass.hip is the old layout: PION_EQSEL=0 held the shared kernels)
+            old = not os.path.exists(os.path.join(csrc, "kernels_prepass.hip"))
+            eqs = [["-DPION_EQSEL=%d" % e] for e in range(0 if old else 1, 4)]
+        out += [(mode, src, flags + eq) for mode, flags in MODES.items() for eq in eqs]
+    return out
+
+
+def pooled(trees, abi, tmp, jobs_n):
+    """{tag: {build/demangled name: body or descriptor}}, and the sources of each tree"""
+    jobs, outs, srcs = [], {}, {}
     for tag, tree in trees:
-        for src in sorted(glob.glob(os.path.join(tree, "pion_amd", "csrc", "pion_*.hip"))):
-            out = os.path.join(tmp, "%s_%s.s" % (tag, os.path.basename(src)))
-            outs.setdefault(tag, []).append(out)
-            jobs.append([HIPCC] + COMMON + [src, "-o", out])
+        for n, (build, src, flags) in enumerate(units(tree, abi)):
+            out = os.path.join(tmp, "%s_%d.s" % (tag, n))
+            outs.setdefault((tag, build), []).append(out)
+            srcs.setdefault(tag, set()).add(os.path.basename(src))
+            jobs.append([HIPCC] + COMMON + flags + [src, "-o", out])
     with ThreadPoolExecutor(jobs_n) as ex:
         if any(ex.map(lambda c: subprocess.run(c).returncode, jobs)):
             sys.exit("compile failed")
-    pooled = {}
-    for tag, files in outs.items():
-        fns = {}
+    pool = {}
+    for (tag, build), files in outs.items():
+        fns, n = {}, 0
         for f in files:
-            fns.update(functions(f))
+            one = functions(f)
+            n += len(one)
+            fns.update(one)
+        assert len(fns) == n, "one symbol in two objects"
         names = sorted(fns)
         plain = subprocess.run(["c++filt"], input="\n".join(n.split("#")[0] for n in names), capture_output=True,
                                text=True, check=True).stdout.split("\n")
-        pooled[tag] = {d + ("#descriptor" if n.endswith("#descriptor") else ""): fns[n] for n, d in zip(names, plain)}
-        assert len(pooled[tag]) == len(names), "two functions of one demangled name"
-    a, b = pooled["base"], pooled["tree"]
-    diff = [k for k in sorted(set(a) | set(b)) if a.get(k) != b.get(k)]
-    print("C-ABI layer, %s -> %s: functions and descriptors compared: %d, different: %d" % (
-        [os.path.basename(f)[5:-2] for f in outs["base"]], [os.path.basename(f)[5:-2] for f in outs["tree"]],
-        len(set(a) | set(b)), len(diff)))
-    for d in diff:
-        print("DIFF", d, "(only in %s)" % ("tree" if d not in a else "base") if (d in a) != (d in b) else "")
-    return 1 if diff else 0
+        mine = {build + "/" + d + ("#descriptor" if n.endswith("#descriptor") else ""): fns[n]
+                for n, d in zip(names, plain)}
+        assert len(mine) == len(names), "two functions of one demangled name"
+        pool.setdefault(tag, {}).update(mine)
+    return pool, {tag: sorted(s) for tag, s in srcs.items()}
 
 
 def main():
@@ -83,35 +100,16 @@ def main():
         os.makedirs(base)
         tar = subprocess.check_output(["git", "-C", HERE, "archive", args.rev, "pion_amd/csrc", "include"])
         subprocess.run(["tar", "-x", "-C", base], input=tar, check=True)
-        if args.abi:
-            return abi_layer((("base", base), ("tree", HERE)), tmp, args.j)
-        jobs = []
-        for tree, tag in ((base, "base"), (HERE, "tree")):
-            for mode, flags in MODES.items():
-                for eq in range(4):
-                    out = os.path.join(tmp, "%s_%s_%d.s" % (tag, mode, eq))
-                    jobs.append([HIPCC] + COMMON + flags + ["-DPION_EQSEL=%d" % eq,
-                                                              os.path.join(tree, "pion_amd", "csrc", "kernels_fp.hip"),
-                                                              "-o", out])
-        with ThreadPoolExecutor(args.j) as ex:
-            for rc in ex.map(lambda c: subprocess.run(c).returncode, jobs):
-                if rc:
-                    sys.exit("compile failed")
-        total = rows2 = 0
-        diff = []
-        for mode in MODES:
-            for eq in range(4):
-                a = functions(os.path.join(tmp, "base_%s_%d.s" % (mode, eq)))
-                b = functions(os.path.join(tmp, "tree_%s_%d.s" % (mode, eq)))
-                for k in sorted(set(a) | set(b)):
-                    total += 1
-                    rows2 += ("k_stage_rows2" in k and not k.endswith("#descriptor"))
-                    if a.get(k) != b.get(k):
-                        diff.append("%s/%d %s" % (mode, eq, k))
-    print("functions and descriptors compared: %d (k_stage_rows2 instances: %d), different: %d" % (total, rows2,
-                                                                                                 len(diff)))
+        pool, srcs = pooled((("base", base), ("tree", HERE)), args.abi, tmp, args.j)
+    a, b = pool["base"], pool["tree"]
+    names = sorted(set(a) | set(b))
+    diff = [k for k in names if a.get(k) != b.get(k)]
+    rows2 = sum("k_stage_rows2" in k and not k.endswith("#descriptor") for k in names)
+    print("%s%s -> %s: functions and descriptors compared: %d%s, different: %d" % (
+        "C-ABI layer, " if args.abi else "", srcs["base"], srcs["tree"], len(names),
+        "" if args.abi else " (k_stage_rows2 instances: %d)" % rows2, len(diff)))
     for d in diff:
-        print("DIFF", d)
+        print("DIFF", d, "(only in %s)" % ("tree" if d not in a else "base") if (d in a) != (d in b) else "")
     return 1 if diff else 0
 
 

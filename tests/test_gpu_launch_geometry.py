@@ -261,9 +261,15 @@ SHAPES = [
     # x boundaries: periodic (the xwrap ghost images), reflecting / outflow
     ("periodic_x_rem1", "euler_periodic", [63, 7, 5], {}, lambda p, R, t: t["rem"] == 1),
     ("reflect_outflow_rem31", "euler", [93, 5, 4], {}, lambda p, R, t: t["rem"] == 31),
-    # HLLD flag prepass: nga0 = nx + 4 = 0 and 1 (mod 62), nga1 not a multiple of 4
+    # HLLD flag prepass, dense kernel (9 all-cell planes): its x tiles (gx) at nga0 = nx + 4 = 62 and 63 and its y tiles
+    # (gy) at nga1 not a multiple of 4
     ("prepass_nga0_62", "glm", [58, 9, 5], {}, lambda p, R, t: (58 + 4) % 62 == 0 and (9 + 4) % 4),
     ("prepass_nga0_63", "mhd", [59, 9, 5], {}, lambda p, R, t: (59 + 4) % 62 == 1 and (9 + 4) % 4),
+    # ... and the marching kernel, which launch_prepass takes from PION_PREPASS_ZC = 16 all-cell planes up, at its
+    # 62-cells-per-wavefront x edges; without the screen every stage takes the dense path
+    # (their edge is checked on the configuration itself, in the test)
+    ("prepass_march_nga0_62", "glm", [58, 9, 12], {"PION_HLL_SCREEN": "0"}, lambda p, R, t: True),
+    ("prepass_march_nga0_63", "mhd", [59, 9, 12], {"PION_HLL_SCREEN": "0"}, lambda p, R, t: True),
     # the cell kernel at nx % 64 == 1 and ny % 4 == 1
     ("cell_kernel", "glm", [65, 5, 4], {"PION_STAGE_KERNEL": "cell"}, lambda p, R, t: True),
     ("cell_kernel_euler", "euler", [65, 9, 4], {"PION_STAGE_KERNEL": "cell"}, lambda p, R, t: True),
@@ -285,6 +291,9 @@ def _shape_case(kind, ng, strict):
 @pytest.mark.parametrize("name,kind,ng,env,edge", SHAPES, ids=[s[0] for s in SHAPES])
 def test_shape_strict_bitexact_vs_oracle(name, kind, ng, env, edge):
     cfg, P = _shape_case(kind, ng, 1)
+    if name.startswith("prepass_march"):
+        # PION_PREPASS_ZC = 16 all-cell planes (kernels_prepass.hip), and all-cell rows of 62 k or 62 k + 1 cells
+        assert cfg.ng[2] + 2 * cfg.nbc >= 16 and (cfg.ng[0] + 4) % 62 in (0, 1), ("the case is off its edge", name)
     if env.get("PION_STAGE_KERNEL") != "cell":
         p, R, t = _plan_for(cfg, True, env)
         assert edge(p, R, t), ("the case is off its edge", name, p, R, t)

@@ -284,7 +284,7 @@ def test_fused_dt_equals_dt_kernel(case, strict):
             fused = g.calc_dt()
             g.device_ptr(0)          # invalidates the cached minima -> next call runs k_dt
             kern = g.calc_dt()
-            # both builds: k_dt and the fused reduction call the same function (cell_dt, kernels_fp.hip), whose
+            # both builds: k_dt and the fused reduction call the same function (cell_dt, dev_sweep.h), whose
             # fast-build form spells its multiply-adds out -- a restart goes through k_dt and must continue bit for bit
             assert fused == kern, (fused, kern)
 
