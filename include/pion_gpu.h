@@ -178,6 +178,23 @@ int pion_gpu_unpack_ongrid(void *handle, int plane_lo, int plane_hi, void *dbuf)
 int pion_gpu_fits_images(void *handle, char names[][16], int *n);
 long pion_gpu_fits_count(void *handle, int planes);
 int pion_gpu_pack_fits(void *handle, int plane_lo, int plane_hi, void *dbuf);
+/* FITS input, the same rules run backwards (dev_output.h; the reference's DataIOFits::ReadData / read_fits_image,
+ * dataIO/dataio_fits.cpp:433-548, 865-929): the nvar PRIMITIVE images of the list above -- the derived ones are never
+ * read -- of planes [plane_lo, plane_hi) as a contiguous DEVICE buffer [nvar][planes][ny][nx] of
+ * pion_gpu_fits_prim_count(handle, planes) elements, every element the big-endian double as the file holds it.
+ *   pion_gpu_unpack_fits         swaps each element to a native double, multiplies Bx, By, Bz by 1/sqrt(4 pi) (a
+ *                                multiplication as in the reference: a B written and read back need not have the bits
+ *                                it started with; psi is not scaled) and stores it into the on-grid cell of BOTH P and
+ *                                Ph.  Ghost cells and other planes keep their bits.  Enqueued on the compute stream,
+ *                                returns at once; discards what pion_gpu_upload and pion_gpu_unpack_ongrid discard.
+ *                                Between steps only; a boundary update with assign != 0 must follow.  An element that
+ *                                is not finite, or that constants::equalD(x, -1.e99) holds for (the reference's null
+ *                                value), is stored all the same and counted in a device counter of the handle.
+ *   pion_gpu_unpack_fits_status  synchronises, returns the number of such elements since the last call and clears it.
+ * Both floating-point builds give the same bits.  EINVAL as for pion_gpu_pack_fits. */
+long pion_gpu_fits_prim_count(void *handle, int planes);
+int pion_gpu_unpack_fits(void *handle, int plane_lo, int plane_hi, const void *dbuf);
+int pion_gpu_unpack_fits_status(void *handle, long *nbad);
 /* adopt caller-owned device buffers (e.g. torch tensors) instead of internal ones;
  * both must hold nvar*ncell_all doubles */
 int pion_gpu_bind_device_state(void *handle, void *dP, void *dPh);

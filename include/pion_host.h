@@ -82,11 +82,11 @@ int pion_host_sim_write_snapshot(void *sim, const char *path);
  * Ptot do not.  The images are packed on the device, derived fields and byte order included (pion_gpu_pack_fits), and
  * leave it a chunk of planes at a time: host memory is two chunks.  divB reads the ghost cells the last boundary
  * update and halo exchange left.  Every rank writes its own file.  EINVAL and a text: more than five tracers, a path
- * that cannot be created.  Never exits.  Not read back: a restart reads PIONRAW2. */
+ * that cannot be created.  Never exits.  Read back by pion_host_sim_read_fits. */
 int pion_host_sim_write_fits(void *sim, const char *path);
 /* File type of the regular outputs of pion_host_sim_time_int (step 0, every output step or time, the final state):
  * PION_HOST_FILE_PIONRAW (the default) or PION_HOST_FILE_FITS, <base>_<rank, 4 digits>.<step, 8 digits>.fits.  The
- * checkpoints stay PIONRAW2: they are what a restart reads.  Cadence, the time-step clip and every dt are untouched.
+ * checkpoints stay PIONRAW2 (a restart reads either file type).  Cadence, the time-step clip and every dt are untouched.
  * EINVAL and a text: any other value. */
 #define PION_HOST_FILE_PIONRAW 0
 #define PION_HOST_FILE_FITS 1
@@ -114,6 +114,26 @@ int pion_host_snapshot_read_header(const char *path, pion_gpu_config *cfg, pion_
  * Never exits: a wrong magic, a missing key, truncated data, planes no file covers, files of different times all
  * return EINVAL and a text. */
 int pion_host_sim_read_snapshot(void *sim, const char *const *paths, int npaths);
+/* Header of a FITS file of pion_host_sim_write_fits' kind: the outputs of pion_host_snapshot_read_header (the same
+ * checks, made by the same function), data_offset = 0.  A primary header without pion_slab_lo / pion_slab_n describes
+ * a file that holds the whole slab axis.  Host only.  EINVAL and a text (pion_host_sim_last_error(NULL, .)): not a
+ * FITS file, a header without END, a missing key. */
+int pion_host_fits_read_header(const char *path, pion_gpu_config *cfg, pion_host_snapshot_info *info);
+/* Restart from FITS files (the reference's DataIOFits::ReadData / read_fits_image, dataIO/dataio_fits.cpp:433-548,
+ * 865-929): pion_host_sim_read_snapshot's contract word for word -- the same header checks, planes taken from the
+ * first file that holds them (M writers, N readers), the same fields of the loop set, a pending time-step request
+ * dropped, boundaries assigned and updated, sources and tables set up by the caller first.  What differs is the file:
+ * the nvar primitive images are found by EXTNAME, not by position (the derived images Eint / Temp, divB, Ptot are
+ * never read; HDUs and cards the reader does not know are skipped by the sizes their headers give), and enter the
+ * device as the big-endian bytes the file holds, a chunk of planes at a time (PION_SNAPSHOT_CHUNK_PLANES; host memory
+ * is two chunks): pion_gpu_unpack_fits swaps them and multiplies Bx, By, Bz by 1/sqrt(4 pi).  That is a multiplication,
+ * as in the reference: a B written and read back need not have the bits it started with; every other variable has.
+ * A primitive image a file does not hold is zeros, as in the reference: the call returns 0 and says so in
+ * pion_host_sim_last_error.  EINVAL and a text, never an exit: everything pion_host_sim_read_snapshot refuses; a needed
+ * image whose BITPIX is not -64 or whose NAXISn are not the header's extents; a data unit that runs past the end of
+ * the file; more than five tracers; any element that is not finite or is the reference's null value -1e99 (the text
+ * names their number; the state is then what the files held). */
+int pion_host_sim_read_fits(void *sim, const char *const *paths, int npaths);
 /* SimTime of the loop: out[0..5] = simtime, last_dt, next_optime, finishtime, starttime, (double) timestep */
 int pion_host_sim_get_time(void *sim, double *out6);
 

@@ -1,9 +1,11 @@
 // dev_output.h -- the rules of the FITS output (the reference's dataio_fits::OutputData, dataIO/dataio_fits.cpp:147-320,
 // and put_variable_into_data_array, :748-856), each stated once: which images a file holds and in what order, the value
 // of one image at one cell, the byte order of a stored value, and how the on-grid cells map to the image buffer.
+// At the end of the file the same rules for the read direction (DataIOFits::ReadData and read_fits_image, :433-548,
+// 865-929): which images a restart reads, what the state holds for a file element, which elements it refuses.
 // Plain __host__ __device__ functions of GridDesc and OutputCfg: the kernels of pion_output.hip run them on the device,
-// the host writer (pion_amd/host/fits_io.cpp) runs the same functions in a host loop for a backend without the
-// streaming entries.  Needs only GridDesc and the PION_* constants (the includer provides __host__ / __device__, as
+// the host writer and reader (pion_amd/host/fits_io.cpp) run the same functions in a host loop for a backend without
+// the streaming entries.  Needs only GridDesc and the PION_* constants (the includer provides __host__ / __device__, as
 // for dev_bc.h).
 //
 // Every function that does arithmetic is compiled without FMA contraction, in both builds and on the host: the images
@@ -209,6 +211,59 @@ PION_OUT_HD long out_row_buf(const OutGeom &q, const long im, const long planes,
 PION_OUT_HD long out_count(const OutputCfg &o, const OutGeom &q, const long planes)
 {
   return (long)out_nimage(o) * planes * q.rows * q.nx;
+}
+
+// ---- the read direction (the reference's DataIOFits::ReadData and read_fits_image, dataio_fits.cpp:433-548,
+// 865-929): a restart reads the nvar primitive images of out_image's list -- images 0 .. nvar-1, found by their
+// out_image_name -- and never the derived ones (:901-903).
+//
+// InputCfg: OutputCfg and what only a read needs.  OutputCfg keeps its layout: it is an argument of the pack kernels.
+struct InputCfg {
+  OutputCfg o;
+  double binv;   // 1.0 / sqrt(4.0 * M_PI), evaluated once on the host (the reference's `norm`, :911)
+};
+inline InputCfg in_cfg(const pion_gpu_config &c)
+{
+  InputCfg in;
+  in.o = out_cfg(c);
+  in.binv = 1.0 / std::sqrt(4.0 * M_PI);
+  return in;
+}
+
+// the inverse of out_be64: the double whose big-endian bytes are the 8 bytes of u in memory order
+PION_OUT_HD double in_be64(const unsigned long long u)
+{
+  const unsigned long long s = __builtin_bswap64(u);
+  double x;
+  __builtin_memcpy(&x, &s, sizeof x);
+  return x;
+}
+// the value the state holds for file element x of image im: B times binv (:911-916; a multiplication, so that a B
+// written and read back may differ from the one that was written in the last bit), everything else -- psi included --
+// as it is stored
+PION_OUT_HD double in_value(const InputCfg &in, const OutImage im, const double x)
+{
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+  return (im.kind == OUT_PRIM_B) ? x * in.binv : x;
+}
+// a file element no restart accepts: not finite, or the reference's null value -- constants::equalD(x, -1.e99)
+// (constants.cpp:48-70; :908-921).  The reference tests the element as the file holds it, before the B scaling.
+PION_OUT_HD bool in_rejected(const double x)
+{
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+  const double nulval = -1.e99, ax = fabs(x);
+  if (!(ax <= 1.7976931348623157e308)) return true;   // NaN or infinity
+  if (x == nulval) return true;
+  return (fabs(x - nulval) / (ax + fabs(nulval) + 1.0e-100)) < 1.0e-12;   // (|x| + 1e99 < 1e-100 never holds)
+}
+// the buffer of a read, [nvar][planes][rows][nx]: out_row_buf with the variable in place of the image
+PION_OUT_HD long in_count(const OutputCfg &o, const OutGeom &q, const long planes)
+{
+  return (long)o.nvar * planes * q.rows * q.nx;
 }
 
 }  // namespace pion

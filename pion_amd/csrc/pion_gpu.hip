@@ -406,6 +406,7 @@ void pion_gpu_destroy(void *handle)
   hipFree(h->dscr_list);
   hipFree(h->dscr_count);
   hipFree(h->ddE);
+  hipFree(h->dfits_bad);
   if (h->bstream) hipStreamDestroy(h->bstream);
   if (h->ev_pre) hipEventDestroy(h->ev_pre);
   if (h->ev_bdone) hipEventDestroy(h->ev_bdone);

@@ -99,6 +99,9 @@ struct Handle {
   const double *sum_arr = nullptr;
   bool sum_bc = false;
   bool last_prepass_screened = false;
+  // FITS read (pion_output.hip): rejected elements counted by k_unpack_fits since the last pion_gpu_unpack_fits_status;
+  // allocated at the first unpack
+  unsigned long long *dfits_bad = nullptr;
 };
 
 // the state arrays, the cell flags or the tables were written from outside the stages: what the last stage left

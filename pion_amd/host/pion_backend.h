@@ -67,6 +67,19 @@ typedef struct pion_backend {
    *                       is ongrid_to_host_end's */
   long (*fits_count)(void *handle, int planes);
   int (*fits_to_host_begin)(void *handle, int plane_lo, int plane_hi, int slot);
+  /* FITS input (fits_io.h): the nvar primitive images of planes [plane_lo, plane_hi) as [nvar][planes][ny][nx], every
+   * element big-endian as the file holds it (pion_gpu_unpack_fits' layout), through the same two staging slots.  These
+   * two entries are read ONLY inside sim_control_gpu::read_fits: a caller that never restarts from a FITS file may
+   * hand the loop a table that ends before them.  Both NULL: the reader takes the images whole, converts them on the
+   * host and goes through upload.
+   *   fits_from_host:   ongrid_from_host's contract -- wait until slot `slot` is free, have fill(ctx, buffer) write
+   *                     the chunk's bytes into its host buffer (non-zero: give up and return it), start the copy and
+   *                     the unpack into P and Ph (B rescaled, ghost cells untouched); returns without waiting
+   *   fits_read_status: wait for the unpacks; *nbad = elements that were not finite or the reference's null value
+   *                     since the last call (pion_gpu_unpack_fits_status) */
+  int (*fits_from_host)(void *handle, int plane_lo, int plane_hi, int slot, int (*fill)(void *ctx, double *host),
+                        void *ctx);
+  int (*fits_read_status)(void *handle, long *nbad);
 } pion_backend;
 
 /* the product's backend: libpion_gpu.so */

@@ -110,13 +110,22 @@ int staging_slot(void *h, int slot, long n, Staging **out)
   return 0;
 }
 hipStream_t compute_stream_of(void *h) { return (hipStream_t)pion_gpu_get_stream(h, 0); }
+// what a slot holds for a chunk of `planes` planes: the largest of the three buffers that pass through it, so that a
+// write and a read of either file type in turn do not reallocate it
+long slot_elems(void *h, int planes)
+{
+  long n = pion_gpu_ongrid_count(h, planes);
+  if (pion_gpu_fits_count(h, planes) > n) n = pion_gpu_fits_count(h, planes);
+  if (pion_gpu_fits_prim_count(h, planes) > n) n = pion_gpu_fits_prim_count(h, planes);
+  return n;
+}
 
 // pack (the variables of array `which`, or the FITS images of P) into the slot's device buffer, then copy
 int gpu_to_host_begin(void *h, bool fits, int which, int plane_lo, int plane_hi, int slot)
 {
   const long n = fits ? pion_gpu_fits_count(h, plane_hi - plane_lo) : pion_gpu_ongrid_count(h, plane_hi - plane_lo);
   Staging *st;
-  if (int rc = staging_slot(h, slot, n, &st)) return rc;
+  if (int rc = staging_slot(h, slot, n > 0 ? slot_elems(h, plane_hi - plane_lo) : n, &st)) return rc;
   if (int rc = fits ? pion_gpu_pack_fits(h, plane_lo, plane_hi, st->dev[slot])
                     : pion_gpu_pack_ongrid(h, which, plane_lo, plane_hi, st->dev[slot]))
     return rc;
@@ -151,20 +160,32 @@ int gpu_ongrid_to_host_end(void *h, int slot, const double **host)
   *host = st->host[slot];
   return 0;
 }
-int gpu_ongrid_from_host(void *h, int plane_lo, int plane_hi, int slot, int (*fill)(void *, double *), void *ctx)
+// fill the slot's host buffer, copy, then unpack (the variables as they are, or the big-endian elements of a FITS file)
+int gpu_from_host(void *h, bool fits, int plane_lo, int plane_hi, int slot, int (*fill)(void *, double *), void *ctx)
 {
   if (!fill) return PION_GPU_EINVAL;
-  const long n = pion_gpu_ongrid_count(h, plane_hi - plane_lo);
+  const long n = fits ? pion_gpu_fits_prim_count(h, plane_hi - plane_lo) : pion_gpu_ongrid_count(h, plane_hi - plane_lo);
   Staging *st;
-  if (int rc = staging_slot(h, slot, n, &st)) return rc;   // (waits for the slot's previous copy)
+  // (waits for the slot's previous copy)
+  if (int rc = staging_slot(h, slot, n > 0 ? slot_elems(h, plane_hi - plane_lo) : n, &st)) return rc;
   if (int rc = fill(ctx, st->host[slot])) return rc;
   hipStream_t s = compute_stream_of(h);
   if (hipMemcpyAsync(st->dev[slot], st->host[slot], (size_t)n * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
     return PION_GPU_EDEVICE;
-  if (int rc = pion_gpu_unpack_ongrid(h, plane_lo, plane_hi, st->dev[slot])) return rc;
+  if (int rc = fits ? pion_gpu_unpack_fits(h, plane_lo, plane_hi, st->dev[slot])
+                    : pion_gpu_unpack_ongrid(h, plane_lo, plane_hi, st->dev[slot]))
+    return rc;
   if (hipEventRecord(st->ev[slot], s) != hipSuccess) return PION_GPU_EDEVICE;
   st->busy[slot] = true;
   return 0;
+}
+int gpu_ongrid_from_host(void *h, int plane_lo, int plane_hi, int slot, int (*fill)(void *, double *), void *ctx)
+{
+  return gpu_from_host(h, false, plane_lo, plane_hi, slot, fill, ctx);
+}
+int gpu_fits_from_host(void *h, int plane_lo, int plane_hi, int slot, int (*fill)(void *, double *), void *ctx)
+{
+  return gpu_from_host(h, true, plane_lo, plane_hi, slot, fill, ctx);
 }
 void gpu_destroy(void *h)
 {
@@ -210,6 +231,8 @@ const pion_backend k_gpu = {
     gpu_ongrid_from_host,
     pion_gpu_fits_count,
     gpu_fits_to_host_begin,
+    gpu_fits_from_host,
+    pion_gpu_unpack_fits_status,
 };
 
 }  // namespace

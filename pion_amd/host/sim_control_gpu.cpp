@@ -1,6 +1,7 @@
 // sim_control_gpu.cpp -- see sim_control_gpu.h
 #include "sim_control_gpu.h"
 
+#include "fits_io.h"
 #include "slab_comm.h"
 #include "snapshot_io.h"
 
@@ -419,12 +420,26 @@ int pion_host_sim_read_snapshot(void *s, const char *const *paths, int npaths)
     return PION_GPU_EINVAL;
   }
 }
-int pion_host_snapshot_read_header(const char *path, pion_gpu_config *cfg, pion_host_snapshot_info *info)
+int pion_host_sim_read_fits(void *s, const char *const *paths, int npaths)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  try {
+    const int rc = c->read_fits(paths, npaths);
+    g_last_exception = c->io_error();   // on success: empty, or what the files lacked (an image set to zero)
+    return rc;
+  }
+  catch (const std::exception &e) {
+    g_last_exception = e.what();
+    return PION_GPU_EINVAL;
+  }
+}
+static int read_header(bool fits, const char *path, pion_gpu_config *cfg, pion_host_snapshot_info *info)
 {
   try {
     pion_host::snapshot_header hd;
     std::string err;
-    const int rc = pion_host::snapshot_read_header(path, hd, err);
+    const int rc = fits ? pion_host::fits_read_header(path, hd, nullptr, nullptr, err) : pion_host::snapshot_read_header(path, hd, err);
     if (rc) {
       g_last_exception = err;
       return rc;
@@ -437,6 +452,14 @@ int pion_host_snapshot_read_header(const char *path, pion_gpu_config *cfg, pion_
     g_last_exception = e.what();
     return PION_GPU_EINVAL;
   }
+}
+int pion_host_snapshot_read_header(const char *path, pion_gpu_config *cfg, pion_host_snapshot_info *info)
+{
+  return read_header(false, path, cfg, info);
+}
+int pion_host_fits_read_header(const char *path, pion_gpu_config *cfg, pion_host_snapshot_info *info)
+{
+  return read_header(true, path, cfg, info);
 }
 int pion_host_sim_get_time(void *s, double *out)
 {

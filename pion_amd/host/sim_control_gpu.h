@@ -83,8 +83,8 @@ class sim_control_gpu {
   // <base>_<rank, 4 digits>.<id, 8 digits>.pionraw
   std::string snapshot_name(long id) const;
   // SimPM.typeofop for the regular outputs of output_data(): PION_HOST_FILE_PIONRAW (the default) or
-  // PION_HOST_FILE_FITS (<base>_<rank, 4 digits>.<step, 8 digits>.fits).  Checkpoints stay PIONRAW2: they are what a
-  // restart reads.  EINVAL: any other value
+  // PION_HOST_FILE_FITS (<base>_<rank, 4 digits>.<step, 8 digits>.fits).  Checkpoints stay PIONRAW2 (a restart reads
+  // either: read_snapshot, read_fits).  EINVAL: any other value
   int set_output_filetype(int type);
   // the regular output of step `step`: its name and the writer the file type selects
   std::string output_name(long step) const;
@@ -97,6 +97,10 @@ class sim_control_gpu {
   // timestep, last_dt, next_optime, starttime, finishtime and min_timestep, then assigns and updates the boundaries as
   // Init does.  Wind sources, jets and cooling tables are set up by the caller first, as before Init.
   int read_snapshot(const char *const *paths, int npaths);
+  // the same restart from FITS files (fits_io.h): the primitive images, found by EXTNAME, unpacked on the device
+  // (B times 1/sqrt(4 pi)); an image a file lacks is zeros and a note in io_error(); an element that is not finite or
+  // is the reference's null value -1e99 is EINVAL
+  int read_fits(const char *const *paths, int npaths);
 
   // z-slab of a larger domain: exchange the z ghost planes after every boundary update (under the
   // interior part of the next stage) and min-reduce the time step over the ranks
@@ -134,6 +138,8 @@ class sim_control_gpu {
   // snapshot_io.cpp: what both writers share
   int snapshot_params(std::vector<snapshot_param> &out, long &slab_n);
   int stream_runs(int fd, bool fits, int nrun, long nloc, long plane, long off, long stride, const char *who);
+  // and what both restarts share: everything but the header reader and the meaning of an element
+  int read_files(const char *const *paths, int npaths, bool fits);
 };
 
 }  // namespace pion_host

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <sstream>
 
+#include "fits_io.h"
 #include "sim_control_gpu.h"
 #include "slab_comm.h"
 
@@ -224,6 +225,11 @@ int snapshot_read_header(const char *path, snapshot_header &hd, std::string &err
     err = std::string("snapshot header of ") + path + ": key 'pion_data_offset' is missing (header incomplete)";
     return PION_GPU_EINVAL;
   }
+  return snapshot_header_from_kv(path, hd, (long)pos, err);
+}
+
+int snapshot_header_from_kv(const char *path, snapshot_header &hd, long header_end, std::string &err)
+{
   for (const std::string &k : snapshot_header_keys())
     if (!hd.kv.count(k)) {
       err = std::string("snapshot header of ") + path + ": key '" + k + "' is missing";
@@ -277,7 +283,7 @@ int snapshot_read_header(const char *path, snapshot_header &hd, std::string &err
   I.data_offset = l;
   snprintf(I.outfile, sizeof I.outfile, "%s", hd.kv["outfile"].c_str());
   const int np = (c.ndim == 1) ? 1 : c.ng[c.ndim - 1];
-  bool sane = I.slab_lo >= 0 && I.slab_n >= 1 && I.slab_lo + I.slab_n <= np && I.data_offset >= (long)pos;
+  bool sane = I.slab_lo >= 0 && I.slab_n >= 1 && I.slab_lo + I.slab_n <= np && I.data_offset >= header_end;
   for (int a = 0; a < 3; a++) sane = sane && c.ng[a] >= 1;
   if (!sane) {
     err = std::string("snapshot header of ") + path + ": plane range, NGrid or data offset out of range";
@@ -465,28 +471,40 @@ int sim_control_gpu::write_snapshot(const char *path)
 namespace {
 struct FillCtx {
   int fd;
-  off_t off;          // data offset of the file
-  size_t frun;        // doubles of one variable in the file
-  size_t first;       // first double of the chunk inside a variable's run
-  size_t n;           // doubles of the chunk per variable
   int nvar;
+  size_t n;           // doubles of the chunk per variable
+  // byte offset in the file of the chunk's first double of each variable; < 0: the file has no image of that variable
+  // (a FITS file may lack one) and its run is zero bytes
+  off_t var_off[PION_MAX_NVAR];
 };
 int fill_chunk(void *p, double *dst)
 {
   const FillCtx *c = (const FillCtx *)p;
-  for (int v = 0; v < c->nvar; v++)
-    if (full_pread(c->fd, dst + (size_t)v * c->n, c->n * sizeof(double),
-                   c->off + (off_t)(((size_t)v * c->frun + c->first) * sizeof(double))))
-      return PION_GPU_EINVAL;
+  for (int v = 0; v < c->nvar; v++) {
+    if (c->var_off[v] < 0) memset(dst + (size_t)v * c->n, 0, c->n * sizeof(double));
+    else if (full_pread(c->fd, dst + (size_t)v * c->n, c->n * sizeof(double), c->var_off[v])) return PION_GPU_EINVAL;
+  }
   return 0;
 }
 }  // namespace
 
-int sim_control_gpu::read_snapshot(const char *const *paths, int npaths)
+int sim_control_gpu::read_snapshot(const char *const *paths, int npaths) { return read_files(paths, npaths, false); }
+int sim_control_gpu::read_fits(const char *const *paths, int npaths) { return read_files(paths, npaths, true); }
+
+// The restart from either file type: PIONRAW2 (fits false) or FITS (fits_io.h).  What differs is how a header is read,
+// where a variable's run lies in a file, and what an element is: the native double itself, or the big-endian file
+// element of dev_output.h's read rules -- converted by the backend's fits_from_host (k_unpack_fits), or, without that
+// entry, by fits_convert_run in a host loop.
+int sim_control_gpu::read_files(const char *const *paths, int npaths, bool fits)
 {
+  const std::string who = fits ? "read_fits" : "read_snapshot";
   io_error_.clear();
   if (!paths || npaths < 1) {
-    io_error_ = "read_snapshot: no files";
+    io_error_ = who + ": no files";
+    return PION_GPU_EINVAL;
+  }
+  if (fits && cfg.ntracer > 5) {   // (dataio_fits.cpp:157, as write_fits)
+    io_error_ = who + ": only accepts <= 5 tracers (this sim has " + std::to_string(cfg.ntracer) + ")";
     return PION_GPU_EINVAL;
   }
   Global G;
@@ -496,8 +514,12 @@ int sim_control_gpu::read_snapshot(const char *const *paths, int npaths)
 
   // every header: the same problem as this sim's, and the same moment as the first file's
   std::vector<snapshot_header> H((size_t)npaths);
+  std::vector<std::vector<long>> image_off((size_t)npaths);   // FITS: where each variable's data unit starts (-1: absent)
+  std::string note;                                           // FITS: the images a file lacks
   for (int i = 0; i < npaths; i++) {
-    if (int rc = snapshot_read_header(paths[i], H[i], io_error_)) return rc;
+    if (int rc = fits ? fits_read_header(paths[i], H[i], &image_off[i], &note, io_error_)
+                      : snapshot_read_header(paths[i], H[i], io_error_))
+      return rc;
     const pion_gpu_config &c = H[i].cfg;
     const char *bad = nullptr;
     if (c.ndim != cfg.ndim || c.coord_sys != cfg.coord_sys) bad = "gridndim / coord_sys";
@@ -511,19 +533,20 @@ int sim_control_gpu::read_snapshot(const char *const *paths, int npaths)
     for (int a = 0; a < cfg.ndim && !bad; a++)
       if (fabs(c.xmin[a] - G.xmin[a]) > 1.0e-9 * cfg.dx) bad = "Xmin";
     if (bad) {
-      io_error_ = std::string("read_snapshot: ") + paths[i] + " does not match this sim's configuration: " + bad;
+      io_error_ = who + ": " + paths[i] + " does not match this sim's configuration: " + bad;
       return PION_GPU_EINVAL;
     }
     const pion_host_snapshot_info &a = H[0].info, &b = H[i].info;
     if (a.t_sim != b.t_sim || a.t_step != b.t_step || a.last_dt != b.last_dt || a.next_optime != b.next_optime
         || a.t_start != b.t_start) {
-      io_error_ = std::string("read_snapshot: ") + paths[i] + " and " + paths[0] + " are of different moments of a run (t_sim, t_step, last_dt, pion_next_optime or t_start differ)";
+      io_error_ = who + ": " + paths[i] + " and " + paths[0] + " are of different moments of a run (t_sim, t_step, last_dt, pion_next_optime or t_start differ)";
       return PION_GPU_EINVAL;
     }
+    if (fits) continue;   // (fits_read_header has sized every data unit against the file)
     struct stat st;
     const long need = b.data_offset + (long)cfg.nvar * b.slab_n * plane * (long)sizeof(double);
     if (stat(paths[i], &st) != 0 || (long)st.st_size < need) {
-      io_error_ = std::string("read_snapshot: ") + paths[i] + " is truncated: its header promises " + std::to_string(need) + " bytes";
+      io_error_ = who + ": " + paths[i] + " is truncated: its header promises " + std::to_string(need) + " bytes";
       return PION_GPU_EINVAL;
     }
   }
@@ -536,7 +559,7 @@ int sim_control_gpu::read_snapshot(const char *const *paths, int npaths)
     }
   for (long p = 0; p < nloc; p++)
     if (owner[p] < 0) {
-      io_error_ = "read_snapshot: plane " + std::to_string(G.slab_lo + p) + " of the slab axis is in none of the files given";
+      io_error_ = who + ": plane " + std::to_string(G.slab_lo + p) + " of the slab axis is in none of the files given";
       return PION_GPU_EINVAL;
     }
 
@@ -544,7 +567,10 @@ int sim_control_gpu::read_snapshot(const char *const *paths, int npaths)
   dt_requested_ = false;
   if (comm_) comm_->reset();
 
-  const bool stream = be_->ongrid_from_host && be_->ongrid_count;
+  // (the two FITS entries of the table are read here and nowhere else: pion_backend.h)
+  const bool stream = fits ? (be_->ongrid_count && be_->fits_from_host && be_->fits_read_status)
+                           : (be_->ongrid_from_host && be_->ongrid_count);
+  long nbad = 0;   // FITS: rejected elements
   std::vector<double> A;   // the whole array with zero ghosts, when the backend cannot stream
   const long nb = cfg.nbc, nxa = cfg.ng[0] + 2 * nb, nya = (cfg.ndim >= 2) ? cfg.ng[1] + 2 * nb : 1,
              nza = (cfg.ndim == 3) ? cfg.ng[2] + 2 * nb : 1;
@@ -558,24 +584,33 @@ int sim_control_gpu::read_snapshot(const char *const *paths, int npaths)
     Fd f;
     f.fd = open(paths[i], O_RDONLY);
     if (f.fd < 0) {
-      io_error_ = std::string("read_snapshot: cannot open ") + paths[i];
-      return PION_GPU_EINVAL;
+      io_error_ = who + ": cannot open " + paths[i];
+      rc = PION_GPU_EINVAL;
+      break;
     }
     const pion_host_snapshot_info &I = H[i].info;
     FillCtx c;
-    c.fd = f.fd, c.off = I.data_offset, c.frun = (size_t)I.slab_n * plane, c.nvar = cfg.nvar;
+    c.fd = f.fd, c.nvar = cfg.nvar;
+    const size_t frun = (size_t)I.slab_n * plane;   // doubles of one variable in the file
+    // (a chunk of the primitive images of a FITS file has the size of a chunk of variables)
     const long cp = stream ? chunk_planes(be_->ongrid_count(h_, 1), p1 - p0) : p1 - p0;
     for (long a = p0; a < p1 && !rc; a += cp) {
       const long b = std::min(p1, a + cp);
-      c.first = (size_t)(G.slab_lo + a - I.slab_lo) * plane;
+      const size_t first = (size_t)(G.slab_lo + a - I.slab_lo) * plane;   // first double of the chunk inside a run
       c.n = (size_t)(b - a) * plane;
+      for (int v = 0; v < cfg.nvar; v++) {
+        if (!fits) c.var_off[v] = I.data_offset + (off_t)(((size_t)v * frun + first) * sizeof(double));
+        else c.var_off[v] = (image_off[i][v] < 0) ? -1 : (off_t)(image_off[i][v] + (long)(first * sizeof(double)));
+      }
       if (stream) {
-        rc = be_->ongrid_from_host(h_, (int)a, (int)b, slot, fill_chunk, &c);
+        rc = fits ? be_->fits_from_host(h_, (int)a, (int)b, slot, fill_chunk, &c)
+                  : be_->ongrid_from_host(h_, (int)a, (int)b, slot, fill_chunk, &c);
         slot ^= 1;
       }
       else {
         std::vector<double> R((size_t)cfg.nvar * c.n);
         rc = fill_chunk(&c, R.data());
+        for (int v = 0; fits && v < cfg.nvar && !rc; v++) nbad += fits_convert_run(cfg, v, &R[(size_t)v * c.n], c.n);
         for (int v = 0; v < cfg.nvar && !rc; v++) {
           size_t o = (size_t)v * c.n;
           for (long pl = a; pl < b; pl++)
@@ -588,15 +623,27 @@ int sim_control_gpu::read_snapshot(const char *const *paths, int npaths)
             }
         }
       }
-      if (rc) io_error_ = std::string("read_snapshot: reading the planes from ") + paths[i] + " failed: " + last_error();
+      if (rc) io_error_ = who + ": reading the planes from " + paths[i] + " failed: " + last_error();
     }
     p0 = p1;
   }
   if (!rc && !stream) {
     rc = be_->upload(h_, A.data());
-    if (rc) io_error_ = "read_snapshot: upload failed: " + last_error();
+    if (rc) io_error_ = who + ": upload failed: " + last_error();
+  }
+  if (fits && stream) {
+    // (after a failure too: the count of the chunks that were unpacked must not reach the next read)
+    const int rs = be_->fits_read_status(h_, &nbad);
+    if (!rc && rs) {
+      rc = rs;
+      io_error_ = who + ": reading the count of rejected elements failed: " + last_error();
+    }
   }
   if (rc) return rc;
+  if (nbad != 0) {
+    io_error_ = who + ": " + std::to_string(nbad) + " element(s) of the files are not finite or hold the null value -1e99";
+    return PION_GPU_EINVAL;
+  }
   const pion_host_snapshot_info &I = H[0].info;
   T.simtime = I.t_sim;
   T.timestep = I.t_step;
@@ -610,7 +657,8 @@ int sim_control_gpu::read_snapshot(const char *const *paths, int npaths)
   last_output_step_ = -1;
   // assign_boundary_data + TimeUpdateInternalBCs/ExternalBCs (sim_init.cpp:246-267)
   rc = update_boundaries(cfg.tm_ooa, cfg.tm_ooa, 1);
-  if (rc) io_error_ = "read_snapshot: boundary update failed: " + last_error();
+  if (rc) io_error_ = who + ": boundary update failed: " + last_error();
+  else io_error_ = note;   // not a failure: what the files lacked
   return rc;
 }
 

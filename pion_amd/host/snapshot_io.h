@@ -21,7 +21,9 @@
 // oracle's table) goes through its whole-array download / upload, ghosts stripped / embedded here.
 //
 // The members sim_control_gpu::write_snapshot / read_snapshot are defined in snapshot_io.cpp, and with them what the
-// FITS writer (fits_io.h) shares: the list of parameters (snapshot_params) and the streamed write loop (stream_runs).
+// FITS writer and reader (fits_io.h) share: the list of parameters (snapshot_params), the streamed write loop
+// (stream_runs), the checks of a header (snapshot_header_from_kv) and the whole restart but the meaning of a file
+// element (read_files).
 #ifndef PION_SNAPSHOT_IO_H
 #define PION_SNAPSHOT_IO_H
 
@@ -46,6 +48,10 @@ struct snapshot_header {
 
 // returns 0 or PION_GPU_EINVAL with a text in err; never throws
 int snapshot_read_header(const char *path, snapshot_header &hd, std::string &err);
+// hd.kv -> hd.cfg and hd.info with every check of a header, for both file types (the FITS reader of fits_io.h fills
+// hd.kv from the cards of the primary header); header_end: the byte the header's text ends at (pion_data_offset must
+// not lie before it)
+int snapshot_header_from_kv(const char *path, snapshot_header &hd, long header_end, std::string &err);
 // the header names every file carries, in file order
 const std::vector<std::string> &snapshot_header_keys();
 

@@ -29,25 +29,45 @@ class SnapshotInfo(C.Structure):
                 ("data_offset", C.c_long), ("outfile", C.c_char * 256)]
 
 
-def read_snapshot_header(path):
-    """pion_host_snapshot_read_header: (global cfg, dict of pion_host_snapshot_info); host only, needs no device"""
+def _read_header(entry, path):
     lib = load_host_library()
     cfg, info = abi.PionGpuConfig(), SnapshotInfo()
-    rc = lib.pion_host_snapshot_read_header(os.fsencode(path), C.byref(cfg), C.byref(info))
+    rc = getattr(lib, entry)(os.fsencode(path), C.byref(cfg), C.byref(info))
     if rc != 0:
         buf = C.create_string_buffer(600)
         lib.pion_host_sim_last_error(None, buf, 600)
-        raise ValueError("pion_host_snapshot_read_header rc=%d: %s" % (rc, buf.value.decode(errors="replace")))
+        raise ValueError("%s rc=%d: %s" % (entry, rc, buf.value.decode(errors="replace")))
     d = {k: getattr(info, k) for k, _ in SnapshotInfo._fields_}
     d["outfile"] = d["outfile"].decode()
     return cfg, d
+
+
+def read_snapshot_header(path):
+    """pion_host_snapshot_read_header: (global cfg, dict of pion_host_snapshot_info); host only, needs no device"""
+    return _read_header("pion_host_snapshot_read_header", path)
+
+
+def read_fits_header(path):
+    """pion_host_fits_read_header: the same of a FITS file (data_offset is 0)"""
+    return _read_header("pion_host_fits_read_header", path)
+
+
+def is_fits(path):
+    """True where the file begins as a FITS file does (SIMPLE  =), whatever its name; False where it begins otherwise
+    (the PIONRAW2 reader checks its own magic); None where it cannot be read (the C++ reader says so)"""
+    try:
+        with open(path, "rb") as f:
+            return f.read(9) == b"SIMPLE  ="
+    except OSError:
+        return None
 
 
 def load_host_library():
     global _host
     if _host is not None:
         return _host
-    path = os.path.join(_HERE, "host", "libpion_host.so")
+    # PION_HOST_LIB: an alternative build of the same library (A/B runs, with PION_GPU_LIB naming the one it was linked to)
+    path = os.environ.get("PION_HOST_LIB") or os.path.join(_HERE, "host", "libpion_host.so")
     if not os.path.exists(path):
         raise ImportError("%s not found: build it with `make -C pion_amd/host`" % path)
     abi.share_torch_hip_runtime()
@@ -81,6 +101,9 @@ def load_host_library():
     if hasattr(h, "pion_host_sim_write_fits"):   # (likewise)
         h.pion_host_sim_write_fits.argtypes = [C.c_void_p, C.c_char_p]
         h.pion_host_sim_set_output_filetype.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(h, "pion_host_sim_read_fits"):   # (likewise)
+        h.pion_host_sim_read_fits.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int]
+        h.pion_host_fits_read_header.argtypes = [C.c_char_p, C.POINTER(abi.PionGpuConfig), C.POINTER(SnapshotInfo)]
     h.pion_host_comm_unique_id.argtypes = [C.c_void_p]
     h.pion_host_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     h.pion_host_comm_destroy.argtypes = [C.c_void_p]
@@ -213,7 +236,7 @@ class HostSim:
 
     def write_fits(self, path):
         """the FITS file of this sim's on-grid cells, derived images included (pion_host_sim_write_fits);
-        pion_amd.fits.read loads it"""
+        pion_amd.fits.read loads it, restart() continues a run from it"""
         rc = self.lib.pion_host_sim_write_fits(self.s, os.fsencode(path))
         if rc != 0:
             raise RuntimeError("pion_host_sim_write_fits rc=%d: %s" % (rc, self.last_error()))
@@ -226,13 +249,26 @@ class HostSim:
             raise ValueError("pion_host_sim_set_output_filetype rc=%d: %s" % (rc, self.last_error()))
 
     def restart(self, paths):
-        """pion_host_sim_read_snapshot: restart from the file(s) that hold this sim's planes (one path or a list)"""
+        """restart from the file(s) that hold this sim's planes (one path or a list): PIONRAW2 files
+        (pion_host_sim_read_snapshot) or FITS files (pion_host_sim_read_fits), told apart by the first bytes of the
+        first file, not by its name; a list that mixes the two is an error.  Returns the note a FITS restart may leave
+        (an image a file lacked, set to zero), else an empty string."""
         if isinstance(paths, (str, bytes, os.PathLike)):
             paths = [paths]
+        if not paths:
+            raise RuntimeError("restart: no files")
+        kinds = [(p, k) for p, k in ((p, is_fits(p)) for p in paths) if k is not None]
+        fits = bool(kinds) and kinds[0][1]
+        for p, k in kinds[1:]:
+            if k != fits:
+                raise RuntimeError("restart: %s and %s are files of two types (FITS and PIONRAW2)"
+                                   % (os.fsdecode(kinds[0][0]), os.fsdecode(p)))
         arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
-        rc = self.lib.pion_host_sim_read_snapshot(self.s, arr, len(paths))
+        entry = "pion_host_sim_read_fits" if fits else "pion_host_sim_read_snapshot"
+        rc = getattr(self.lib, entry)(self.s, arr, len(paths))
         if rc != 0:
-            raise RuntimeError("pion_host_sim_read_snapshot rc=%d: %s" % (rc, self.last_error()))
+            raise RuntimeError("%s rc=%d: %s" % (entry, rc, self.last_error()))
+        return self.last_error() if fits else ""
 
     def get_time(self):
         """dict simtime, last_dt, next_optime, finishtime, starttime, timestep of the loop"""

@@ -87,6 +87,11 @@ def load_library():
         lib.pion_gpu_fits_count.argtypes = [C.c_void_p, C.c_int]
         lib.pion_gpu_fits_count.restype = C.c_long
         lib.pion_gpu_pack_fits.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(lib, "pion_gpu_unpack_fits"):   # (likewise)
+        lib.pion_gpu_fits_prim_count.argtypes = [C.c_void_p, C.c_int]
+        lib.pion_gpu_fits_prim_count.restype = C.c_long
+        lib.pion_gpu_unpack_fits.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        lib.pion_gpu_unpack_fits_status.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
     lib.pion_gpu_interface_flux.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
     lib.pion_gpu_cooling_update.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp]
     lib.pion_gpu_cooling_edot.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
@@ -115,6 +120,7 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_rows_windows", "pion_gpu_get_rows_windows",
     "pion_gpu_ongrid_count", "pion_gpu_pack_ongrid", "pion_gpu_unpack_ongrid",
     "pion_gpu_fits_images", "pion_gpu_fits_count", "pion_gpu_pack_fits",
+    "pion_gpu_fits_prim_count", "pion_gpu_unpack_fits", "pion_gpu_unpack_fits_status",
 ]
 
 
@@ -370,6 +376,23 @@ class GpuSim:
         [nimage][planes][ny][nx], every element a big-endian double (view it as dtype '>f8'), B and divB times
         sqrt(4 pi); enqueued on the compute stream.  Call it after update_bcs: divB reads ghost cells."""
         self._chk(self.lib.pion_gpu_pack_fits(self.h, plane_lo, plane_hi, C.c_void_p(dbuf_ptr)), "pack_fits")
+
+    def fits_prim_count(self, planes):
+        """pion_gpu_fits_prim_count: elements (8 bytes each) of the primitive images of `planes` planes"""
+        return self.lib.pion_gpu_fits_prim_count(self.h, int(planes))
+
+    def unpack_fits(self, plane_lo, plane_hi, dbuf_ptr):
+        """pion_gpu_unpack_fits: the big-endian elements [nvar][planes][ny][nx] of the primitive images at dbuf_ptr
+        into the on-grid cells of planes [plane_lo, plane_hi) of P and Ph, B times 1/sqrt(4 pi); ghost cells are left
+        alone; enqueued on the compute stream"""
+        self._chk(self.lib.pion_gpu_unpack_fits(self.h, plane_lo, plane_hi, C.c_void_p(dbuf_ptr)), "unpack_fits")
+
+    def unpack_fits_status(self):
+        """pion_gpu_unpack_fits_status: synchronises; the number of elements unpacked since the last call that were
+        not finite or the reference's null value -1e99 (the counter is cleared)"""
+        n = C.c_long(-1)
+        self._chk(self.lib.pion_gpu_unpack_fits_status(self.h, C.byref(n)), "unpack_fits_status")
+        return n.value
 
     def unpack_ongrid(self, plane_lo, plane_hi, dbuf_ptr):
         """pion_gpu_unpack_ongrid: the reverse, into P and Ph; ghost cells and other planes are left alone"""
