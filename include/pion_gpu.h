@@ -445,6 +445,15 @@ int pion_gpu_unpack_halo(void *handle, int which, int face, void *dbuf);
 int pion_gpu_interface_flux(void *handle, int n, int axis, double dt, const double *Pl,
                             const double *Pr, const double *aux, double *F, double *Pstar);
 
+/* The cell update of a stage for n independent cells, through the stage kernels' own device functions.
+ * P_out (n*nvar): FV_solver_*::CellAdvanceTime (solver_eqn_hydro_adi.cpp:372-448, solver_eqn_mhd_adi.cpp:452-504,
+ * :822-844) of (P_in, dU), both n*nvar, then grid_update_state_vector's T > MaxTemperature ceiling
+ * (time_integrator.cpp:926-932), with FV_dt = fv_dt and the GLM speeds of pion_gpu_set_glm_speeds.
+ * dt_out (n): CellTimeStep of P_in.  dU and P_out may both be NULL (no update), or dt_out (no time step).
+ * Returns PION_GPU_EPHYSICS, with the outputs written, when a cell's density came out <= 0. */
+int pion_gpu_cell_advance(void *handle, int n, double fv_dt, const double *P_in, const double *dU,
+                          double *P_out, double *dt_out);
+
 /* mp_only_cooling::TimeUpdateMP (microphysics/mp_only_cooling.cpp:167-218) for n
  * independent cells: P_in n*nvar, P_out n*nvar. */
 int pion_gpu_cooling_update(void *handle, int n, double dt, const double *P_in, double *P_out);

@@ -1,5 +1,5 @@
 // kernels.h -- launch interface between the C-ABI layer (pion_gpu.hip, pion_step.hip, pion_bc.hip) and the
-// floating-point kernels: kernels_fp.hip (stage, cooling source and flux test, one object per equation set),
+// floating-point kernels: kernels_fp.hip (stage, cooling source, flux and cell test, one object per equation set),
 // kernels_prepass.hip and kernels_dt.hip.  Each is compiled twice, once per floating-point mode, into namespaces
 // pion::fp_strict (-ffp-contract=off: bit-parity with the reference's x86-64 -O3 build) and pion::fp_fast (FMA
 // contraction allowed); pion_gpu_config::strict_fp selects at run time.
@@ -111,6 +111,14 @@ struct FluxTestArgs {
   FluxCtx fc;
 };
 
+// cell-update test seam (k_cell_test): n independent cells through the stage kernels' cell_update and cell_dt
+struct CellTestArgs {
+  int n, eqntype, ntracer;
+  const double *Pin, *dU;   // [n][nvar]; dU null: no update
+  double *Pout, *dt;        // [n][nvar], [n]; dt null: no time step
+  StageArgs st;             // as a stage launch fills it: fc, glm_damp, max_temp, g, cfl, errword
+};
+
 struct CoolTestArgs {
   int n, nvar;
   double dt, gamma;
@@ -140,6 +148,7 @@ struct CoolTestArgs {
   PION_PER_EQN(launch_stage, StageArgs)                            \
   PION_PER_EQN(launch_cooling_dE, StageArgs)                       \
   PION_PER_EQN(launch_flux_test, FluxTestArgs)                     \
+  PION_PER_EQN(launch_cell_test, CellTestArgs)                     \
   int launch_prepass(const PrepassArgs &a, hipStream_t s);         \
   int launch_dt(const DtArgs &a, hipStream_t s);                   \
   int launch_dt_mp(const DtArgs &a, hipStream_t s);                \

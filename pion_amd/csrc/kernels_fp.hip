@@ -16,7 +16,7 @@
 //              HBM sees: read the stencil state (cached re-reads), read the start-of-step
 //              state, write the new state.
 //   k_stage_rows2  the production form of the same stage (stage_rows2.h), k_cooling_dE its cooling source,
-//   k_flux_test    the interface-flux test seam.
+//   k_flux_test    the interface-flux test seam, k_cell_test the cell-update one.
 #include "dev_cooling.h"
 #include "kernels.h"
 
@@ -433,6 +433,32 @@ __global__ __launch_bounds__(256) void k_flux_test(const FluxTestArgs a)
 #include "stage_rows2.h"
 
 // ---------------------------------------------------------------------------
+// cell-update test seam: CellAdvanceTime + the temperature ceiling (the stage kernels' cell_update) and
+// CellTimeStep (cell_dt) on n independent cells
+// ---------------------------------------------------------------------------
+template <int EQ, int NTR>
+__global__ __launch_bounds__(256) void k_cell_test(const CellTestArgs a)
+{
+  constexpr int NV = Eqn<EQ, NTR>::NV;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  double P0[NV];
+#pragma unroll
+  for (int v = 0; v < NV; v++) P0[v] = a.Pin[(long)i * NV + v];
+  if (a.dU) {
+    double dU[NV], Pf[NV];
+#pragma unroll
+    for (int v = 0; v < NV; v++) dU[v] = a.dU[(long)i * NV + v];
+    int err = 0;
+    cell_update<EQ, NTR>(a.st, P0, dU, err, Pf);
+#pragma unroll
+    for (int v = 0; v < NV; v++) a.Pout[(long)i * NV + v] = Pf[v];
+    if (err) atomicOr(a.st.errword, err);
+  }
+  if (a.dt) a.dt[i] = cell_dt<EQ>(P0, a.st.g.ndim, a.st.fc.gamma, a.st.g.dx, a.st.cfl);
+}
+
+// ---------------------------------------------------------------------------
 // cooling source term, one thread per on-grid cell of the planes a stage launch updates:
 // calc_noRT_microphysics_dU (time_integrator.cpp:438-489) -> mp_only_cooling::TimeUpdateMP.  Only the
 // energy component of dU changes, so the kernel leaves dE = PtoU(p_new)[ERG] - PtoU(P)[ERG] (the same two
@@ -526,6 +552,13 @@ static int flux_go(const FluxTestArgs &a, hipStream_t s)
   return (int)hipGetLastError();
 }
 
+template <int EQ, int NTR>
+static int cell_go(const CellTestArgs &a, hipStream_t s)
+{
+  hipLaunchKernelGGL((k_cell_test<EQ, NTR>), dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}
+
 #define PION_SOLVER_CASES_HD(FN, EQ, NTR, A, S)          \
   switch (A.solver) {                                    \
     case 0: return FN<EQ, NTR, 0>(A, S);                 \
@@ -595,6 +628,15 @@ int PION_CAT(launch_flux_test_, PION_SUFFIX)(const FluxTestArgs &a, hipStream_t 
     case 0: PION_CASES(flux_go, PION_EQ, 0, a, s)
     case 1: PION_CASES(flux_go, PION_EQ, 1, a, s)
     case 2: PION_CASES(flux_go, PION_EQ, 2, a, s)
+    default: return -1;
+  }
+}
+int PION_CAT(launch_cell_test_, PION_SUFFIX)(const CellTestArgs &a, hipStream_t s)
+{
+  switch (a.ntracer) {
+    case 0: return cell_go<PION_EQ, 0>(a, s);
+    case 1: return cell_go<PION_EQ, 1>(a, s);
+    case 2: return cell_go<PION_EQ, 2>(a, s);
     default: return -1;
   }
 }

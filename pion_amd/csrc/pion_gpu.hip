@@ -672,6 +672,48 @@ int pion_gpu_interface_flux(void *handle, int n, int axis, double dt, const doub
   return 0;
 }
 
+int pion_gpu_cell_advance(void *handle, int n, double fv_dt, const double *P_in, const double *dU, double *P_out,
+                          double *dt_out)
+{
+  Handle *h = use(handle);
+  if (!h) return PION_GPU_EINVAL;
+  if (n <= 0 || !P_in || (dU == nullptr) != (P_out == nullptr) || (!dU && !dt_out)) {
+    h->err = "cell_advance: n > 0, P_in, and dU with P_out and / or dt_out required";
+    return PION_GPU_EINVAL;
+  }
+  DevBuf<double> bp, bu, bo, bt;
+  const size_t nb = sizeof(double) * (size_t)n * h->cfg.nvar;
+  CellTestArgs a{};
+  // fc, glm_damp, max_temp, cfl and the error word exactly as a full second-order stage of dt = fv_dt gets them
+  stage_physics(h, StageStep{fv_dt, h->cfg.sp_ooa, 1}, a.st);
+  a.n = n;
+  a.eqntype = h->cfg.eqntype;
+  a.ntracer = h->cfg.ntracer;
+  HCHECK(h, hipMalloc(&bp.p, nb));
+  HCHECK(h, hipMemcpy(bp.p, P_in, nb, hipMemcpyHostToDevice));
+  a.Pin = bp.p;
+  if (dU) {
+    HCHECK(h, hipMalloc(&bu.p, nb));
+    HCHECK(h, hipMalloc(&bo.p, nb));
+    HCHECK(h, hipMemcpy(bu.p, dU, nb, hipMemcpyHostToDevice));
+    a.dU = bu.p;
+    a.Pout = bo.p;
+  }
+  if (dt_out) {
+    HCHECK(h, hipMalloc(&bt.p, sizeof(double) * (size_t)n));
+    a.dt = bt.p;
+  }
+  const int rc = h->cfg.strict_fp ? fp_strict::launch_cell_test(a, h->stream) : fp_fast::launch_cell_test(a, h->stream);
+  if (rc != 0) {
+    h->err = "cell-update launch failed";
+    return PION_GPU_EDEVICE;
+  }
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  if (dU) HCHECK(h, hipMemcpy(P_out, bo.p, nb, hipMemcpyDeviceToHost));
+  if (dt_out) HCHECK(h, hipMemcpy(dt_out, bt.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+  return check_errword(h);
+}
+
 static int cool_go(Handle *h, int n, double dt, const double *Pin, double *Pout, const double *rho, const double *T,
                    double *edot)
 {

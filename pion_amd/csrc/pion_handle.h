@@ -139,6 +139,10 @@ void time_begin(Handle *h, int slot);
 inline void time_end(Handle *h, int slot) { time_begin(h, slot); }
 FluxCtx make_fluxctx(const Handle *h, double fv_dt);
 int check_errword(Handle *h);
+// a stage as the kernels see it, and everything of StageArgs that is the same for every part of it (pion_step.hip;
+// the cell-update test seam fills its arguments through it too)
+struct StageStep { double dt; int space_ooa, is_full_step; };   // dt: the stage's (= FV_dt)
+void stage_physics(const Handle *h, const StageStep &st, StageArgs &a);
 
 // get_mp_timescales_no_radiation (calc_timestep.cpp:445-459): EP.MP_timestep_limit 1, 2, 3 ask
 // mp_only_cooling::timescales for the cooling time (tc = true); 4 (recombination time only) gets 1e99

@@ -9,6 +9,35 @@
 using namespace pion;
 using namespace pion::impl;
 
+// everything of StageArgs that is the same for every part of a stage
+void impl::stage_physics(const Handle *h, const StageStep &st, StageArgs &a)
+{
+  const pion_gpu_config &cfg = h->cfg;
+  a.g = h->g;
+  a.flags = h->dflags;
+  a.hllflag = h->dhll;
+  a.eta = h->deta;
+  a.errword = h->derr;
+  a.fc = make_fluxctx(h, st.dt);
+  a.eqntype = cfg.eqntype;
+  a.ntracer = cfg.ntracer;
+  a.solver = cfg.solver;
+  a.space_ooa = st.space_ooa;
+  a.cooling = cfg.cooling;
+  a.dt = st.dt;
+  a.glm_damp = exp(-st.dt * h->glm_chyp * h->glm_cr);
+  a.max_temp = cfg.max_temp;
+  a.cool = h->cool;
+  a.use_march = h->use_march;
+  a.zslope_lds = h->zslope_lds;
+  a.plain_cells = any_wind(h) ? 0 : 1;
+  // periodic x: k_stage_rows2 writes the x ghost images of its rows (the boundary launch then skips them)
+  a.xwrap = (a.use_march != 0 && h->fuse_bc && cfg.bc_type[0] == PION_BC_PERIODIC
+             && cfg.bc_type[1] == PION_BC_PERIODIC && h->g.ng[0] >= 2 * h->g.nbc[0]) ? 1 : 0;
+  a.ncu = h->ncu;
+  a.cfl = cfg.cfl;
+}
+
 namespace {
 
 // halo planes of the slab axis (the last axis: z planes in 3-D, y rows in 2-D): buffer layout
@@ -132,7 +161,6 @@ struct StagePart {
   bool beside;
   bool whole() const { return first && last; }
 };
-struct StageStep { double dt; int space_ooa, is_full_step; };   // dt: the stage's (= FV_dt)
 
 // The three parts: a whole stage, the interior [nb, nz-nb), which reads no ghost plane of the slab axis, and both
 // strips [0, nb) and [nz-nb, nz), on the compute stream or beside it on `side`.  A 1-D grid has no slab axis and never
@@ -215,35 +243,6 @@ int stage_arrays(Handle *h, const StageStep &st, const double *S, StageArgs &a)
   // first-order scheme (OA1/OA1): stencil and destination coincide -> go through Ph
   if (st.is_full_step && S == h->dP) a.out = h->dPh;
   return 0;
-}
-
-// everything of StageArgs that is the same for every part of a stage
-void stage_physics(const Handle *h, const StageStep &st, StageArgs &a)
-{
-  const pion_gpu_config &cfg = h->cfg;
-  a.g = h->g;
-  a.flags = h->dflags;
-  a.hllflag = h->dhll;
-  a.eta = h->deta;
-  a.errword = h->derr;
-  a.fc = make_fluxctx(h, st.dt);
-  a.eqntype = cfg.eqntype;
-  a.ntracer = cfg.ntracer;
-  a.solver = cfg.solver;
-  a.space_ooa = st.space_ooa;
-  a.cooling = cfg.cooling;
-  a.dt = st.dt;
-  a.glm_damp = exp(-st.dt * h->glm_chyp * h->glm_cr);
-  a.max_temp = cfg.max_temp;
-  a.cool = h->cool;
-  a.use_march = h->use_march;
-  a.zslope_lds = h->zslope_lds;
-  a.plain_cells = any_wind(h) ? 0 : 1;
-  // periodic x: k_stage_rows2 writes the x ghost images of its rows (the boundary launch then skips them)
-  a.xwrap = (a.use_march != 0 && h->fuse_bc && cfg.bc_type[0] == PION_BC_PERIODIC
-             && cfg.bc_type[1] == PION_BC_PERIODIC && h->g.ng[0] >= 2 * h->g.nbc[0]) ? 1 : 0;
-  a.ncu = h->ncu;
-  a.cfl = cfg.cfl;
 }
 
 // The ranges as the kernels read them, the one place that knows the three encodings.  3-D: planes [kz0, kz1) and, if

@@ -93,6 +93,8 @@ def load_library():
         lib.pion_gpu_unpack_fits.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         lib.pion_gpu_unpack_fits_status.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
     lib.pion_gpu_interface_flux.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
+    if hasattr(lib, "pion_gpu_cell_advance"):   # (likewise)
+        lib.pion_gpu_cell_advance.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp]
     lib.pion_gpu_cooling_update.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp]
     lib.pion_gpu_cooling_edot.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     lib.pion_gpu_cooling_timescale.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
@@ -121,6 +123,7 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_ongrid_count", "pion_gpu_pack_ongrid", "pion_gpu_unpack_ongrid",
     "pion_gpu_fits_images", "pion_gpu_fits_count", "pion_gpu_pack_fits",
     "pion_gpu_fits_prim_count", "pion_gpu_unpack_fits", "pion_gpu_unpack_fits_status",
+    "pion_gpu_cell_advance",
 ]
 
 
@@ -411,6 +414,25 @@ class GpuSim:
         self._chk(self.lib.pion_gpu_interface_flux(self.h, n, axis, dt, _p(Pl), _p(Pr), _p(aux), _p(F), _p(Ps)),
                   "interface_flux")
         return F, Ps
+
+    def cell_advance(self, Pin, dU, fv_dt=0.0):
+        """pion_gpu_cell_advance: CellAdvanceTime + the temperature ceiling of n cells (Pin, dU: [n, nvar])"""
+        Pin = np.ascontiguousarray(Pin, dtype=np.float64)
+        dU = np.ascontiguousarray(dU, dtype=np.float64)
+        assert Pin.ndim == 2 and Pin.shape[1] == self.nvar and dU.shape == Pin.shape
+        out = np.zeros_like(Pin)
+        self._chk(self.lib.pion_gpu_cell_advance(self.h, Pin.shape[0], fv_dt, _p(Pin), _p(dU), _p(out), None),
+                  "cell_advance")
+        return out
+
+    def cell_timestep(self, Pin):
+        """pion_gpu_cell_advance, the time step alone: CellTimeStep of n cells"""
+        Pin = np.ascontiguousarray(Pin, dtype=np.float64)
+        assert Pin.ndim == 2 and Pin.shape[1] == self.nvar
+        out = np.zeros(Pin.shape[0])
+        self._chk(self.lib.pion_gpu_cell_advance(self.h, Pin.shape[0], 0.0, _p(Pin), None, None, _p(out)),
+                  "cell_timestep")
+        return out
 
     def cooling_update(self, Pin, dt):
         Pin = np.ascontiguousarray(Pin, dtype=np.float64)
