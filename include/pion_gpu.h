@@ -79,7 +79,13 @@ extern "C" {
 
 /* cooling functions of mp_only_cooling (microphysics/mp_only_cooling.h) */
 #define PION_COOL_NONE 0
-#define PION_COOL_WSS09_CIE_LINE_HEAT_COOL 8
+#define PION_COOL_KI02 2                     /* Koyama & Inutsuka (2002): no table, no curve */
+#define PION_COOL_SD93_CIE 4                 /* 4..7: a total-CIE curve the caller supplies, pion_gpu_set_cooling_curve */
+#define PION_COOL_SD93_PLUS_HEATING 5
+#define PION_COOL_WSS09_CIE_PLUS_HEATING 6
+#define PION_COOL_WSS09_CIE_ONLY_COOLING 7
+#define PION_COOL_WSS09_CIE_LINE_HEAT_COOL 8 /* tables, pion_gpu_set_cooling_tables */
+/* (3, Dalgarno & McCray: mp_only_cooling::Edot has no case for it and stops, mp_only_cooling.cpp:410-412 -- EINVAL) */
 
 /* cell flag bits (grid/cell_interface.h:83-121) */
 #define PION_CELL_ISGD 1
@@ -314,6 +320,21 @@ int pion_gpu_set_jet(void *handle, int jetradius, const double *jetstate);
 int pion_gpu_set_cooling_tables(void *handle, int nT, const double *T,
                                 const double *tabs, const double *slopes);
 
+/* The total-CIE cooling curve of EP.cooling = 4..7 (SD93 or WSS09; cooling_function_SD93CIE,
+ * microphysics/cooling_SD93_cie.cpp): n knots (log10 T, log10 Lambda), strictly increasing in log10 T and not
+ * necessarily uniform, with the natural-spline second-derivative coefficients c[n] that pion_host_build_cooling_curve
+ * computes (GSL's cspline representation, what setup_SD93_cie / setup_WSS09_CIE leave in the spline, :150-166, 611-627).
+ * Outside the knots the curve is extrapolated linearly in log-log space with min_slope below and max_slope above; the
+ * reference's choices are 8.0 below and the slope of the last interval above, (logL[n-1] - logL[n-2]) /
+ * (logT[n-1] - logT[n-2]) (:160-164, 621-625).  Evaluated per cell as cooling_rate_SD93CIE (:666-704) and combined as
+ * mp_only_cooling::Edot_* (microphysics/mp_only_cooling.cpp:424-482).  2 <= n <= 256 (the cooling kernels keep the
+ * curve in LDS); EINVAL for any other n, knots that do not increase, or a value that is not finite.  Discards the cached
+ * time step and the screen summary, as pion_gpu_set_cooling_tables does.  (PION_COOL_BISECT=1 in the environment: the
+ * device bisects even uniformly spaced knots, as it does for the tables; a cross-check.)  A stage, a time step or a cooling seam of a
+ * handle with cooling 4..7 and no curve is EINVAL with a text; 0, 2 and 8 need no curve. */
+int pion_gpu_set_cooling_curve(void *handle, int n, const double *logT, const double *logL, const double *c,
+                               double min_slope, double max_slope);
+
 /* ---- the hot path ------------------------------------------------------ */
 
 /* assign_update_bcs::TimeUpdateInternalBCs + TimeUpdateExternalBCs
@@ -457,8 +478,12 @@ int pion_gpu_cell_advance(void *handle, int n, double fv_dt, const double *P_in,
 /* mp_only_cooling::TimeUpdateMP (microphysics/mp_only_cooling.cpp:167-218) for n
  * independent cells: P_in n*nvar, P_out n*nvar. */
 int pion_gpu_cooling_update(void *handle, int n, double dt, const double *P_in, double *P_out);
-/* mp_only_cooling::Edot (:491-521) for n (rho,T) pairs */
+/* mp_only_cooling::Edot (:377-415; the handle's EP.cooling: :424-482, :491-521, cooling.cpp:373-399) for n (rho,T) pairs */
 int pion_gpu_cooling_edot(void *handle, int n, const double *rho, const double *T, double *edot);
+/* cooling_function_SD93CIE::cooling_rate_SD93CIE (cooling_SD93_cie.cpp:666-704) on the curve of
+ * pion_gpu_set_cooling_curve, through the cooling kernels' own function with the curve staged in LDS: lambda[i] =
+ * Lambda(T[i]) for n temperatures (infinity for T < 0 or a T that is not finite).  Any handle with a curve set. */
+int pion_gpu_cooling_curve_eval(void *handle, int n, const double *T, double *lambda);
 /* mp_only_cooling::timescales(P, gamma, tc=true, ...) (:333-368) for n independent cells: P_in n*nvar,
  * t_cool n doubles (1e99 below 1.1 MinT_allowed) */
 int pion_gpu_cooling_timescale(void *handle, int n, const double *P_in, double *t_cool);

@@ -158,6 +158,21 @@ double pion_host_cooling_rate_wss09(double T);
 double pion_host_hii_rrr(double T);
 double pion_host_hii_total_cooling(double T);
 
+/* ---- a total-CIE cooling curve supplied by the caller (EP.cooling = 4..7; pion_gpu_set_cooling_curve): knots
+ * (log10 T, log10 Lambda), 2 <= n <= 256, strictly increasing in log10 T, not necessarily uniform.
+ * build: the natural-spline second-derivative coefficients c_out[n] (GSL's cspline representation), what
+ *   cooling_function_SD93CIE's set-up leaves in its spline (microphysics/cooling_SD93_cie.cpp:150-166, 611-627).
+ * set / rate: a process-global curve and cooling_function_SD93CIE::cooling_rate_SD93CIE on it (:666-704):
+ *   HUGE_VAL for T < 0 or non-finite T, linear extrapolation in log-log space with min_slope below and max_slope
+ *   above the knots, the spline inside, exp(ln10 s).  The reference's slopes: 8.0 below, the slope of the last
+ *   interval above (:160-164, 621-625).
+ * read: a text file of two columns (log10 T, log10 Lambda), '#' starts a comment; -1 and a message in err for a file
+ *   that cannot be opened, a malformed line, fewer than 2 or more than min(max_n, 256) knots, unsorted knots. */
+int pion_host_build_cooling_curve(int n, const double *logT, const double *logL, double *c_out);
+int pion_host_cooling_curve_set(int n, const double *logT, const double *logL, double min_slope, double max_slope);
+double pion_host_cooling_curve_rate(double T);
+int pion_host_read_cooling_curve(const char *path, int max_n, double *logT, double *logL, int *n, char *err, int errlen);
+
 /* ---- stellar_wind_evolution::read_evolution_file (grid/stellar_wind_BC.cpp:1026-1100): two header lines, then rows
  * of 8 or 15 columns (time M L Teff Mdot vrot vcrit vinf [X_H X_He X_C X_N X_O X_Z X_D], cgs); a column a row lacks
  * keeps the previous row's value (0 at first), as sscanf leaves it untouched; lines without any number are skipped.

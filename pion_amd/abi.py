@@ -25,6 +25,7 @@ BC_NAMES = {
     "DMR": BC_DMACH, "slab": BC_SLAB, "axisymmetric": BC_AXISYMMETRIC, "jetreflect": BC_JETREFLECT,
 }
 COOL_NONE, COOL_WSS09_CIE_LINE_HEAT_COOL = 0, 8
+COOL_KI02, COOL_SD93_CIE, COOL_SD93_PLUS_HEATING, COOL_WSS09_CIE_PLUS_HEATING, COOL_WSS09_CIE_ONLY_COOLING = 2, 4, 5, 6, 7
 # cell flags
 CELL_ISGD, CELL_ISBD, CELL_ISDOMAIN, CELL_TIMESTEP, CELL_ISLEAF = 1, 2, 4, 8, 16
 # primitive / conserved indices (constants.h:256-281)

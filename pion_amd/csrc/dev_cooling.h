@@ -8,8 +8,17 @@
 //   Cash-Karp RK5   microphysics/integrator.cpp:42-84 (tableau), 285-392 (Step_RK5CK incl. the
 //                   first-order shortcut), 401-531 (Stepper_RKCK, BISECTION_STEPPER),
 //                   540-602 (Int_Adaptive_RKCK)
-// No transcendental function is evaluated per cell: the tables are built once on
+// For EP.cooling = 8 no transcendental function is evaluated per cell: the tables are built once on
 // the host and handed over through pion_gpu_set_cooling_tables.
+//
+// The other cooling functions of mp_only_cooling::Edot (mp_only_cooling.cpp:377-415) share everything but Edot:
+//   EP.cooling = 4..7  Edot_SD93CIE_cool, _heat_cool, Edot_WSS09CIE_cool, _heat_cool (:424-482) on a total-CIE curve the
+//                      caller supplies (pion_gpu_set_cooling_curve), evaluated as
+//                      cooling_function_SD93CIE::cooling_rate_SD93CIE (cooling_SD93_cie.cpp:666-704): log10 T, a
+//                      natural cubic spline in GSL's cspline representation, exp
+//   EP.cooling = 2     Koyama & Inutsuka (2002), CoolingFn::CoolingRate (cooling.cpp:333-336, 373-399)
+// They travel in a CoolForm (kernels.h) to kernel instances of their own; TimeUpdateMP, the Cash-Karp driver and
+// timescales below are templates on the type that holds the rate's constants and call the matching edot overload.
 #ifndef PION_DEV_COOLING_H
 #define PION_DEV_COOLING_H
 
@@ -53,12 +62,89 @@ struct Cooling {
     rate += 8.01e-12 * (c.tab[0 * NT + iT] + dT * c.slope[0 * NT + iT]) * rho2 * c.inv_Mu2_elec_H;
     return rate;
   }
+  // The interval of a CIE curve that holds x, x[0] <= x <= x[n-1]: the largest i in [0, n-2] with x[i] <= x, which is
+  // what gsl_interp_bsearch ends on (x[i] <= x < x[i+1], the last interval at the upper end).  Uniform knots: a first
+  // guess from the spacing, corrected against the knots themselves; else the bisection.
+  static PDEV int curve_interval(const CoolForm &f, const double x)
+  {
+    const int n = f.n;
+    int lo = 0;
+    if (f.inv_dx > 0.0) {
+      const double gi = fmin(fmax((x - f.x[0]) * f.inv_dx, 0.0), (double)(n - 2));
+      lo = (int)gi;
+      while (lo > 0 && f.x[lo] > x) lo--;
+      while (lo < n - 2 && !(f.x[lo + 1] > x)) lo++;
+    }
+    else {
+      int hi = n - 1;
+      while (hi > lo + 1) {
+        const int i = (hi + lo) / 2;
+        if (f.x[i] > x) hi = i;
+        else lo = i;
+      }
+    }
+    return lo;
+  }
+  // cooling_function_SD93CIE::cooling_rate_SD93CIE (cooling_SD93_cie.cpp:666-704) on the caller's curve; the spline
+  // polynomial in the expressions and order of the host evaluator (cooling_tables.cpp, Spline::eval = GSL's cspline)
+  static PDEV double curve_rate(const CoolForm &f, double T)
+  {
+    if (T < 0.0 || !isfinite(T)) return HUGE_VAL;
+    const int n = f.n;
+    double rate;
+    T = log10(T);
+    if (T > f.x[n - 1]) rate = f.y[n - 1] + f.max_slope * (T - f.x[n - 1]);
+    else if (T < f.x[0]) rate = f.y[0] + f.min_slope * (T - f.x[0]);
+    else {
+      const int i = curve_interval(f, T);
+      const double dx = f.x[i + 1] - f.x[i];
+      const double dy = f.y[i + 1] - f.y[i];
+      const double delx = T - f.x[i];
+      const double b_i = (dy / dx) - dx * (f.c[i + 1] + 2.0 * f.c[i]) / 3.0;
+      const double d_i = (f.c[i + 1] - f.c[i]) / (3.0 * dx);
+      rate = f.y[i] + delx * (b_i + delx * (f.c[i] + delx * d_i));
+    }
+    return exp(2.3025850929940459 * rate);  // pconst.ln10(), constants.h:44
+  }
+  // mp_only_cooling::Edot (mp_only_cooling.cpp:377-415), EP.cooling = 4..7: the four combinations of :424-482, each in
+  // the reference's statement order.  An infinite or NaN rate (T < 0 after an overshoot) goes back unchanged: the
+  // integrator's !isfinite branch halves the step on it.
+  static PDEV double edot(const CoolFormT<COOL_FORM_CURVE> &f, const double rho, const double T)
+  {
+    // (Lambda once, ahead of the uniform switch: the same values as the reference's four expressions, one inlined
+    // copy of the curve evaluation per call site instead of four)
+    const double L = curve_rate(f, T);
+    switch (f.flag) {
+      case 4:   // Edot_SD93CIE_cool :429
+        return -(rho * rho / f.Mu_elec / f.Mu_ion) * L;
+      case 5:   // Edot_SD93CIE_heat_cool :446-447
+        return (rho * rho) * (2.733e-21 * exp(-0.782991 * log(T)) / f.Mu_elec / f.Mu - L / f.Mu_elec / f.Mu_ion);
+      case 7:   // Edot_WSS09CIE_cool :463
+        return 2e-26 * rho / f.Mu - (rho * rho / f.Mu / f.Mu) * L;
+      default:  // 6: Edot_WSS09CIE_heat_cool :481
+        return (rho * rho) * (2.733e-21 * exp(-0.782991 * log(T)) / f.Mu_elec / f.Mu - L / f.Mu / f.Mu);
+    }
+  }
+  // EP.cooling = 2: -CoolingFn::CoolingRate(T, 0, rho/Mu, 0, 0) with WhichFunction = 2, Koyama & Inutsuka (2002) as
+  // corrected by Vazquez-Semadeni et al. (2007) (mp_only_cooling.cpp:387; cooling.cpp:333-336, 373-399; MinTemp = 5 K,
+  // cooling.cpp:110)
+  static PDEV double edot(const CoolFormT<COOL_FORM_KI02> &f, const double rho, const double T)
+  {
+    const double nH = rho / f.Mu;
+    if (T <= 0.0 || isnan(T) || isinf(T)) return -0.0;
+    double rate = 0.0;
+    if (T > 5.0) rate += nH * nH * (2.0e-19 * exp(-1.184e5 / (T + 1.0e3)) + 2.8e-28 * sqrt(T) * exp(-92.0 / T));
+    rate -= nH * 2.0e-26;
+    return -rate;
+  }
   // mp_only_cooling::dPdt
-  static PDEV double dPdt(const CoolDev &c, const double rho, const double gamma, const double E)
+  template <class C>
+  static PDEV double dPdt(const C &c, const double rho, const double gamma, const double E)
   {
     return edot(c, rho, E * (gamma - 1.0) * c.Mu_tot_over_kB / rho);
   }
-  static PDEV void step_rk5ck(const CoolDev &c, const double rho, const double gamma, const double p0,
+  template <class C>
+  static PDEV void step_rk5ck(const C &c, const double rho, const double gamma, const double p0,
                               const double dt, double *pf, double *dp)
   {
     const double b21 = 0.2, b31 = 3. / 40., b32 = 9. / 40., b41 = 0.3, b42 = -0.9, b43 = 1.2, b51 = -11. / 54.,
@@ -95,7 +181,8 @@ struct Cooling {
     *pf = p0 + c1 * k1 + c3 * k3 + c4 * k4 + c6 * k6;
     *dp = dc1 * k1 + dc3 * k3 + dc4 * k4 + dc5 * k5 + dc6 * k6;
   }
-  static PDEV int stepper_rkck(const CoolDev &c, const double rho, const double gamma, const double p0,
+  template <class C>
+  static PDEV int stepper_rkck(const C &c, const double rho, const double gamma, const double p0,
                                const double t0, const double htry, const double errtol, double *p1,
                                double *hdid, double *hnext)
   {
@@ -132,7 +219,8 @@ struct Cooling {
     }
     return rval;
   }
-  static PDEV int int_adaptive_rkck(const CoolDev &c, const double rho, const double gamma, const double p0,
+  template <class C>
+  static PDEV int int_adaptive_rkck(const C &c, const double rho, const double gamma, const double p0,
                                     const double t0, const double dt, const double errtol, double *pf)
   {
     double t = t0, p1 = p0, p2 = 0.0;
@@ -151,7 +239,8 @@ struct Cooling {
     return err;
   }
   // TimeUpdateMP: returns the new pressure (all other primitives are unchanged)
-  static PDEV double time_update(const CoolDev &c, const double rho, const double pg_in, const double dt,
+  template <class C>
+  static PDEV double time_update(const C &c, const double rho, const double pg_in, const double dt,
                                  const double g, int &errbits)
   {
     if (!isfinite(rho) || !isfinite(pg_in)) errbits |= ERR_COOLING;
@@ -165,7 +254,8 @@ struct Cooling {
     else if (Tf < c.MinT_allowed) pg *= c.MinT_allowed / (Tf);
     return pg;
   }
-  static PDEV double timescale(const CoolDev &c, const double rho, const double pg, const double gam)
+  template <class C>
+  static PDEV double timescale(const C &c, const double rho, const double pg, const double gam)
   {
     double Eint = pg / (gam - 1.0);
     double T = pg * c.Mu_tot_over_kB / rho;
@@ -177,6 +267,26 @@ struct Cooling {
     return mintime;
   }
 };
+
+
+// a CoolForm as a workgroup uses it: the CIE curve of EP.cooling = 4..7 staged in LDS (3 n doubles), as k_cooling_dE_form
+template <int FORM>
+PDEV void stage_form(const CoolForm &f, double *ccrv, CoolFormT<FORM> &cool)
+{
+  static_cast<CoolForm &>(cool) = f;
+  if constexpr (FORM == COOL_FORM_CURVE) {
+    const int n = f.n;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      ccrv[i] = f.x[i];
+      ccrv[n + i] = f.y[i];
+      ccrv[2 * n + i] = f.c[i];
+    }
+    __syncthreads();
+    cool.x = ccrv;
+    cool.y = ccrv + n;
+    cool.c = ccrv + 2 * n;
+  }
+}
 
 }  // namespace pion
 #endif

@@ -31,6 +31,24 @@ struct CoolDev {
   float lg0, inv_dlg;
 };
 
+// The cooling functions of mp_only_cooling other than the tabulated one (EP.cooling = 2, 4..7).  CoolDev and StageArgs
+// are by-value arguments of kernels whose code is pinned, so this travels as an argument of its own, to the kernel
+// instances of these forms only (DESIGN.md s6d on OutputCfg).
+enum { COOL_FORM_CURVE = 1, COOL_FORM_KI02 = 2 };
+struct CoolForm {
+  int flag;              // EP.cooling: 2 (KI02) or 4..7 (a uniform run-time switch within COOL_FORM_CURVE)
+  int n;                 // knots of the CIE curve (0 for KI02)
+  const double *x;       // [n] log10 T, strictly increasing
+  const double *y;       // [n] log10 Lambda
+  const double *c;       // [n] natural-spline second-derivative coefficients (GSL's cspline representation)
+  double min_slope, max_slope;   // linear extrapolation in log-log space below / above the knots
+  double inv_dx;         // uniformly spaced knots: 1 / spacing (first guess of the interval), else 0: bisect
+  double Mu, Mu_elec, Mu_ion;    // mean masses per H nucleus / electron / ion (mp_only_cooling.cpp:81-85)
+  double Mu_tot_over_kB, MinT_allowed, MaxT_allowed;   // as CoolDev's
+};
+template <int FORM>
+struct CoolFormT : CoolForm {};
+
 struct StageArgs {
   GridDesc g;
   const double *S;    // stencil state ("Ph")      [nvar][ncell]
@@ -143,10 +161,27 @@ struct CoolTestArgs {
     return -1;                                        \
   }
 
+// k_cooling_dE_form: the cooling source of EP.cooling = 2, 4..7
+#define PION_PER_EQN_FORM(FN)                                              \
+  int FN##_hd(const StageArgs &a, const CoolForm &f, hipStream_t s);       \
+  int FN##_mhd(const StageArgs &a, const CoolForm &f, hipStream_t s);      \
+  int FN##_glm(const StageArgs &a, const CoolForm &f, hipStream_t s);      \
+  inline int FN(const StageArgs &a, const CoolForm &f, hipStream_t s)      \
+  {                                                                        \
+    if (a.eqntype == EQEUL) return FN##_hd(a, f, s);                       \
+    if (a.eqntype == EQMHD) return FN##_mhd(a, f, s);                      \
+    if (a.eqntype == EQGLM) return FN##_glm(a, f, s);                      \
+    return -1;                                                             \
+  }
+
 #define PION_DECLARE_FP(NS)                                        \
   namespace NS {                                                   \
   PION_PER_EQN(launch_stage, StageArgs)                            \
+  PION_PER_EQN(launch_stage_dE, StageArgs)                         \
   PION_PER_EQN(launch_cooling_dE, StageArgs)                       \
+  PION_PER_EQN_FORM(launch_cooling_dE_form)                        \
+  int launch_dt_mp_form(const DtArgs &a, const CoolForm &f, hipStream_t s);   \
+  int launch_cool_form(const CoolTestArgs &a, const CoolForm &f, int what, hipStream_t s); \
   PION_PER_EQN(launch_flux_test, FluxTestArgs)                     \
   PION_PER_EQN(launch_cell_test, CellTestArgs)                     \
   int launch_prepass(const PrepassArgs &a, hipStream_t s);         \

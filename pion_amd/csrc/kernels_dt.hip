@@ -99,6 +99,40 @@ int launch_dt_mp(const DtArgs &a, hipStream_t s)
   return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// The cooling-time reduction for EP.cooling = 2, 4..7 (CoolForm; the CIE curve of 4..7 in LDS).  A kernel of its own
+// with k_dt_mp's loop restated, so that the code of that one stays what it was.  (The full reduction of these flags is
+// k_dt with do_mp = 0 followed by this kernel: pion_gpu_calc_dt_device.)
+// ---------------------------------------------------------------------------
+template <int FORM>
+__global__ __launch_bounds__(256) void k_dt_mp_form(const DtArgs a, const CoolForm f)
+{
+  __shared__ double ccrv[(FORM == COOL_FORM_CURVE) ? 3 * PION_COOL_NT_MAX : 1];
+  CoolFormT<FORM> cool;
+  stage_form<FORM>(f, ccrv, cool);
+  const long nc = a.g.ncell;
+  const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
+  double tmp = 1.0e99;
+  for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < non; k += (long)gridDim.x * blockDim.x) {
+    const long c = ongrid_cell(a.g, k);
+    const uint8_t fl = a.flags[c];
+    if (!(fl & 2) && (fl & 16)) {
+      const double t = Cooling::timescale(cool, a.Ph[0 * nc + c], a.Ph[1 * nc + c], a.gamma);
+      tmp = (t < tmp) ? t : tmp;
+    }
+  }
+  tmp = wave_min64(tmp);
+  if ((threadIdx.x & 63) == 0) atomicMin(&a.result[1], (unsigned long long)__double_as_longlong(tmp));
+}
+int launch_dt_mp_form(const DtArgs &a, const CoolForm &f, hipStream_t s)
+{
+  const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
+  long nb = (non + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  if (f.flag == 2) hipLaunchKernelGGL(k_dt_mp_form<COOL_FORM_KI02>, dim3((unsigned)nb), dim3(256), 0, s, a, f);
+  else hipLaunchKernelGGL(k_dt_mp_form<COOL_FORM_CURVE>, dim3((unsigned)nb), dim3(256), 0, s, a, f);
+  return (int)hipGetLastError();
+}
 int launch_dt(const DtArgs &a, hipStream_t s)
 {
   const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
@@ -135,6 +169,41 @@ __global__ void k_cool_timescale(const CoolTestArgs a)
   if (i >= a.n) return;
   const double *p = a.Pin + (long)i * a.nvar;
   a.edot[i] = Cooling::timescale(a.cool, p[0], p[1], a.gamma);
+}
+// the same seams for EP.cooling = 2, 4..7 (what: 0 TimeUpdateMP, 1 Edot, 2 timescales), and what = 3: the CIE curve
+// itself, edot[i] = Lambda(T[i]) through the kernels' own curve_rate (curve in LDS, as the production kernels hold it)
+template <int FORM>
+__global__ __launch_bounds__(256) void k_cool_form(const CoolTestArgs a, const CoolForm f, const int what)
+{
+  __shared__ double ccrv[(FORM == COOL_FORM_CURVE) ? 3 * PION_COOL_NT_MAX : 1];
+  CoolFormT<FORM> cool;
+  stage_form<FORM>(f, ccrv, cool);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  if (what == 0) {
+    int err = 0;
+    const double *p = a.Pin + (long)i * a.nvar;
+    double *o = a.Pout + (long)i * a.nvar;
+    for (int v = 0; v < a.nvar; v++) o[v] = p[v];
+    o[1] = Cooling::time_update(cool, p[0], p[1], a.dt, a.gamma, err);
+    if (err) atomicOr(a.errword, err);
+  }
+  else if (what == 1) a.edot[i] = Cooling::edot(cool, a.rho[i], a.T[i]);
+  else if (what == 2) {
+    const double *p = a.Pin + (long)i * a.nvar;
+    a.edot[i] = Cooling::timescale(cool, p[0], p[1], a.gamma);
+  }
+  else {
+    if constexpr (FORM == COOL_FORM_CURVE) a.edot[i] = Cooling::curve_rate(cool, a.T[i]);
+    else a.edot[i] = 0.0;
+  }
+}
+int launch_cool_form(const CoolTestArgs &a, const CoolForm &f, int what, hipStream_t s)
+{
+  if (what < 0 || what > 3 || (what == 3 && f.flag == 2)) return -1;
+  if (f.flag == 2) hipLaunchKernelGGL(k_cool_form<COOL_FORM_KI02>, dim3((a.n + 255) / 256), dim3(256), 0, s, a, f, what);
+  else hipLaunchKernelGGL(k_cool_form<COOL_FORM_CURVE>, dim3((a.n + 255) / 256), dim3(256), 0, s, a, f, what);
+  return (int)hipGetLastError();
 }
 int launch_cool_timescale(const CoolTestArgs &a, hipStream_t s)
 {

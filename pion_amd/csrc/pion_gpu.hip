@@ -196,7 +196,10 @@ int pion_gpu_create(const pion_gpu_config *cfg, int device, void **handle)
   // MHD: LF, FKJ98 linear, Roe, HLLD, HLL (exact/hybrid are fatal in riemannMHD.cpp:176-181)
   else if (!(cfg->solver == 0 || cfg->solver == 1 || cfg->solver == 4 || cfg->solver == 7 || cfg->solver == 8))
     return PION_GPU_EINVAL;
-  if (cfg->cooling != 0 && cfg->cooling != PION_COOL_WSS09_CIE_LINE_HEAT_COOL) return PION_GPU_EINVAL;
+  // mp_only_cooling's cooling functions (mp_only_cooling.cpp:93-115): 3 (DMcC) has no case in Edot (:377-415) and stops there
+  if (cfg->cooling != PION_COOL_NONE && cfg->cooling != PION_COOL_KI02
+      && !(cfg->cooling >= PION_COOL_SD93_CIE && cfg->cooling <= PION_COOL_WSS09_CIE_LINE_HEAT_COOL))
+    return PION_GPU_EINVAL;
   if (cfg->mp_timestep_limit < 0 || cfg->mp_timestep_limit > 4) return PION_GPU_EINVAL;  // calc_timestep.cpp:457
 
   Handle *h = new Handle;
@@ -333,7 +336,7 @@ int pion_gpu_create(const pion_gpu_config *cfg, int device, void **handle)
 
   // microphysics constants (mp_only_cooling.cpp:81-95,140-146; constants.h:53,64)
   const double m_p = 1.672621898e-24, kB = 1.38064852e-16;
-  const double Mu = 1.40 * m_p, Mu_tot = 0.609 * m_p, Mu_elec = 1.167 * m_p;
+  const double Mu = 1.40 * m_p, Mu_tot = 0.609 * m_p, Mu_elec = 1.167 * m_p, Mu_ion = 1.273 * m_p;
   h->Mu_tot_over_kB = Mu_tot / kB;
   memset(&h->cool, 0, sizeof h->cool);
   h->cool.inv_Mu2 = 1.0 / (Mu * Mu);
@@ -343,6 +346,14 @@ int pion_gpu_create(const pion_gpu_config *cfg, int device, void **handle)
   h->cool.MaxT_allowed = cfg->max_temp;
   if (h->cool.MinT_allowed < 1.0 || h->cool.MinT_allowed > 1.0e6) h->cool.MinT_allowed = 1.0;
   if (h->cool.MaxT_allowed < 1.0e2 || h->cool.MaxT_allowed > 3.0e10) h->cool.MaxT_allowed = 1.0e8;
+  memset(&h->form, 0, sizeof h->form);
+  h->form.flag = cfg->cooling;
+  h->form.Mu = Mu;
+  h->form.Mu_elec = Mu_elec;
+  h->form.Mu_ion = Mu_ion;
+  h->form.Mu_tot_over_kB = h->Mu_tot_over_kB;
+  h->form.MinT_allowed = h->cool.MinT_allowed;
+  h->form.MaxT_allowed = h->cool.MaxT_allowed;
 
   // eq_refvec after SetAvgState (eqns_hydro_adiabatic.cpp:437-453); only the Euler Riemann
   // solvers (riemann.cpp) read it
@@ -423,6 +434,7 @@ void pion_gpu_destroy(void *handle)
   hipFree(h->dcoolT);
   hipFree(h->dcooltab);
   hipFree(h->dcoolslope);
+  hipFree(h->dcurve);
   for (int s = 0; s < 4; s++)
     for (hipEvent_t e : h->ev[s]) hipEventDestroy(e);
   if (h->ev_packed_src) hipEventDestroy(h->ev_packed_src);
@@ -623,6 +635,57 @@ int pion_gpu_set_cooling_tables(void *handle, int nT, const double *T, const dou
   return 0;
 }
 
+int pion_gpu_set_cooling_curve(void *handle, int n, const double *logT, const double *logL, const double *c,
+                               double min_slope, double max_slope)
+{
+  Handle *h = use(handle);
+  if (!h) return PION_GPU_EINVAL;
+  state_changed(h);   // t_mp depends on the curve
+  if (n < 2 || n > PION_COOL_NT_MAX || !logT || !logL || !c) {
+    // (the cooling kernels keep the curve in LDS: 3 x PION_COOL_NT_MAX doubles)
+    h->err = "cooling curve: 2 <= n <= 256 knots required";
+    return PION_GPU_EINVAL;
+  }
+  bool ok = std::isfinite(min_slope) && std::isfinite(max_slope);
+  for (int i = 0; i < n && ok; i++)
+    ok = std::isfinite(logT[i]) && std::isfinite(logL[i]) && std::isfinite(c[i]) && (i == 0 || logT[i] > logT[i - 1]);
+  if (!ok) {
+    h->err = "cooling curve: knots must be finite and strictly increasing in log10 T, slopes finite";
+    return PION_GPU_EINVAL;
+  }
+  std::vector<double> buf(3 * (size_t)n);
+  for (int i = 0; i < n; i++) {
+    buf[i] = logT[i];
+    buf[n + i] = logL[i];
+    buf[2 * n + i] = c[i];
+  }
+  h->have_curve = false;
+  hipFree(h->dcurve);
+  h->dcurve = nullptr;
+  HCHECK(h, hipMalloc(&h->dcurve, sizeof(double) * buf.size()));
+  HCHECK(h, hipMemcpy(h->dcurve, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice));
+  // uniformly spaced knots?  Then the device guesses the interval from the spacing; the guess is corrected against
+  // the knots, so it only has to land near the truth.
+  h->form.inv_dx = 0.0;
+  {
+    const double inv = (n - 1) / (logT[n - 1] - logT[0]);
+    bool uni = std::isfinite(inv) && inv > 0.0;
+    for (int i = 0; i < n && uni; i++) uni = fabs((logT[i] - logT[0]) * inv - i) <= 0.25;
+    if (uni) h->form.inv_dx = inv;
+  }
+  if (const char *e = getenv("PION_COOL_BISECT")) {
+    if (atoi(e) != 0) h->form.inv_dx = 0.0;   // A/B and cross-check: always bisect
+  }
+  h->form.n = n;
+  h->form.x = h->dcurve;
+  h->form.y = h->dcurve + n;
+  h->form.c = h->dcurve + 2 * n;
+  h->form.min_slope = min_slope;
+  h->form.max_slope = max_slope;
+  h->have_curve = true;
+  return 0;
+}
+
 void *pion_gpu_get_stream(void *handle, int which)
 {
   Handle *h = use(handle);
@@ -717,8 +780,9 @@ int pion_gpu_cell_advance(void *handle, int n, double fv_dt, const double *P_in,
 static int cool_go(Handle *h, int n, double dt, const double *Pin, double *Pout, const double *rho, const double *T,
                    double *edot)
 {
-  if (!h->have_tables) {
-    h->err = "cooling tables not set";
+  const bool form = cool_is_form(h->cfg);
+  if (const char *m = form ? cool_missing(h) : (h->have_tables ? nullptr : "cooling tables not set")) {
+    h->err = m;
     return PION_GPU_EINVAL;
   }
   CoolTestArgs a;
@@ -742,12 +806,14 @@ static int cool_go(Handle *h, int n, double dt, const double *Pin, double *Pout,
     if (edot) {  // cooling time of each state (edot = the output array, n doubles)
       HCHECK(h, hipMalloc(&d2, sizeof(double) * (size_t)n));
       a.edot = d2;
-      rc = h->cfg.strict_fp ? fp_strict::launch_cool_timescale(a, h->stream) : fp_fast::launch_cool_timescale(a, h->stream);
+      if (form) rc = h->cfg.strict_fp ? fp_strict::launch_cool_form(a, h->form, 2, h->stream) : fp_fast::launch_cool_form(a, h->form, 2, h->stream);
+      else rc = h->cfg.strict_fp ? fp_strict::launch_cool_timescale(a, h->stream) : fp_fast::launch_cool_timescale(a, h->stream);
       HCHECK(h, hipStreamSynchronize(h->stream));
       HCHECK(h, hipMemcpy(edot, d2, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
     }
     else {
-      rc = h->cfg.strict_fp ? fp_strict::launch_cool_update(a, h->stream) : fp_fast::launch_cool_update(a, h->stream);
+      if (form) rc = h->cfg.strict_fp ? fp_strict::launch_cool_form(a, h->form, 0, h->stream) : fp_fast::launch_cool_form(a, h->form, 0, h->stream);
+      else rc = h->cfg.strict_fp ? fp_strict::launch_cool_update(a, h->stream) : fp_fast::launch_cool_update(a, h->stream);
       HCHECK(h, hipStreamSynchronize(h->stream));
       HCHECK(h, hipMemcpy(Pout, d1, nb, hipMemcpyDeviceToHost));
     }
@@ -762,7 +828,8 @@ static int cool_go(Handle *h, int n, double dt, const double *Pin, double *Pout,
     a.rho = d0;
     a.T = d1;
     a.edot = d2;
-    rc = h->cfg.strict_fp ? fp_strict::launch_cool_edot(a, h->stream) : fp_fast::launch_cool_edot(a, h->stream);
+    if (form) rc = h->cfg.strict_fp ? fp_strict::launch_cool_form(a, h->form, 1, h->stream) : fp_fast::launch_cool_form(a, h->form, 1, h->stream);
+    else rc = h->cfg.strict_fp ? fp_strict::launch_cool_edot(a, h->stream) : fp_fast::launch_cool_edot(a, h->stream);
     HCHECK(h, hipStreamSynchronize(h->stream));
     HCHECK(h, hipMemcpy(edot, d2, nb, hipMemcpyDeviceToHost));
   }
@@ -780,6 +847,36 @@ int pion_gpu_cooling_edot(void *handle, int n, const double *rho, const double *
 int pion_gpu_cooling_timescale(void *handle, int n, const double *P_in, double *t_cool)
 {
   return cool_go(use(handle), n, 0.0, P_in, nullptr, nullptr, nullptr, t_cool);
+}
+
+int pion_gpu_cooling_curve_eval(void *handle, int n, const double *T, double *lambda)
+{
+  Handle *h = use(handle);
+  if (!h) return PION_GPU_EINVAL;
+  if (!h->have_curve || n <= 0 || !T || !lambda) {
+    h->err = h->have_curve ? "cooling_curve_eval: n > 0, T and lambda required" : "cooling curve not set";
+    return PION_GPU_EINVAL;
+  }
+  CoolTestArgs a;
+  memset(&a, 0, sizeof a);
+  a.n = n;
+  DevBuf<double> bt, bl;
+  const size_t nb = sizeof(double) * (size_t)n;
+  HCHECK(h, hipMalloc(&bt.p, nb));
+  HCHECK(h, hipMalloc(&bl.p, nb));
+  HCHECK(h, hipMemcpy(bt.p, T, nb, hipMemcpyHostToDevice));
+  a.T = bt.p;
+  a.edot = bl.p;
+  CoolForm f = h->form;
+  f.flag = PION_COOL_WSS09_CIE_ONLY_COOLING;   // (any of 4..7: the curve instance)
+  const int rc = h->cfg.strict_fp ? fp_strict::launch_cool_form(a, f, 3, h->stream) : fp_fast::launch_cool_form(a, f, 3, h->stream);
+  if (rc != 0) {
+    h->err = "cooling-curve launch failed";
+    return PION_GPU_EDEVICE;
+  }
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  HCHECK(h, hipMemcpy(lambda, bl.p, nb, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int pion_gpu_enable_timing(void *handle, int on)

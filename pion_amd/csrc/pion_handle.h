@@ -61,6 +61,11 @@ struct Handle {
   CoolDev cool;
   double *dcoolT = nullptr, *dcooltab = nullptr, *dcoolslope = nullptr;
   bool have_tables = false;
+  // the cooling functions other than the tabulated one (EP.cooling = 2, 4..7): constants, and for 4..7 the caller's CIE
+  // curve (pion_gpu_set_cooling_curve) in dcurve [3][n]: knots, values, spline coefficients
+  CoolForm form;
+  double *dcurve = nullptr;
+  bool have_curve = false;
   // solver state
   double glm_chyp = 0.0, glm_cr = 0.0;
   double refvec_avg[PION_MAX_NVAR];
@@ -150,6 +155,21 @@ void stage_physics(const Handle *h, const StageStep &st, StageArgs &a);
 static inline bool mp_dt_limited(const pion_gpu_config &cfg)
 {
   return cfg.cooling != 0 && cfg.mp_timestep_limit >= 1 && cfg.mp_timestep_limit <= 3;
+}
+
+// EP.cooling = 2, 4..7: the kernel instances that take a CoolForm
+static inline bool cool_is_form(const pion_gpu_config &cfg)
+{
+  return cfg.cooling != 0 && cfg.cooling != PION_COOL_WSS09_CIE_LINE_HEAT_COOL;
+}
+// what a handle with cooling still lacks before anything may be launched (null: nothing).  Flag 8 needs its tables,
+// flags 4..7 their curve, KI02 nothing.
+static inline const char *cool_missing(const Handle *h)
+{
+  const int f = h->cfg.cooling;
+  if (f == PION_COOL_WSS09_CIE_LINE_HEAT_COOL && !h->have_tables) return "cooling tables not set";
+  if (f >= PION_COOL_SD93_CIE && f <= PION_COOL_WSS09_CIE_ONLY_COOLING && !h->have_curve) return "cooling curve not set";
+  return nullptr;
 }
 
 // device scratch of one call: freed on every return path

@@ -108,6 +108,13 @@ static bool stage_can_split(const Handle *h)
 static int launch_cooling_time(Handle *h, hipStream_t s)
 {
   const DtArgs d = dt_args(h, h->dP, 1);
+  if (cool_is_form(h->cfg)) {
+    time_begin(h, 3);
+    const int rc = h->cfg.strict_fp ? fp_strict::launch_dt_mp_form(d, h->form, s) : fp_fast::launch_dt_mp_form(d, h->form, s);
+    time_end(h, 3);
+    if (rc != 0) h->err = "cooling-time kernel launch failed";
+    return (rc != 0) ? PION_GPU_EDEVICE : 0;
+  }
   return fp_launch(h, 3, fp_strict::launch_dt_mp, fp_fast::launch_dt_mp, d, s, "cooling-time kernel launch failed");
 }
 
@@ -338,7 +345,8 @@ int stage_extras(Handle *h, const StageStep &st, const StagePart &pt, StageArgs 
               && ((h->g.ndim == 3 && h->g.nbc[2] >= 2) || h->g.ndim == 2) && a.out == h->dP;
   // the cooling time: not in the stage kernel's fused reduction but in its own launch behind the last part of the
   // stage (k_dt_mp, rate tables in LDS; PION_SPLIT_DT_MP=0: fused, A/B)
-  x.split_mp = x.fuse_dt && mp_dt_limited(cfg) && h->split_dt_mp;
+  // (EP.cooling = 2, 4..7: always split -- the stage kernels carry the tabulated rate only)
+  x.split_mp = x.fuse_dt && mp_dt_limited(cfg) && (h->split_dt_mp || cool_is_form(cfg));
   // pressure-range summary of the array this launch writes: whole stages of the rows kernel on a grid of ordinary
   // cells, rows per wavefront dividing the block height
   x.leave_sum = pt.whole() && h->dhll && h->screen_ok && a.plain_cells && a.rows >= 1 && cfg.cooling == 0
@@ -386,8 +394,8 @@ int stage_end(Handle *h, const StageStep &st, const StagePart &pt, const StageEx
 // One part of a stage, as the list of its steps, in the order their work goes onto the part's stream
 int stage_launch(Handle *h, const StageStep &st, const StagePart &pt)
 {
-  if (h->cfg.cooling != 0 && !h->have_tables) {
-    h->err = "cooling tables not set";
+  if (const char *m = cool_missing(h)) {
+    h->err = m;
     return PION_GPU_EINVAL;
   }
   // the stencil state: Ph.  At the start of a step Ph == P in every cell.
@@ -398,7 +406,26 @@ int stage_launch(Handle *h, const StageStep &st, const StagePart &pt)
   stage_physics(h, st, a);
   if (int rc = stage_ranges(h, pt, a)) return rc;
   stage_tiling(h, pt.r[0].n(), a);
-  if (h->cfg.cooling != 0 && a.use_march != 0) {
+  const bool form = cool_is_form(h->cfg);
+  if (form) {
+    // EP.cooling = 2, 4..7: the source always comes from its own launch, for the cell-per-thread kernel too (whole grid)
+    a.dE = h->ddE;
+    StageArgs ac = a;
+    if (a.use_march == 0) {
+      ac.kz0 = 0;
+      ac.kz1 = h->g.ng[2];
+      ac.kz2 = ac.kz3 = 0;
+    }
+    time_begin(h, 1);
+    const int rc = h->cfg.strict_fp ? fp_strict::launch_cooling_dE_form(ac, h->form, pt.stream)
+                                    : fp_fast::launch_cooling_dE_form(ac, h->form, pt.stream);
+    time_end(h, 1);
+    if (rc != 0) {
+      h->err = "cooling kernel launch failed";
+      return PION_GPU_EDEVICE;
+    }
+  }
+  else if (h->cfg.cooling != 0 && a.use_march != 0) {
     // calc_noRT_microphysics_dU as its own launch (thread per cell, full occupancy): dE per cell
     a.dE = h->ddE;
     if (int rc = fp_launch(h, 1, fp_strict::launch_cooling_dE, fp_fast::launch_cooling_dE, a, pt.stream,
@@ -417,7 +444,11 @@ int stage_launch(Handle *h, const StageStep &st, const StagePart &pt)
   }
   const char *const failed = "stage kernel launch failed (unsupported eqn/solver/tracer combination?)";
   h->launches_last_part = 0;
-  if (!stage_windowed(h)) {
+  if (form && a.use_march == 0) {
+    if (int rc = fp_launch(h, 0, fp_strict::launch_stage_dE, fp_fast::launch_stage_dE, a, pt.stream, failed)) return rc;
+    h->launches_last_part = 1;
+  }
+  else if (!stage_windowed(h)) {
     if (int rc = fp_launch(h, 0, fp_strict::launch_stage, fp_fast::launch_stage, a, pt.stream, failed)) return rc;
     h->launches_last_part = 1;
   }
@@ -466,14 +497,29 @@ int pion_gpu_calc_dt_device(void *handle, void **dptr)
 {
   Handle *h = use(handle);
   const DtArgs a = dt_args(h, h->ph_valid ? h->dPh : h->dP, mp_dt_limited(h->cfg) ? 1 : 0);
-  if (a.do_mp && !h->have_tables) {
-    h->err = "cooling tables not set";
+  if (const char *m = a.do_mp ? cool_missing(h) : nullptr) {
+    h->err = m;
     return PION_GPU_EINVAL;
   }
   if (!h->dt_cached) {
     // (after a full step through k_stage_rows2 the minima of the new state are already in ddt)
     HCHECK(h, hipMemcpyAsync(h->ddt, h->ddt_init, 2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if (int rc = fp_launch(h, 3, fp_strict::launch_dt, fp_fast::launch_dt, a, h->stream, "dt kernel launch failed"))
+    if (cool_is_form(h->cfg)) {
+      // EP.cooling = 2, 4..7: k_dt for the dynamics alone, then the cooling time of the same array from k_dt_mp_form
+      DtArgs d = a;
+      d.do_mp = 0;
+      if (int rc = fp_launch(h, 3, fp_strict::launch_dt, fp_fast::launch_dt, d, h->stream, "dt kernel launch failed"))
+        return rc;
+      if (a.do_mp) {
+        const int rc = h->cfg.strict_fp ? fp_strict::launch_dt_mp_form(a, h->form, h->stream)
+                                        : fp_fast::launch_dt_mp_form(a, h->form, h->stream);
+        if (rc != 0) {
+          h->err = "cooling-time kernel launch failed";
+          return PION_GPU_EDEVICE;
+        }
+      }
+    }
+    else if (int rc = fp_launch(h, 3, fp_strict::launch_dt, fp_fast::launch_dt, a, h->stream, "dt kernel launch failed"))
       return rc;
     h->dt_cached = true;
   }

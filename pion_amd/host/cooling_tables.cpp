@@ -15,6 +15,10 @@
 //
 // C-ABI (plain pointers), called by the host driver before pion_gpu_set_cooling_tables.
 #include <cmath>
+#include <cstdio>
+#include <fstream>
+#include <sstream>
+#include <string>
 #include <vector>
 
 #include "cooling_data.h"
@@ -137,9 +141,108 @@ struct Tables {
   }
 };
 
+// A total-CIE cooling curve handed over by the caller (EP.cooling = 4..7): the natural spline through (log10 T,
+// log10 Lambda) and the two linear extrapolations of cooling_function_SD93CIE (cooling_SD93_cie.cpp:160-164,
+// 621-625 set-up; :666-704 evaluation)
+struct Curve {
+  Spline s;
+  double min_slope = 0.0, max_slope = 0.0;
+  bool set = false;
+  double rate(double T) const
+  {
+    if (T < 0.0 || !std::isfinite(T) || !set) return HUGE_VAL;
+    const int n = (int)s.x.size();
+    double rate;
+    T = std::log10(T);
+    if (T > s.x[n - 1]) rate = s.y[n - 1] + max_slope * (T - s.x[n - 1]);
+    else if (T < s.x[0]) rate = s.y[0] + min_slope * (T - s.x[0]);
+    else rate = s.eval(T);
+    return std::exp(2.3025850929940459 * rate);  // pconst.ln10(), constants.h:44
+  }
+};
+Curve g_curve;
+
+bool curve_ok(int n, const double *logT, const double *logL)
+{
+  if (n < 2 || n > 256 || !logT || !logL) return false;
+  for (int i = 0; i < n; i++) {
+    if (!std::isfinite(logT[i]) || !std::isfinite(logL[i])) return false;
+    if (i > 0 && !(logT[i] > logT[i - 1])) return false;
+  }
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+// The natural-spline second-derivative coefficients c_out[n] (GSL's cspline representation, c[0] = c[n-1] = 0) of
+// the curve (logT[n], logL[n]); 2 <= n <= 256 knots, strictly increasing and finite, else -1.  What
+// cooling_function_SD93CIE's set-up leaves in its spline (cooling_SD93_cie.cpp:150-166, 611-627).
+int pion_host_build_cooling_curve(int n, const double *logT, const double *logL, double *c_out)
+{
+  if (!curve_ok(n, logT, logL) || !c_out) return -1;
+  Spline s;
+  s.init(logT, logL, n);
+  for (int i = 0; i < n; i++) c_out[i] = s.c[i];
+  return 0;
+}
+
+// the process-global curve pion_host_cooling_curve_rate evaluates (tests and fixtures: the one-argument evaluator is
+// what a double(double) rate-curve hook takes); -1 and the curve unset for bad input
+int pion_host_cooling_curve_set(int n, const double *logT, const double *logL, double min_slope, double max_slope)
+{
+  g_curve.set = false;
+  if (!curve_ok(n, logT, logL) || !std::isfinite(min_slope) || !std::isfinite(max_slope)) return -1;
+  g_curve.s.init(logT, logL, n);
+  g_curve.min_slope = min_slope;
+  g_curve.max_slope = max_slope;
+  g_curve.set = true;
+  return 0;
+}
+
+// cooling_function_SD93CIE::cooling_rate_SD93CIE (cooling_SD93_cie.cpp:666-704) on the curve set above: HUGE_VAL for
+// T < 0 or non-finite T (and with no curve set)
+double pion_host_cooling_curve_rate(double T) { return g_curve.rate(T); }
+
+// Text file of a curve: two columns, log10 T and log10 Lambda, one knot per line; '#' starts a comment, blank lines
+// are skipped.  Fills logT[], logL[] (max_n each) and *n.  Returns 0, or -1 and a message in err[errlen]: unreadable
+// file, a line that is not two finite numbers (or has more), fewer than 2 or more than max_n / 256 knots, knots not
+// strictly increasing.
+int pion_host_read_cooling_curve(const char *path, int max_n, double *logT, double *logL, int *n, char *err, int errlen)
+{
+  auto fail = [&](const std::string &m) {
+    if (err && errlen > 0) std::snprintf(err, (size_t)errlen, "%s", m.c_str());
+    return -1;
+  };
+  if (n) *n = 0;
+  if (!path || !logT || !logL || !n || max_n < 2) return fail("read_cooling_curve: bad arguments");
+  if (max_n > 256) max_n = 256;
+  std::ifstream f(path);
+  if (!f) return fail(std::string("cannot open ") + path);
+  std::string line;
+  int lineno = 0, k = 0;
+  while (std::getline(f, line)) {
+    lineno++;
+    const size_t hash = line.find('#');
+    if (hash != std::string::npos) line.erase(hash);
+    if (line.find_first_not_of(" \t\r\n") == std::string::npos) continue;
+    const std::string where = std::string(path) + ":" + std::to_string(lineno);
+    std::istringstream is(line);
+    double x, y;
+    std::string rest;
+    if (!(is >> x >> y) || (is >> rest)) return fail(where + ": expected two numbers (log10 T, log10 Lambda)");
+    if (!std::isfinite(x) || !std::isfinite(y)) return fail(where + ": non-finite value");
+    if (k > 0 && !(x > logT[k - 1])) return fail(where + ": log10 T must increase strictly");
+    if (k >= max_n) return fail(where + ": more than " + std::to_string(max_n) + " knots");
+    logT[k] = x;
+    logL[k] = y;
+    k++;
+  }
+  if (k < 2) return fail(std::string(path) + ": fewer than 2 knots");
+  *n = k;
+  return 0;
+}
 
 // mp_only_cooling::gen_mpoc_lookup_tables: T[nT], tabs[5][nT] = {rrhp, C_rrh, C_ffhe, C_fbdn, C_cie},
 // slopes[5][nT].  Returns 0.

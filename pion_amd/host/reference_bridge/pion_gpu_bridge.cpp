@@ -78,6 +78,12 @@ pion_gpu_bridge::pion_gpu_bridge(class SimParams &par, class GridBaseClass *grid
     if (t < 0) throw std::runtime_error("pion_gpu_bridge: boundary type not handled on the device");
     cfg_.bc_type[d] = t;
   }
+  // The device runs EP.cooling = 2 and 4..7 too, but 4..7 need the CIE curve, and the reference object keeps its spline
+  // arrays protected (cooling_function_SD93CIE::Tarray, Larray): this bridge cannot hand them over.  A build that can
+  // reach them calls pion_host_build_cooling_curve + pion_gpu_set_cooling_curve itself.
+  if (par.EP.cooling != 0 && par.EP.cooling != PION_COOL_WSS09_CIE_LINE_HEAT_COOL)
+    throw std::runtime_error("pion_gpu_bridge: cooling flag " + std::to_string(par.EP.cooling)
+                             + " is not translated (supported: 0 and 8)");
   cfg_.cooling = par.EP.cooling;
   cfg_.mp_timestep_limit = par.EP.MP_timestep_limit;
   cfg_.strict_fp = strict_fp;

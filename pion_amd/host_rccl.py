@@ -174,6 +174,13 @@ class HostSim:
     def gpu_handle(self):
         return self.lib.pion_host_sim_handle(self.s)
 
+    def set_cooling_curve(self, logT, logL, c, min_slope, max_slope):
+        """The total-CIE curve of EP.cooling = 4..7 (cooling.build_curve) on the loop's device handle: before init()
+        or restart(), as the tables of EP.cooling = 8."""
+        from . import lib as gpu_lib
+        gpu_lib.GpuSim(self.cfg, 0, borrowed_handle=self.gpu_handle()).set_cooling_curve(logT, logL, c, min_slope,
+                                                                                       max_slope)
+
     def init(self, P, simtime=0.0, finishtime=1e300, first_step_dt_limit=None, timestep=0, last_dt=1e100):
         """sim_init::Init; on a restart pass the snapshot's simtime / timestep / last_dt"""
         self.lib.pion_host_sim_set_time(self.s, int(timestep), float(last_dt))

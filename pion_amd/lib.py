@@ -65,6 +65,9 @@ def load_library():
         lib.pion_gpu_rows_windows.argtypes = [C.POINTER(abi.PionGpuConfig), C.c_long, C.c_int, C.c_int, C.c_int, _ip, _ip]
         lib.pion_gpu_get_rows_windows.argtypes = [C.c_void_p, C.POINTER(C.c_long), _ip, _ip]
     lib.pion_gpu_set_cooling_tables.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+    if hasattr(lib, "pion_gpu_set_cooling_curve"):   # (likewise)
+        lib.pion_gpu_set_cooling_curve.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, C.c_double]
+        lib.pion_gpu_cooling_curve_eval.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
     lib.pion_gpu_update_bcs.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int]
     lib.pion_gpu_calc_dt.argtypes = [C.c_void_p, _dp, _dp]
     lib.pion_gpu_set_glm_speeds.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
@@ -109,7 +112,7 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_create", "pion_gpu_destroy", "pion_gpu_last_error", "pion_gpu_ncell_all",
     "pion_gpu_ng_all", "pion_gpu_upload", "pion_gpu_download", "pion_gpu_bind_device_state",
     "pion_gpu_device_ptr", "pion_gpu_set_stream", "pion_gpu_synchronize", "pion_gpu_set_wind_cells",
-    "pion_gpu_set_cooling_tables", "pion_gpu_update_bcs", "pion_gpu_calc_dt",
+    "pion_gpu_set_cooling_tables", "pion_gpu_set_cooling_curve", "pion_gpu_cooling_curve_eval", "pion_gpu_update_bcs", "pion_gpu_calc_dt",
     "pion_gpu_set_glm_speeds", "pion_gpu_stage", "pion_gpu_advance_time", "pion_gpu_halo_count",
     "pion_gpu_pack_halo", "pion_gpu_unpack_halo", "pion_gpu_interface_flux",
     "pion_gpu_cooling_update", "pion_gpu_cooling_edot", "pion_gpu_cooling_timescale", "pion_gpu_enable_timing",
@@ -307,6 +310,16 @@ class GpuSim:
         self._chk(self.lib.pion_gpu_set_cooling_tables(self.h, T.size, _p(T), _p(tabs), _p(slopes)),
                   "set_cooling_tables")
 
+    def set_cooling_curve(self, logT, logL, c, min_slope, max_slope):
+        """The total-CIE curve of EP.cooling = 4..7, as cooling.build_curve returns it."""
+        logT = np.ascontiguousarray(logT, dtype=np.float64)
+        logL = np.ascontiguousarray(logL, dtype=np.float64)
+        c = np.ascontiguousarray(c, dtype=np.float64)
+        if not (logT.shape == logL.shape == c.shape and logT.ndim == 1):
+            raise ValueError("logT, logL and c must be 1-D arrays of one length")
+        self._chk(self.lib.pion_gpu_set_cooling_curve(self.h, logT.size, _p(logT), _p(logL), _p(c), float(min_slope),
+                                                      float(max_slope)), "set_cooling_curve")
+
     # --- the hot path
     def update_bcs(self, simtime=0.0, cstep=2, maxstep=2, assign=0):
         self._chk(self.lib.pion_gpu_update_bcs(self.h, simtime, cstep, maxstep, assign), "update_bcs")
@@ -445,6 +458,13 @@ class GpuSim:
         T = np.ascontiguousarray(T, dtype=np.float64)
         out = np.zeros_like(rho)
         self._chk(self.lib.pion_gpu_cooling_edot(self.h, rho.size, _p(rho), _p(T), _p(out)), "cooling_edot")
+        return out
+
+    def cooling_curve_eval(self, T):
+        """Lambda(T) of the curve set by set_cooling_curve, through the cooling kernels' own function"""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        out = np.zeros_like(T)
+        self._chk(self.lib.pion_gpu_cooling_curve_eval(self.h, T.size, _p(T), _p(out)), "cooling_curve_eval")
         return out
 
     def cooling_timescale(self, Pin):
