@@ -275,6 +275,10 @@ int pion_gpu_get_flags(void *handle, unsigned char *out);
 /* The HLLD -> HLL switch of every cell (ncell_all bytes, ghosts included) as the prepass of the last stage left it
  * (synchronises; read-only).  EINVAL for a handle without the switch (not MHD / GLM with HLLD). */
 int pion_gpu_get_hll_switch(void *handle, unsigned char *out);
+/* The H-correction eta of every cell along `axis` (ncell_all doubles, ghosts included; the value of interface
+ * (c | c+1 along axis) is stored at c, the last cell of a column holds 0) as the prepass of the last stage left it
+ * (synchronises; read-only).  EINVAL for a handle without the H-correction (artvisc 3 / 4) or axis outside 0..ndim-1. */
+int pion_gpu_get_hcorr_eta(void *handle, int axis, double *out);
 /* The screened prepass (3-D MHD / GLM with HLLD; PION_HLL_SCREEN=0 in the environment switches it off): number of
  * blocks of cells the last stage's prepass evaluated, and number of blocks.  active = -1, total = 0 when that prepass
  * was the dense one.  Synchronises: call it outside timed regions. */

@@ -576,6 +576,16 @@ int pion_gpu_get_hll_switch(void *handle, unsigned char *out)
   return 0;
 }
 
+int pion_gpu_get_hcorr_eta(void *handle, int axis, double *out)
+{
+  Handle *h = use(handle);
+  if (!h || !out || !h->deta || axis < 0 || axis >= h->g.ndim) return PION_GPU_EINVAL;
+  HCHECK(h, hipMemcpyAsync(out, h->deta + (size_t)axis * h->g.ncell, sizeof(double) * h->g.ncell, hipMemcpyDeviceToHost,
+                           h->stream));
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int pion_gpu_get_hll_screen_counts(void *handle, int *active, int *total)
 {
   Handle *h = use(handle);

@@ -60,6 +60,8 @@ def load_library():
     if hasattr(lib, "pion_gpu_get_hll_switch"):   # (a PION_GPU_LIB build for A/B runs may predate these two read-backs)
         lib.pion_gpu_get_hll_switch.argtypes = [C.c_void_p, C.c_void_p]
         lib.pion_gpu_get_hll_screen_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(lib, "pion_gpu_get_hcorr_eta"):   # (likewise)
+        lib.pion_gpu_get_hcorr_eta.argtypes = [C.c_void_p, C.c_int, _dp]
     if hasattr(lib, "pion_gpu_rows_windows"):   # (likewise)
         _ip = C.POINTER(C.c_int)
         lib.pion_gpu_rows_windows.argtypes = [C.POINTER(abi.PionGpuConfig), C.c_long, C.c_int, C.c_int, C.c_int, _ip, _ip]
@@ -122,7 +124,7 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_add_wind_source", "pion_gpu_get_wind_cells", "pion_gpu_get_wind_source_pos",
     "pion_gpu_wind_orbit_position", "pion_gpu_get_flags", "pion_gpu_add_rotating_wind_source",
     "pion_gpu_wind_angle_tables", "pion_gpu_get_hll_switch", "pion_gpu_get_hll_screen_counts",
-    "pion_gpu_rows_windows", "pion_gpu_get_rows_windows",
+    "pion_gpu_get_hcorr_eta", "pion_gpu_rows_windows", "pion_gpu_get_rows_windows",
     "pion_gpu_ongrid_count", "pion_gpu_pack_ongrid", "pion_gpu_unpack_ongrid",
     "pion_gpu_fits_images", "pion_gpu_fits_count", "pion_gpu_pack_fits",
     "pion_gpu_fits_prim_count", "pion_gpu_unpack_fits", "pion_gpu_unpack_fits_status",
@@ -284,6 +286,13 @@ class GpuSim:
         """pion_gpu_get_hll_switch: the HLLD -> HLL switch per cell as the last stage's prepass left it (uint8, ncell_all)"""
         out = np.zeros(self.ncell, dtype=np.uint8)
         self._chk(self.lib.pion_gpu_get_hll_switch(self.h, out.ctypes.data), "get_hll_switch")
+        return out
+
+    def get_hcorr_eta(self, axis):
+        """pion_gpu_get_hcorr_eta: the H-correction eta along `axis` per cell as the last stage's prepass left it
+        (float64, ncell_all; the value of interface (c | c+1) at c)"""
+        out = np.zeros(self.ncell)
+        self._chk(self.lib.pion_gpu_get_hcorr_eta(self.h, int(axis), _p(out)), "get_hcorr_eta")
         return out
 
     def get_hll_screen_counts(self):

@@ -224,9 +224,18 @@ class CpuSim:
         return out.reshape(self.shape[1:])
 
     def aux(self, which):
+        return self.get_aux(which).reshape(self.shape[1:])
+
+    def get_aux(self, which):
+        """orc_get_aux: what the last stage's prepass kept, per cell (ncell_all, ghosts included).  which 0..2: the
+        H-correction eta along x / y / z (interface (c | c+1) at c), 3: div v, 4: sum over axes of |dp| / min p"""
+        if self.kind != "orc":
+            raise NotImplementedError("get_aux: the oracle only")
+        if which not in (0, 1, 2, 3, 4):
+            raise ValueError("get_aux: which = 0..4")
         out = np.empty(self.ncell)
-        self._f("get_aux")(self.h, C.c_int(which), _p(out))
-        return out.reshape(self.shape[1:])
+        self._chk(self._f("get_aux")(self.h, C.c_int(which), _p(out)), "get_aux")
+        return out
 
     def set_wind_cells(self, idx, states):
         idx = np.ascontiguousarray(idx, dtype=np.int64)
