@@ -201,6 +201,34 @@ int pion_gpu_pack_fits(void *handle, int plane_lo, int plane_hi, void *dbuf);
 long pion_gpu_fits_prim_count(void *handle, int planes);
 int pion_gpu_unpack_fits(void *handle, int plane_lo, int plane_hi, const void *dbuf);
 int pion_gpu_unpack_fits_status(void *handle, long *nbad);
+/* Projected images (pion_amd/csrc/dev_project.h states the rules): up to PION_PROJ_MAX_FIELDS fields
+ * coef rho^a T^b w per call, a in {0, 1, 2} by multiplication, w = 1 (var < 0) or primitive variable `var`,
+ * T = p Mu_tot_over_kB / rho (the Temp image's rule), T^b = exp(b log T), skipped for b == 0.
+ *   3-D Cartesian, axis 0, 1, 2 (line of sight along x, y, z): the image value is (sum of the field over the on-grid
+ *     cells of the column) dx, the additions in the fixed order dev_project.h states (y, z: increasing index; x: 64
+ *     partial sums of every 64th cell, then a pairwise tree), whatever the launch geometry.  The image axes are the
+ *     two remaining axes in grid order: element [j][i] has i on the lower-numbered one.
+ *   2-D cylindrical (z,R), axis PION_PROJ_AXIS_PERP (line of sight perpendicular to the symmetry axis): the reference's
+ *     calc_projection_column (analysis/projection/perp_projection.cpp:404-487) as written, with the slopes of :338-390,
+ *     one ray per cell (z_i, impact parameter b_j = R_j): the image is [NR][NZ], z fastest (:236).
+ * pion_gpu_project writes [nfields][NJ][NI] native-endian doubles, pion_gpu_project_count(handle, axis, nfields) of
+ * them, into the DEVICE buffer dbuf from array `which` (0 = P, 1 = Ph); enqueued on the compute stream, returns at once.
+ * Only on-grid cells are read.  Both floating-point builds give the same bits.  `name` (NUL-terminated, 1 to 15
+ * printable characters, no quote) becomes the image's EXTNAME in pion_host_sim_write_projection's file.
+ * pion_gpu_project_count returns < 0, and both EINVAL with a text, for: 1-D, spherical and 2-D Cartesian grids; a line
+ * of sight along the axis of a cylindrical grid (or any axis but PION_PROJ_AXIS_PERP there); PION_PROJ_AXIS_PERP on a
+ * Cartesian grid; NR == 1; nfields outside 1 .. 8; a outside {0, 1, 2}; var >= nvar; a name that is empty, not
+ * terminated or not printable; coef or b not finite; b != 0 on a handle with cooling == 0 (it has no temperature). */
+#define PION_PROJ_MAX_FIELDS 8
+#define PION_PROJ_AXIS_PERP 3
+typedef struct pion_gpu_proj_field {
+  char name[16];
+  int a;          /* power of rho: 0, 1, 2 */
+  int var;        /* < 0: w = 1; else w = primitive variable var */
+  double coef, b; /* b: power of T */
+} pion_gpu_proj_field;
+long pion_gpu_project_count(void *handle, int axis, int nfields);
+int pion_gpu_project(void *handle, int which, int axis, int nfields, const pion_gpu_proj_field *fields, void *dbuf);
 /* adopt caller-owned device buffers (e.g. torch tensors) instead of internal ones;
  * both must hold nvar*ncell_all doubles */
 int pion_gpu_bind_device_state(void *handle, void *dP, void *dPh);

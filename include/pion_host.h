@@ -91,6 +91,25 @@ int pion_host_sim_write_fits(void *sim, const char *path);
 #define PION_HOST_FILE_PIONRAW 0
 #define PION_HOST_FILE_FITS 1
 int pion_host_sim_set_output_filetype(void *sim, int type);
+/* Projected images of the state (pion_gpu_project; the rules: pion_amd/csrc/dev_project.h): column sums of a 3-D
+ * Cartesian grid along axis 0, 1 or 2, or, for a cylindrical (z,R) grid and axis PION_PROJ_AXIS_PERP, the reference's
+ * perpendicular Abel integral (analysis/projection/perp_projection.cpp: calc_projection_column, :404-487, slopes
+ * :338-390, pixels :225-252).  Up to 8 fields coef rho^a T^b w per file.
+ * pion_host_sim_write_projection: a FITS file with the primary header of pion_host_sim_write_fits plus pion_proj_axis
+ *   and, per field n = 0 .., pion_proj_<n>_a, _var, _coef, _b; then one double-precision IMAGE extension per field,
+ *   NAXIS1 = NI, NAXIS2 = NJ, EXTNAME = the field's name, big-endian, in units of (code units of the field) * dx (the
+ *   Abel images: * length).  Written under a ".part" name and renamed; pion_amd/fits.py reads it.  The images are made
+ *   on the device and only they cross to the host; a backend table without the projection entries downloads the state
+ *   and runs the same functions in a host loop.
+ * pion_host_sim_set_projection_output: from now on every regular output of pion_host_sim_time_int (step 0, each output
+ *   step or time, the final state) is accompanied by <base>_proj_<rank, 4 digits>.<step, 8 digits>.fits; nfields = 0
+ *   turns that off.  Cadence, the time-step clip, checkpoints and every dt are untouched.
+ * EINVAL and a text, never an exit: everything pion_gpu_project refuses (1-D, spherical and 2-D Cartesian grids, a
+ * line of sight along the axis of a cylindrical grid, NR == 1, a bad field, b != 0 without cooling); a sim with a slab
+ * extent set or a communicator of more than one rank (the images of several ranks are not assembled); a path that
+ * cannot be created. */
+int pion_host_sim_write_projection(void *sim, const char *path, int axis, int nfields, const pion_gpu_proj_field *fields);
+int pion_host_sim_set_projection_output(void *sim, int axis, int nfields, const pion_gpu_proj_field *fields);
 typedef struct pion_host_snapshot_info {
   double t_start, t_finish, t_sim, min_timestep, last_dt;   /* SimPM.starttime, finishtime, simtime, min_timestep, last_dt */
   double opfreq_time, next_optime;

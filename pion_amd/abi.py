@@ -36,6 +36,26 @@ STAGE_WHOLE, STAGE_INTERIOR, STAGE_ZBOUNDARY = 0, 1, 2
 STAGE_SLABBOUNDARY = STAGE_ZBOUNDARY   # the boundary part of the slab axis: z planes (3-D), y rows (2-D)
 
 E_OK, E_INVAL, E_DEVICE, E_PHYSICS, E_NOMEM = 0, -1, -2, -3, -4
+# projected images (pion_gpu_project): fields per call, and the axis of a cylindrical grid's perpendicular line of sight
+PROJ_MAX_FIELDS, PROJ_AXIS_PERP = 8, 3
+
+
+class ProjField(C.Structure):
+    """pion_gpu_proj_field (include/pion_gpu.h): coef rho^a T^b w, w = 1 (var < 0) or primitive variable var"""
+    _fields_ = [("name", C.c_char * 16), ("a", C.c_int), ("var", C.c_int), ("coef", C.c_double), ("b", C.c_double)]
+
+
+def proj_fields(fields):
+    """a ctypes array of ProjField from dicts / tuples (name, a[, var[, coef[, b]]]); defaults var -1, coef 1, b 0.
+    A name longer than 15 bytes is handed over unterminated, so that the library refuses it."""
+    arr = (ProjField * max(len(fields), 1))()
+    for i, f in enumerate(fields):
+        if isinstance(f, dict):
+            f = (f["name"], f.get("a", 0), f.get("var", -1), f.get("coef", 1.0), f.get("b", 0.0))
+        name, a, var, coef, b = (tuple(f) + (-1, 1.0, 0.0)[len(f) - 2:])[:5]
+        arr[i].name = name.encode()[:16]
+        arr[i].a, arr[i].var, arr[i].coef, arr[i].b = int(a), int(var), float(coef), float(b)
+    return arr
 
 
 class PionGpuConfig(C.Structure):

@@ -1,0 +1,205 @@
+// pion_project.hip -- the device part of the projected images: pion_gpu_project sums the fields of dev_project.h
+// along one axis of a 3-D Cartesian grid, or applies the reference's perpendicular Abel integral
+// (analysis/projection/perp_projection.cpp:404-487) to every z column of a cylindrical (z,R) grid, into a device
+// buffer [nfields][NJ][NI] of native doubles.  The rules -- the field, the cells of a pixel, the order of the
+// additions, the Abel segment -- are dev_project.h's; this file holds the three kernels that run them and the C-ABI
+// entry points.  Nothing here is part of a step: no stage kernel, StageArgs or handle state is touched.  The whole
+// file is compiled without FMA contraction (Makefile), like every function of dev_project.h.
+//
+//   k_project_yz    line of sight along y or z.  A lane per pixel, 64 consecutive x per wavefront (loads are whole
+//                   lines), the column walked in increasing index by that one lane.  No LDS, no atomics.
+//   k_project_x     line of sight along x.  A wavefront per pixel: lane l sums the cells l, l + 64, .. of the row
+//                   (coalesced), then the rule's tree over the 64 partial sums by __shfl_down.  No LDS, no atomics.
+//   k_project_abel  cylindrical.  A workgroup of 4 wavefronts owns ABEL_J impact rows x 256 z cells; a wavefront's
+//                   lanes are 64 consecutive z.  The geometric weights of a segment (AbelW: Rmin, xdx, x2dx -- two
+//                   sqrt and a log) depend on (j, ir) only, so per block of ABEL_IR rows each thread evaluates ONE
+//                   (j, ir) pair into LDS and every lane reads them back as broadcasts; each v[ir][z], s[ir][z] a
+//                   lane loads and evaluates is used for all ABEL_J impact rows, accumulators in registers.  Per
+//                   pixel the additions are the rule's -- abel_add in increasing ir from abel_start(j) --, so the
+//                   image does not depend on the tiling.  LDS: ABEL_J * ABEL_IR weights (6 KiB) and the rows' start
+//                   indices; no table that grows with NR.
+// blockIdx.y: the field.  Unit, cell and buffer indices are long; the launch grid is checked against 2^31 - 1.
+#include <hip/hip_runtime.h>
+
+#include "dev_project.h"
+#include "pion_handle.h"
+
+using namespace pion;
+using namespace pion::impl;
+
+namespace {
+
+constexpr int PRJ_WAVES = 4;
+constexpr int ABEL_J = 16, ABEL_IR = 16;   // ABEL_J * ABEL_IR = the workgroup's 256 threads: one weight each per block
+static_assert(ABEL_J * ABEL_IR == 64 * PRJ_WAVES, "one (j, ir) pair per thread");
+
+__global__ void __launch_bounds__(64 * PRJ_WAVES)
+k_project_yz(const double *__restrict__ A, double *__restrict__ out, const GridDesc g, const OutputCfg o,
+             const ProjFields F, const ProjGeom q)
+{
+  const int nseg = (q.ni + 63) / 64;
+  const long u = (long)blockIdx.x * PRJ_WAVES + (threadIdx.x >> 6);   // unit: (image row j, 64 pixels of it)
+  if (u >= (long)q.nj * nseg) return;
+  const long j = u / nseg;
+  const int i = (int)(u - j * nseg) * 64 + (int)(threadIdx.x & 63);
+  if (i >= q.ni) return;
+  const pion_gpu_proj_field &f = F.f[blockIdx.y];
+  const long first = q.c0 + i * q.si + j * q.sj;
+  double s = 0.0;
+  for (int k = 0; k < q.nsum; k++) s = proj_add(s, proj_value(g, o, f, A, first + k * q.ss));
+  out[((long)blockIdx.y * q.nj + j) * q.ni + i] = proj_times_dx(g, s);
+}
+
+__global__ void __launch_bounds__(64 * PRJ_WAVES)
+k_project_x(const double *__restrict__ A, double *__restrict__ out, const GridDesc g, const OutputCfg o,
+            const ProjFields F, const ProjGeom q)
+{
+  const long u = (long)blockIdx.x * PRJ_WAVES + (threadIdx.x >> 6);   // pixel: j * ni + i
+  if (u >= (long)q.nj * q.ni) return;
+  const long j = u / q.ni;
+  const long i = u - j * q.ni;
+  const int lane = (int)(threadIdx.x & 63);
+  const pion_gpu_proj_field &f = F.f[blockIdx.y];
+  const long first = q.c0 + i * q.si + j * q.sj;
+  double p = 0.0;
+  for (int ix = lane; ix < q.nsum; ix += PROJ_LANES) p = proj_add(p, proj_value(g, o, f, A, first + ix));
+  // p_l = p_l + p_(l+h) for l < h; what the lanes l >= h compute is never read
+  for (int h = PROJ_LANES / 2; h >= 1; h /= 2) p = proj_add(p, __shfl_down(p, h, 64));
+  if (lane == 0) out[(long)blockIdx.y * q.nj * q.ni + u] = proj_times_dx(g, p);
+}
+
+__global__ void __launch_bounds__(64 * PRJ_WAVES)
+k_project_abel(const double *__restrict__ A, double *__restrict__ out, const GridDesc g, const OutputCfg o,
+               const ProjFields F, const ProjGeom q)
+{
+  __shared__ AbelW W[ABEL_IR][ABEL_J];
+  __shared__ int start[ABEL_J];   // abel_start of the tile's rows; nr for a row past the grid
+  __shared__ int nact[ABEL_IR];   // rows of the tile whose sum has begun at row ir of the block (they are the first ones)
+
+  const int nr = q.nsum, nz = q.ni, t = (int)threadIdx.x;
+  const int nzt = (nz + 64 * PRJ_WAVES - 1) / (64 * PRJ_WAVES);
+  // z tiles fastest; the j tiles in increasing j, so that the longest sums are dispatched first
+  const long jt = (long)blockIdx.x / nzt;
+  const int j0 = (int)jt * ABEL_J;
+  const int z = (int)((long)blockIdx.x - jt * nzt) * 64 * PRJ_WAVES + t;
+  const bool zok = z < nz;
+  const pion_gpu_proj_field &f = F.f[blockIdx.y];
+  const long first = q.c0 + (zok ? z : 0);   // (a lane past the row reads nothing)
+
+  if (t < ABEL_J) start[t] = (j0 + t < nr) ? abel_start(g, nr, j0 + t) : nr;
+  __syncthreads();
+  const int ir_lo = start[0];
+
+  double acc[ABEL_J];
+#pragma unroll
+  for (int jj = 0; jj < ABEL_J; jj++) acc[jj] = 0.0;
+
+  // v and s of the row the walk is at.  s[ir] needs v[ir + 1]; the last row takes the slope of the one before it
+  double vcur = 0.0, s = 0.0;
+  if (zok) {
+    vcur = proj_value(g, o, f, A, first + ir_lo * q.ss);
+    if (ir_lo == nr - 1) s = abel_slope(g, nr - 2, proj_value(g, o, f, A, first + (nr - 2) * q.ss), vcur);
+  }
+
+  for (int irb = ir_lo; irb < nr; irb += ABEL_IR) {
+    __syncthreads();   // the previous block's weights have been read
+    {
+      const int jj = t % ABEL_J, k = t / ABEL_J, ir = irb + k;
+      AbelW w;
+      w.Rmin = w.xdx = w.x2dx = 0.0;
+      if (ir < nr && ir >= start[jj]) w = abel_weights(g, nr, j0 + jj, ir);
+      W[k][jj] = w;
+      if (jj == 0) {
+        int n = 0;
+        for (int m = 0; m < ABEL_J; m++) n += (ir >= start[m]) ? 1 : 0;   // (start[] does not decrease along the tile)
+        nact[k] = n;
+      }
+    }
+    __syncthreads();
+    const int kmax = min(ABEL_IR, nr - irb);
+    for (int k = 0; k < kmax; k++) {
+      const int ir = irb + k;
+      double vnext = 0.0;
+      if (ir + 1 < nr) {
+        if (zok) vnext = proj_value(g, o, f, A, first + (long)(ir + 1) * q.ss);
+        s = abel_slope(g, ir, vcur, vnext);
+      }
+      const int n = __builtin_amdgcn_readfirstlane(nact[k]);
+#pragma unroll
+      for (int jj = 0; jj < ABEL_J; jj++)
+        if (jj < n) acc[jj] = abel_add(acc[jj], vcur, s, W[k][jj]);
+      vcur = vnext;
+    }
+  }
+  if (!zok) return;
+#pragma unroll
+  for (int jj = 0; jj < ABEL_J; jj++)
+    if (j0 + jj < nr) {
+      const bool none = abel_b(g, j0 + jj) > abel_grid_max(g, nr);   // perp_projection.cpp:417-420
+      out[((long)blockIdx.y * q.nj + (j0 + jj)) * q.ni + z] = none ? 0.0 : abel_finish(acc[jj]);
+    }
+}
+
+OutputCfg project_cfg(const Handle *h)
+{
+  OutputCfg o = out_cfg(h->cfg);
+  o.Mu_tot_over_kB = h->Mu_tot_over_kB;
+  return o;
+}
+
+}  // namespace
+
+extern "C" {
+
+long pion_gpu_project_count(void *handle, int axis, int nfields)
+{
+  Handle *h = (Handle *)handle;
+  if (!h) return PION_GPU_EINVAL;
+  if (const char *why = proj_refused_grid(h->g, axis)) {
+    h->err = why;
+    return PION_GPU_EINVAL;
+  }
+  if (nfields < 1 || nfields > PION_PROJ_MAX_FIELDS) {
+    h->err = "project: between 1 and 8 fields per call";
+    return PION_GPU_EINVAL;
+  }
+  return proj_count(proj_geom(h->g, axis), nfields);
+}
+
+int pion_gpu_project(void *handle, int which, int axis, int nfields, const pion_gpu_proj_field *fields, void *dbuf)
+{
+  Handle *h = use(handle);
+  if (!h) return PION_GPU_EINVAL;
+  const OutputCfg o = project_cfg(h);
+  const char *why = proj_refused_grid(h->g, axis);
+  if (!why) why = proj_refused_fields(o, nfields, fields);
+  if (!why && (which < 0 || which > 1)) why = "project: which is 0 (P) or 1 (Ph)";
+  if (!why && !dbuf) why = "project: no buffer";
+  if (why) {
+    h->err = why;
+    return PION_GPU_EINVAL;
+  }
+  const ProjGeom q = proj_geom(h->g, axis);
+  ProjFields F;
+  F.n = nfields;
+  for (int i = 0; i < PION_PROJ_MAX_FIELDS; i++) F.f[i] = fields[i < nfields ? i : 0];
+  const double *A = which ? h->dPh : h->dP;
+  long nblk;
+  if (h->g.cyl == 1) nblk = (long)((q.ni + 64 * PRJ_WAVES - 1) / (64 * PRJ_WAVES)) * ((q.nj + ABEL_J - 1) / ABEL_J);
+  else if (axis == 0) nblk = ((long)q.nj * q.ni + PRJ_WAVES - 1) / PRJ_WAVES;
+  else nblk = ((long)q.nj * ((q.ni + 63) / 64) + PRJ_WAVES - 1) / PRJ_WAVES;
+  if (nblk > (1L << 31) - 1) {
+    h->err = "project: the image is too large for one launch";
+    return PION_GPU_EINVAL;
+  }
+  const dim3 grid((unsigned)nblk, (unsigned)nfields), block(64 * PRJ_WAVES);
+  if (h->g.cyl == 1)
+    hipLaunchKernelGGL(k_project_abel, grid, block, 0, h->stream, A, (double *)dbuf, h->g, o, F, q);
+  else if (axis == 0)
+    hipLaunchKernelGGL(k_project_x, grid, block, 0, h->stream, A, (double *)dbuf, h->g, o, F, q);
+  else
+    hipLaunchKernelGGL(k_project_yz, grid, block, 0, h->stream, A, (double *)dbuf, h->g, o, F, q);
+  HCHECK(h, hipGetLastError());
+  return 0;
+}
+}

@@ -16,7 +16,9 @@
 #define __device__
 #endif
 #include "../csrc/dev_output.h"
+#include "../csrc/dev_project.h"
 #include "sim_control_gpu.h"
+#include "slab_comm.h"
 #include "snapshot_io.h"
 
 namespace pion_host {
@@ -476,6 +478,127 @@ int sim_control_gpu::write_fits(const char *path)
   // 4.
   if (!rc && rename(tmp.c_str(), path) != 0) {
     io_error_ = std::string("write_fits: cannot rename to ") + path + ": " + strerror(errno);
+    rc = PION_GPU_EINVAL;
+  }
+  if (rc) unlink(tmp.c_str());
+  return rc;
+}
+
+// ---- projected images (the rules: dev_project.h) -----------------------------------------------------------------
+int sim_control_gpu::projection_refused(int axis, int nfields, const pion_gpu_proj_field *fields, const char *who)
+{
+  const char *why = nullptr;
+  if (slab.set || (comm_ && comm_->world() > 1))
+    why = "project: this sim is one rank of a slab run, and the images of more than one rank are not assembled";
+  if (!why) why = pion::proj_refused_grid(grid_desc(cfg), axis);
+  if (!why) why = pion::proj_refused_fields(pion::out_cfg(cfg), nfields, fields);
+  if (!why) return 0;
+  io_error_ = std::string(who) + ": " + why;
+  return PION_GPU_EINVAL;
+}
+
+int sim_control_gpu::set_projection_output(int axis, int nfields, const pion_gpu_proj_field *fields)
+{
+  io_error_.clear();
+  if (nfields == 0) {
+    proj_fields_.clear();
+    return 0;
+  }
+  if (int rc = projection_refused(axis, nfields, fields, "set_projection_output")) return rc;
+  proj_axis_ = axis;
+  proj_fields_.assign(fields, fields + nfields);
+  return 0;
+}
+
+int sim_control_gpu::write_projection(const char *path, int axis, int nfields, const pion_gpu_proj_field *fields)
+{
+  io_error_.clear();
+  if (!path || !*path) {
+    io_error_ = "write_projection: no path";
+    return PION_GPU_EINVAL;
+  }
+  if (int rc = projection_refused(axis, nfields, fields, "write_projection")) return rc;
+  std::vector<snapshot_param> params;
+  long nloc = 0;
+  if (int rc = snapshot_params(params, nloc)) return rc;
+  if (int rc = finish_halo()) {
+    io_error_ = "write_projection: finish_halo failed";
+    return rc;
+  }
+  auto real = [](double x) {
+    char b[64];
+    snprintf(b, sizeof b, "%.17g", x);
+    return std::string(b);
+  };
+  params.push_back({"pion_proj_axis", std::to_string(axis), 'i'});
+  for (int i = 0; i < nfields; i++) {
+    const std::string k = "pion_proj_" + std::to_string(i) + "_";
+    params.push_back({k + "a", std::to_string(fields[i].a), 'i'});
+    params.push_back({k + "var", std::to_string(fields[i].var), 'i'});
+    params.push_back({k + "coef", real(fields[i].coef), 'd'});
+    params.push_back({k + "b", real(fields[i].b), 'd'});
+  }
+  const pion::GridDesc g = grid_desc(cfg);
+  const pion::OutputCfg o = pion::out_cfg(cfg);
+  const pion::ProjGeom q = pion::proj_geom(g, axis);
+  const long npix = (long)q.nj * q.ni, n = pion::proj_count(q, nfields);
+
+  // 1. the images, native doubles [nfields][NJ][NI]
+  std::vector<double> img((size_t)n);
+  if (be_->project_count && be_->project_to_host) {
+    if (be_->project_count(h_, axis, nfields) != n) {
+      io_error_ = "write_projection: the backend refuses: " + last_error();
+      return PION_GPU_EINVAL;
+    }
+    if (int rc = be_->project_to_host(h_, axis, nfields, fields, img.data())) {
+      io_error_ = "write_projection: project_to_host failed: " + last_error();
+      return rc;
+    }
+  }
+  else {
+    // no projection entries: array 0 whole, every pixel by dev_project.h's functions here
+    std::vector<double> A((size_t)cfg.nvar * g.ncell);
+    if (int rc = be_->download(h_, 0, A.data())) {
+      io_error_ = "write_projection: download failed: " + last_error();
+      return rc;
+    }
+    for (int f = 0; f < nfields; f++)
+      for (long j = 0; j < q.nj; j++)
+        for (long i = 0; i < q.ni; i++) {
+          const long first = q.c0 + i * q.si + j * q.sj;
+          img[(size_t)(f * npix + j * q.ni + i)] = (g.cyl == 1) ? pion::abel_column(g, o, fields[f], q, A.data(), first, (int)j)
+                                                               : pion::proj_column(g, o, fields[f], q, axis, A.data(), first);
+        }
+  }
+  // 2. the file: big-endian, every extension's header of the same length
+  std::vector<unsigned long long> R((size_t)n);
+  for (long k = 0; k < n; k++) R[(size_t)k] = pion::out_be64(img[(size_t)k]);
+  const std::string primary = fits_primary_header(params);
+  const long naxis[2] = {q.ni, q.nj};
+  std::vector<std::string> ext((size_t)nfields);
+  for (int i = 0; i < nfields; i++) ext[(size_t)i] = fits_image_header(fields[i].name, 2, naxis);
+  const long run_bytes = npix * (long)sizeof(double);
+  const long stride = (long)ext[0].size() + padded(run_bytes);
+  const long total = (long)primary.size() + nfields * stride;
+
+  const std::string tmp = std::string(path) + ".part";
+  int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  if (fd < 0) {
+    io_error_ = "write_projection: cannot create " + tmp + ": " + strerror(errno);
+    return PION_GPU_EINVAL;
+  }
+  int rc = (ftruncate(fd, (off_t)total) != 0) ? PION_GPU_EINVAL : 0;   // (the padding reads as zero bytes)
+  if (!rc && full_pwrite(fd, primary.data(), primary.size(), 0)) rc = PION_GPU_EINVAL;
+  for (int i = 0; i < nfields && !rc; i++) {
+    const long at = (long)primary.size() + i * stride;
+    if (full_pwrite(fd, ext[(size_t)i].data(), ext[(size_t)i].size(), (off_t)at)) rc = PION_GPU_EINVAL;
+    if (!rc && full_pwrite(fd, R.data() + (size_t)i * npix, (size_t)run_bytes, (off_t)(at + (long)ext[(size_t)i].size())))
+      rc = PION_GPU_EINVAL;
+  }
+  if (rc) io_error_ = "write_projection: writing " + tmp + " failed: " + strerror(errno);
+  close(fd);
+  if (!rc && rename(tmp.c_str(), path) != 0) {
+    io_error_ = std::string("write_projection: cannot rename to ") + path + ": " + strerror(errno);
     rc = PION_GPU_EINVAL;
   }
   if (rc) unlink(tmp.c_str());

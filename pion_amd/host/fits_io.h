@@ -37,6 +37,12 @@
 // them, multiplies B by 1/sqrt(4 pi) and counts the elements that are not finite or hold the reference's null value
 // -1e99, which fail the restart.  A backend without that entry takes the same dev_output.h functions in a host loop
 // (fits_convert_run) and goes through upload.
+//
+// Projected images (sim_control_gpu::write_projection, defined in fits_io.cpp; the rules: pion_amd/csrc/dev_project.h)
+// use the same writer: the same primary header with pion_proj_axis and pion_proj_<n>_{a,var,coef,b} appended, then one
+// two-dimensional IMAGE extension per field (NAXIS1 = NI, NAXIS2 = NJ, EXTNAME = the field's name).  The images come
+// from the backend's project_* entries; a table without them downloads array 0 and runs dev_project.h's functions in a
+// host loop.  An image is small, so it is written whole, under a ".part" name and renamed.
 #ifndef PION_FITS_IO_H
 #define PION_FITS_IO_H
 

@@ -80,6 +80,14 @@ typedef struct pion_backend {
   int (*fits_from_host)(void *handle, int plane_lo, int plane_hi, int slot, int (*fill)(void *ctx, double *host),
                         void *ctx);
   int (*fits_read_status)(void *handle, long *nbad);
+  /* Projected images (fits_io.h; the rules: pion_amd/csrc/dev_project.h): the images of pion_gpu_project, native
+   * doubles [nfields][NJ][NI].  These two entries are read ONLY inside sim_control_gpu::write_projection: a caller
+   * that never writes a projection may hand the loop a table that ends before them.  Both NULL: the writer takes
+   * array 0 through download and runs dev_project.h's functions in a host loop.
+   *   project_count:   doubles of one call, < 0 for a configuration pion_gpu_project refuses (text in last_error)
+   *   project_to_host: project array P on the device and copy the images into `host`; complete on return */
+  long (*project_count)(void *handle, int axis, int nfields);
+  int (*project_to_host)(void *handle, int axis, int nfields, const pion_gpu_proj_field *fields, double *host);
 } pion_backend;
 
 /* the product's backend: libpion_gpu.so */

@@ -187,6 +187,20 @@ int gpu_fits_from_host(void *h, int plane_lo, int plane_hi, int slot, int (*fill
 {
   return gpu_from_host(h, true, plane_lo, plane_hi, slot, fill, ctx);
 }
+// the images of one call: projected into slot 0's device buffer, copied into the caller's memory, waited for
+int gpu_project_to_host(void *h, int axis, int nfields, const pion_gpu_proj_field *fields, double *host)
+{
+  const long n = pion_gpu_project_count(h, axis, nfields);
+  if (n < 0) return (int)n;
+  if (!host) return PION_GPU_EINVAL;
+  Staging *st;
+  if (int rc = staging_slot(h, 0, n, &st)) return rc;
+  if (int rc = pion_gpu_project(h, 0, axis, nfields, fields, st->dev[0])) return rc;
+  hipStream_t s = compute_stream_of(h);
+  if (hipMemcpyAsync(host, st->dev[0], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
+    return PION_GPU_EDEVICE;
+  return hipStreamSynchronize(s) == hipSuccess ? 0 : PION_GPU_EDEVICE;
+}
 void gpu_destroy(void *h)
 {
   Staging st;
@@ -233,6 +247,8 @@ const pion_backend k_gpu = {
     gpu_fits_to_host_begin,
     gpu_fits_from_host,
     pion_gpu_unpack_fits_status,
+    pion_gpu_project_count,
+    gpu_project_to_host,
 };
 
 }  // namespace

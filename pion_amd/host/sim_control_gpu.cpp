@@ -216,6 +216,13 @@ std::string sim_control_gpu::output_name(long step) const
   return T.outfile + b;
 }
 
+std::string sim_control_gpu::projection_name(long step) const
+{
+  char b[64];
+  snprintf(b, sizeof b, "_proj_%04d.%08ld.fits", comm_ ? comm_->rank() : 0, step);
+  return T.outfile + b;
+}
+
 int sim_control_gpu::write_output(const char *path)
 {
   return (filetype_ == PION_HOST_FILE_FITS) ? write_fits(path) : write_snapshot(path);
@@ -250,6 +257,9 @@ int sim_control_gpu::output_data()
   // (the reference writes a final state that is also a regular output twice, from Time_Int and from Finalise; once here)
   if (last_output_step_ == T.timestep) return 0;
   if (int rc = write_output(output_name(T.timestep).c_str())) return rc;
+  if (!proj_fields_.empty())
+    if (int rc = write_projection(projection_name(T.timestep).c_str(), proj_axis_, (int)proj_fields_.size(), proj_fields_.data()))
+      return rc;
   last_output_step_ = T.timestep;
   return 0;
 }
@@ -396,6 +406,30 @@ int pion_host_sim_write_fits(void *s, const char *path)
   auto *c = static_cast<pion_host::sim_control_gpu *>(s);
   try {
     return io_result(c, c->write_fits(path));
+  }
+  catch (const std::exception &e) {
+    g_last_exception = e.what();
+    return PION_GPU_EINVAL;
+  }
+}
+int pion_host_sim_write_projection(void *s, const char *path, int axis, int nfields, const pion_gpu_proj_field *fields)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  try {
+    return io_result(c, c->write_projection(path, axis, nfields, fields));
+  }
+  catch (const std::exception &e) {
+    g_last_exception = e.what();
+    return PION_GPU_EINVAL;
+  }
+}
+int pion_host_sim_set_projection_output(void *s, int axis, int nfields, const pion_gpu_proj_field *fields)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  try {
+    return io_result(c, c->set_projection_output(axis, nfields, fields));
   }
   catch (const std::exception &e) {
     g_last_exception = e.what();

@@ -93,6 +93,17 @@ class sim_control_gpu {
   int write_fits(const char *path);
   // the PIONRAW2 file (snapshot_io.h) of this sim's on-grid cells; completes a halo exchange in flight first
   int write_snapshot(const char *path);
+  // Projected images (fits_io.h; the rules: pion_amd/csrc/dev_project.h, after the reference's
+  // analysis/projection/perp_projection.cpp:404-487): a FITS file with write_fits' primary header plus pion_proj_axis
+  // and per field pion_proj_<n>_{a,var,coef,b}, and one double-precision IMAGE extension [NJ][NI] per field, EXTNAME =
+  // the field's name, in units of code * dx.  Projected on the device (backend entries project_*), or -- a table
+  // without them -- from a download by the same functions in a host loop.  EINVAL and a text: what pion_gpu_project
+  // refuses; a sim with a slab extent set (images of more than one rank are not assembled); a path that cannot be created
+  int write_projection(const char *path, int axis, int nfields, const pion_gpu_proj_field *fields);
+  // from now on every regular output of output_data() is accompanied by <base>_proj_<rank, 4 digits>.<step, 8
+  // digits>.fits; nfields 0 turns it off again.  The same refusals, made here.  Cadence and time steps are untouched
+  int set_projection_output(int axis, int nfields, const pion_gpu_proj_field *fields);
+  std::string projection_name(long step) const;
   // restart from the files that hold this sim's planes (written by any number of ranks); sets P, Ph, simtime,
   // timestep, last_dt, next_optime, starttime, finishtime and min_timestep, then assigns and updates the boundaries as
   // Init does.  Wind sources, jets and cooling tables are set up by the caller first, as before Init.
@@ -135,6 +146,9 @@ class sim_control_gpu {
   long last_output_step_ = -1;   // step whose regular output has been written
   std::string io_error_;
   int filetype_ = 0;             // PION_HOST_FILE_*
+  int proj_axis_ = 0;            // set_projection_output: the images that accompany a regular output (none: empty)
+  std::vector<pion_gpu_proj_field> proj_fields_;
+  int projection_refused(int axis, int nfields, const pion_gpu_proj_field *fields, const char *who);
   // snapshot_io.cpp: what both writers share
   int snapshot_params(std::vector<snapshot_param> &out, long &slab_n);
   int stream_runs(int fd, bool fits, int nrun, long nloc, long plane, long off, long stride, const char *who);

@@ -104,6 +104,9 @@ def load_host_library():
     if hasattr(h, "pion_host_sim_read_fits"):   # (likewise)
         h.pion_host_sim_read_fits.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int]
         h.pion_host_fits_read_header.argtypes = [C.c_char_p, C.POINTER(abi.PionGpuConfig), C.POINTER(SnapshotInfo)]
+    if hasattr(h, "pion_host_sim_write_projection"):   # (likewise)
+        h.pion_host_sim_write_projection.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
+        h.pion_host_sim_set_projection_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     h.pion_host_comm_unique_id.argtypes = [C.c_void_p]
     h.pion_host_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     h.pion_host_comm_destroy.argtypes = [C.c_void_p]
@@ -247,6 +250,22 @@ class HostSim:
         rc = self.lib.pion_host_sim_write_fits(self.s, os.fsencode(path))
         if rc != 0:
             raise RuntimeError("pion_host_sim_write_fits rc=%d: %s" % (rc, self.last_error()))
+
+    def write_projection(self, path, axis, fields):
+        """the FITS file of the projected images of P along `axis` (pion_host_sim_write_projection): 0, 1, 2 on a 3-D
+        Cartesian grid, abi.PROJ_AXIS_PERP on a cylindrical (z,R) one; fields as abi.proj_fields takes them, (name, a,
+        var, coef, b) for coef rho^a T^b w.  pion_amd.fits.read returns the images by name."""
+        rc = self.lib.pion_host_sim_write_projection(self.s, os.fsencode(path), int(axis), len(fields),
+                                                     abi.proj_fields(fields))
+        if rc != 0:
+            raise RuntimeError("pion_host_sim_write_projection rc=%d: %s" % (rc, self.last_error()))
+
+    def set_projection_output(self, axis, fields):
+        """from now on every regular output of time_int is accompanied by <base>_proj_<rank>.<step>.fits with these
+        images (pion_host_sim_set_projection_output); no fields turns it off"""
+        rc = self.lib.pion_host_sim_set_projection_output(self.s, int(axis), len(fields), abi.proj_fields(fields))
+        if rc != 0:
+            raise ValueError("pion_host_sim_set_projection_output rc=%d: %s" % (rc, self.last_error()))
 
     def set_output_filetype(self, filetype):
         """FILE_PIONRAW (the default) or FILE_FITS for the regular outputs of time_int; checkpoints stay PIONRAW2

@@ -97,6 +97,10 @@ def load_library():
         lib.pion_gpu_fits_prim_count.restype = C.c_long
         lib.pion_gpu_unpack_fits.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         lib.pion_gpu_unpack_fits_status.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+    if hasattr(lib, "pion_gpu_project"):   # (likewise)
+        lib.pion_gpu_project_count.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        lib.pion_gpu_project_count.restype = C.c_long
+        lib.pion_gpu_project.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.pion_gpu_interface_flux.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
     if hasattr(lib, "pion_gpu_cell_advance"):   # (likewise)
         lib.pion_gpu_cell_advance.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp]
@@ -128,7 +132,7 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_ongrid_count", "pion_gpu_pack_ongrid", "pion_gpu_unpack_ongrid",
     "pion_gpu_fits_images", "pion_gpu_fits_count", "pion_gpu_pack_fits",
     "pion_gpu_fits_prim_count", "pion_gpu_unpack_fits", "pion_gpu_unpack_fits_status",
-    "pion_gpu_cell_advance",
+    "pion_gpu_cell_advance", "pion_gpu_project_count", "pion_gpu_project",
 ]
 
 
@@ -418,6 +422,39 @@ class GpuSim:
         n = C.c_long(-1)
         self._chk(self.lib.pion_gpu_unpack_fits_status(self.h, C.byref(n)), "unpack_fits_status")
         return n.value
+
+    def project_count(self, axis, nfields):
+        """pion_gpu_project_count: doubles one project() call writes, [nfields][NJ][NI]; raises for a grid or an axis
+        the projection refuses (no device call)"""
+        n = self.lib.pion_gpu_project_count(self.h, int(axis), int(nfields))
+        if n < 0:
+            raise PionGpuError("project_count", n, self._err())
+        return n
+
+    def project(self, axis, fields, which=0, dbuf_ptr=None):
+        """pion_gpu_project: the projected images of array `which` along `axis` (0, 1, 2 on a 3-D Cartesian grid:
+        column sums times dx; abi.PROJ_AXIS_PERP on a cylindrical (z,R) grid: the perpendicular Abel integral).
+        fields: what abi.proj_fields takes -- (name, a, var, coef, b) for coef rho^a T^b w.  With dbuf_ptr the images
+        go into that device buffer, enqueued on the compute stream; without it they are returned as an ndarray
+        [nfields][NJ][NI] (a torch buffer in between)."""
+        arr = fields if isinstance(fields, C.Array) else abi.proj_fields(fields)
+        nf = len(fields)
+        if dbuf_ptr is not None:
+            self._chk(self.lib.pion_gpu_project(self.h, int(which), int(axis), nf, arr, C.c_void_p(dbuf_ptr)), "project")
+            return None
+        n = self.lib.pion_gpu_project_count(self.h, int(axis), max(1, min(nf, abi.PROJ_MAX_FIELDS)))
+        import torch
+        buf = torch.empty((max(n, 1),), dtype=torch.float64, device="cuda:%d" % torch.cuda.current_device())
+        self._chk(self.lib.pion_gpu_project(self.h, int(which), int(axis), nf, arr, C.c_void_p(buf.data_ptr())), "project")
+        self.synchronize()
+        return buf.cpu().numpy().reshape(nf, -1, self.project_shape(axis)[1])
+
+    def project_shape(self, axis):
+        """(NJ, NI) of an image along `axis`"""
+        ng = list(self.cfg.ng)
+        if self.cfg.coord_sys == 2:
+            return ng[1], ng[0]
+        return (ng[2], ng[1]) if axis == 0 else ((ng[2], ng[0]) if axis == 1 else (ng[1], ng[0]))
 
     def unpack_ongrid(self, plane_lo, plane_hi, dbuf_ptr):
         """pion_gpu_unpack_ongrid: the reverse, into P and Ph; ghost cells and other planes are left alone"""
