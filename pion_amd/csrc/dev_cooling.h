@@ -17,8 +17,9 @@
 //                      cooling_function_SD93CIE::cooling_rate_SD93CIE (cooling_SD93_cie.cpp:666-704): log10 T, a
 //                      natural cubic spline in GSL's cspline representation, exp
 //   EP.cooling = 2     Koyama & Inutsuka (2002), CoolingFn::CoolingRate (cooling.cpp:333-336, 373-399)
-// They travel in a CoolForm (kernels.h) to kernel instances of their own; TimeUpdateMP, the Cash-Karp driver and
-// timescales below are templates on the type that holds the rate's constants and call the matching edot overload.
+// They travel in a CoolForm (kernels.h).  TimeUpdateMP, the Cash-Karp driver and timescales below are templates on the
+// type that holds the rate's constants (CoolOf<FORM>::type) and call the matching edot overload; the cooling kernels are
+// templates on FORM the same way, one instance per form.
 #ifndef PION_DEV_COOLING_H
 #define PION_DEV_COOLING_H
 
@@ -269,22 +270,41 @@ struct Cooling {
 };
 
 
-// a CoolForm as a workgroup uses it: the CIE curve of EP.cooling = 4..7 staged in LDS (3 n doubles), as k_cooling_dE_form
+// The rate's constants as a workgroup of 256 threads uses them, what a thread chases per Edot staged in lds
+// (CoolOf<FORM>::lds doubles): an Edot is an interval search of dependent look-ups plus the reads of that interval, a
+// Cash-Karp step six of those, and a thread is bound by the latency of that chain -- LDS answers several times sooner
+// than the L1 / L2 path.  The tables of EP.cooling = 8 (temperature grid, five rates and their slopes: 11 NT doubles,
+// 17.6 KB at NT = 200), the CIE curve of 4..7 (knots, values and spline coefficients: 3 n doubles); KI02 stages nothing.
 template <int FORM>
-PDEV void stage_form(const CoolForm &f, double *ccrv, CoolFormT<FORM> &cool)
+PDEV void stage_cool(const CoolDev &t, const CoolForm &f, double *lds, typename CoolOf<FORM>::type &cool)
 {
-  static_cast<CoolForm &>(cool) = f;
-  if constexpr (FORM == COOL_FORM_CURVE) {
-    const int n = f.n;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-      ccrv[i] = f.x[i];
-      ccrv[n + i] = f.y[i];
-      ccrv[2 * n + i] = f.c[i];
+  if constexpr (FORM == COOL_FORM_TABLE) {
+    const int NT = t.NT;
+    for (int i = threadIdx.x; i < NT; i += 256) lds[i] = t.T[i];
+    for (int i = threadIdx.x; i < 5 * NT; i += 256) {
+      lds[NT + i] = t.tab[i];
+      lds[6 * NT + i] = t.slope[i];
     }
     __syncthreads();
-    cool.x = ccrv;
-    cool.y = ccrv + n;
-    cool.c = ccrv + 2 * n;
+    cool = t;
+    cool.T = lds;
+    cool.tab = lds + NT;
+    cool.slope = lds + 6 * NT;
+  }
+  else {
+    static_cast<CoolForm &>(cool) = f;
+    if constexpr (FORM == COOL_FORM_CURVE) {
+      const int n = f.n;
+      for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        lds[i] = f.x[i];
+        lds[n + i] = f.y[i];
+        lds[2 * n + i] = f.c[i];
+      }
+      __syncthreads();
+      cool.x = lds;
+      cool.y = lds + n;
+      cool.c = lds + 2 * n;
+    }
   }
 }
 

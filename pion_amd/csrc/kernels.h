@@ -32,11 +32,11 @@ struct CoolDev {
 };
 
 // The cooling functions of mp_only_cooling other than the tabulated one (EP.cooling = 2, 4..7).  CoolDev and StageArgs
-// are by-value arguments of kernels whose code is pinned, so this travels as an argument of its own, to the kernel
-// instances of these forms only (DESIGN.md s6d on OutputCfg).
-enum { COOL_FORM_CURVE = 1, COOL_FORM_KI02 = 2 };
+// are by-value arguments of the stage kernels, whose code is pinned, so this travels as an argument of its own, to every
+// cooling kernel; the instances of the tabulated rate (COOL_FORM_TABLE: EP.cooling = 8, constants in CoolDev) ignore it.
+enum { COOL_FORM_TABLE = 0, COOL_FORM_CURVE = 1, COOL_FORM_KI02 = 2 };
 struct CoolForm {
-  int flag;              // EP.cooling: 2 (KI02) or 4..7 (a uniform run-time switch within COOL_FORM_CURVE)
+  int flag;              // EP.cooling: 2 (KI02), 4..7 (a uniform run-time switch within COOL_FORM_CURVE), else the tables
   int n;                 // knots of the CIE curve (0 for KI02)
   const double *x;       // [n] log10 T, strictly increasing
   const double *y;       // [n] log10 Lambda
@@ -48,6 +48,23 @@ struct CoolForm {
 };
 template <int FORM>
 struct CoolFormT : CoolForm {};
+// the kernel instance an EP.cooling runs on (the launchers' dispatch)
+static inline int cool_form_of(const int flag)
+{
+  return (flag == 2) ? COOL_FORM_KI02 : (flag >= 4 && flag <= 7) ? COOL_FORM_CURVE : COOL_FORM_TABLE;
+}
+// per form: the type that holds the rate's constants (dev_cooling.h: Cooling::edot is overloaded on it) and the doubles
+// a workgroup stages in LDS -- temperature grid, five rates and their slopes; knots, values and coefficients; nothing
+template <int FORM>
+struct CoolOf {
+  typedef CoolFormT<FORM> type;
+  static constexpr int lds = (FORM == COOL_FORM_CURVE) ? 3 * PION_COOL_NT_MAX : 1;
+};
+template <>
+struct CoolOf<COOL_FORM_TABLE> {
+  typedef CoolDev type;
+  static constexpr int lds = 11 * PION_COOL_NT_MAX;
+};
 
 struct StageArgs {
   GridDesc g;
@@ -148,48 +165,33 @@ struct CoolTestArgs {
   CoolDev cool;
 };
 
-// a launcher kernels_fp.hip defines once per equation set (-DPION_EQSEL), and its dispatcher on a.eqntype
-#define PION_PER_EQN(FN, ARGS)                        \
-  int FN##_hd(const ARGS &a, hipStream_t s);          \
-  int FN##_mhd(const ARGS &a, hipStream_t s);         \
-  int FN##_glm(const ARGS &a, hipStream_t s);         \
-  inline int FN(const ARGS &a, hipStream_t s)         \
-  {                                                   \
-    if (a.eqntype == EQEUL) return FN##_hd(a, s);     \
-    if (a.eqntype == EQMHD) return FN##_mhd(a, s);    \
-    if (a.eqntype == EQGLM) return FN##_glm(a, s);    \
-    return -1;                                        \
+// a launcher kernels_fp.hip defines once per equation set (-DPION_EQSEL), and its dispatcher on a.eqntype; after ARGS:
+// the type of one more parameter between the arguments and the stream, if the launcher has one
+#define PION_PER_EQN(FN, ARGS, ...)                                            \
+  int FN##_hd(const ARGS &a, __VA_OPT__(__VA_ARGS__ x, ) hipStream_t s);       \
+  int FN##_mhd(const ARGS &a, __VA_OPT__(__VA_ARGS__ x, ) hipStream_t s);      \
+  int FN##_glm(const ARGS &a, __VA_OPT__(__VA_ARGS__ x, ) hipStream_t s);      \
+  inline int FN(const ARGS &a, __VA_OPT__(__VA_ARGS__ x, ) hipStream_t s)      \
+  {                                                                            \
+    if (a.eqntype == EQEUL) return FN##_hd(a, __VA_OPT__(x, ) s);              \
+    if (a.eqntype == EQMHD) return FN##_mhd(a, __VA_OPT__(x, ) s);             \
+    if (a.eqntype == EQGLM) return FN##_glm(a, __VA_OPT__(x, ) s);             \
+    return -1;                                                                 \
   }
 
-// k_cooling_dE_form: the cooling source of EP.cooling = 2, 4..7
-#define PION_PER_EQN_FORM(FN)                                              \
-  int FN##_hd(const StageArgs &a, const CoolForm &f, hipStream_t s);       \
-  int FN##_mhd(const StageArgs &a, const CoolForm &f, hipStream_t s);      \
-  int FN##_glm(const StageArgs &a, const CoolForm &f, hipStream_t s);      \
-  inline int FN(const StageArgs &a, const CoolForm &f, hipStream_t s)      \
-  {                                                                        \
-    if (a.eqntype == EQEUL) return FN##_hd(a, f, s);                       \
-    if (a.eqntype == EQMHD) return FN##_mhd(a, f, s);                      \
-    if (a.eqntype == EQGLM) return FN##_glm(a, f, s);                      \
-    return -1;                                                             \
-  }
-
+// the cooling launchers pick the instance of f.flag (cool_form_of); launch_cool: what = 0 TimeUpdateMP, 1 Edot,
+// 2 timescales, 3 the CIE curve itself
 #define PION_DECLARE_FP(NS)                                        \
   namespace NS {                                                   \
   PION_PER_EQN(launch_stage, StageArgs)                            \
   PION_PER_EQN(launch_stage_dE, StageArgs)                         \
-  PION_PER_EQN(launch_cooling_dE, StageArgs)                       \
-  PION_PER_EQN_FORM(launch_cooling_dE_form)                        \
-  int launch_dt_mp_form(const DtArgs &a, const CoolForm &f, hipStream_t s);   \
-  int launch_cool_form(const CoolTestArgs &a, const CoolForm &f, int what, hipStream_t s); \
+  PION_PER_EQN(launch_cooling_dE, StageArgs, const CoolForm &)     \
   PION_PER_EQN(launch_flux_test, FluxTestArgs)                     \
   PION_PER_EQN(launch_cell_test, CellTestArgs)                     \
   int launch_prepass(const PrepassArgs &a, hipStream_t s);         \
   int launch_dt(const DtArgs &a, hipStream_t s);                   \
-  int launch_dt_mp(const DtArgs &a, hipStream_t s);                \
-  int launch_cool_update(const CoolTestArgs &a, hipStream_t s);    \
-  int launch_cool_edot(const CoolTestArgs &a, hipStream_t s);      \
-  int launch_cool_timescale(const CoolTestArgs &a, hipStream_t s); \
+  int launch_dt_mp(const DtArgs &a, const CoolForm &f, hipStream_t s);   \
+  int launch_cool(const CoolTestArgs &a, const CoolForm &f, int what, hipStream_t s);   \
   }
 
 PION_DECLARE_FP(fp_strict)

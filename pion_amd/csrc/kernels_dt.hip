@@ -1,8 +1,8 @@
 // kernels_dt.hip -- the time-step reductions and the cooling test seams; nothing here depends on the equation set.
 //
 //   k_dt       CellTimeStep + cooling-time reduction (calc_timestep.cpp:271-507).
-//   k_dt_mp    the cooling time alone, rate tables in LDS.
-//   k_cool_*   mp_only_cooling on n independent cells (test seams).
+//   k_dt_mp    the cooling time alone, the rate's constants in LDS.
+//   k_cool     mp_only_cooling on n independent cells (test seam).
 //
 // Compiled twice (Makefile): -DPION_FPNS=fp_strict -ffp-contract=off and -DPION_FPNS=fp_fast -ffp-contract=fast.
 #include "dev_cooling.h"
@@ -58,58 +58,18 @@ __global__ __launch_bounds__(256) void k_dt(const DtArgs a)
 }
 
 // The cooling time alone (calc_microphysics_dt -> get_mp_timescales_no_radiation, calc_timestep.cpp:405-507;
-// mp_only_cooling::timescales, mp_only_cooling.cpp:333-368), rate tables in LDS as in k_cooling_dE: a time scale is two
-// Edot evaluations = two bisections of eight dependent look-ups each, which through global memory cost the fused
+// mp_only_cooling::timescales, mp_only_cooling.cpp:333-368), the rate's constants in LDS as in k_cooling_dE: a time scale
+// is two Edot evaluations = two bisections of eight dependent look-ups each, which through global memory cost the fused
 // reduction of the stage kernel a third of its run time (Wind3D 256^3, second-order instance: 1.58 ms with it, 1.03
-// without; this kernel: see DESIGN.md s4.1).  Min over cells with !isbd && isleaf into result[1].
-__global__ __launch_bounds__(256) void k_dt_mp(const DtArgs a)
-{
-  __shared__ double ctab[11 * PION_COOL_NT_MAX];
-  const int NT = a.cool.NT;
-  for (int i = threadIdx.x; i < NT; i += 256) ctab[i] = a.cool.T[i];
-  for (int i = threadIdx.x; i < 5 * NT; i += 256) {
-    ctab[NT + i] = a.cool.tab[i];
-    ctab[6 * NT + i] = a.cool.slope[i];
-  }
-  __syncthreads();
-  CoolDev cool = a.cool;
-  cool.T = ctab;
-  cool.tab = ctab + NT;
-  cool.slope = ctab + 6 * NT;
-  const long nc = a.g.ncell;
-  const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
-  double tmp = 1.0e99;
-  for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < non; k += (long)gridDim.x * blockDim.x) {
-    const long c = ongrid_cell(a.g, k);
-    const uint8_t fl = a.flags[c];
-    if (!(fl & 2) && (fl & 16)) {
-      const double t = Cooling::timescale(cool, a.Ph[0 * nc + c], a.Ph[1 * nc + c], a.gamma);
-      tmp = (t < tmp) ? t : tmp;
-    }
-  }
-  tmp = wave_min64(tmp);
-  if ((threadIdx.x & 63) == 0) atomicMin(&a.result[1], (unsigned long long)__double_as_longlong(tmp));
-}
-int launch_dt_mp(const DtArgs &a, hipStream_t s)
-{
-  const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
-  long nb = (non + 255) / 256;
-  if (nb > 2048) nb = 2048;   // grid-stride, eight blocks per CU: the tables are staged once per block
-  hipLaunchKernelGGL(k_dt_mp, dim3((unsigned)nb), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// The cooling-time reduction for EP.cooling = 2, 4..7 (CoolForm; the CIE curve of 4..7 in LDS).  A kernel of its own
-// with k_dt_mp's loop restated, so that the code of that one stays what it was.  (The full reduction of these flags is
-// k_dt with do_mp = 0 followed by this kernel: pion_gpu_calc_dt_device.)
-// ---------------------------------------------------------------------------
+// without; this kernel: see DESIGN.md s4.1).  Min over cells with !isbd && isleaf into result[1].  One instance per
+// form of the rate; that of the tables ignores f.  (The full reduction of EP.cooling = 2, 4..7 is k_dt with do_mp = 0
+// followed by this kernel: pion_gpu_calc_dt_device.)
 template <int FORM>
-__global__ __launch_bounds__(256) void k_dt_mp_form(const DtArgs a, const CoolForm f)
+__global__ __launch_bounds__(256) void k_dt_mp(const DtArgs a, const CoolForm f)
 {
-  __shared__ double ccrv[(FORM == COOL_FORM_CURVE) ? 3 * PION_COOL_NT_MAX : 1];
-  CoolFormT<FORM> cool;
-  stage_form<FORM>(f, ccrv, cool);
+  __shared__ double clds[CoolOf<FORM>::lds];
+  typename CoolOf<FORM>::type cool;
+  stage_cool<FORM>(a.cool, f, clds, cool);
   const long nc = a.g.ncell;
   const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
   double tmp = 1.0e99;
@@ -124,60 +84,38 @@ __global__ __launch_bounds__(256) void k_dt_mp_form(const DtArgs a, const CoolFo
   tmp = wave_min64(tmp);
   if ((threadIdx.x & 63) == 0) atomicMin(&a.result[1], (unsigned long long)__double_as_longlong(tmp));
 }
-int launch_dt_mp_form(const DtArgs &a, const CoolForm &f, hipStream_t s)
+// grid-stride, eight blocks per CU: the rate's constants are staged once per block
+static inline dim3 dt_blocks(const DtArgs &a)
 {
   const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
-  long nb = (non + 255) / 256;
-  if (nb > 2048) nb = 2048;
-  if (f.flag == 2) hipLaunchKernelGGL(k_dt_mp_form<COOL_FORM_KI02>, dim3((unsigned)nb), dim3(256), 0, s, a, f);
-  else hipLaunchKernelGGL(k_dt_mp_form<COOL_FORM_CURVE>, dim3((unsigned)nb), dim3(256), 0, s, a, f);
+  const long nb = (non + 255) / 256;
+  return dim3((unsigned)((nb > 2048) ? 2048 : nb));
+}
+int launch_dt_mp(const DtArgs &a, const CoolForm &f, hipStream_t s)
+{
+  const int form = cool_form_of(f.flag);
+  if (form == COOL_FORM_KI02) hipLaunchKernelGGL(k_dt_mp<COOL_FORM_KI02>, dt_blocks(a), dim3(256), 0, s, a, f);
+  else if (form == COOL_FORM_CURVE) hipLaunchKernelGGL(k_dt_mp<COOL_FORM_CURVE>, dt_blocks(a), dim3(256), 0, s, a, f);
+  else hipLaunchKernelGGL(k_dt_mp<COOL_FORM_TABLE>, dt_blocks(a), dim3(256), 0, s, a, f);
   return (int)hipGetLastError();
 }
 int launch_dt(const DtArgs &a, hipStream_t s)
 {
-  const long non = (long)a.g.ng[0] * a.g.ng[1] * a.g.ng[2];
-  long nb = (non + 255) / 256;
-  if (nb > 2048) nb = 2048;
-  hipLaunchKernelGGL(k_dt, dim3((unsigned)nb), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_dt, dt_blocks(a), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
-// cooling test seams
+// cooling test seam: mp_only_cooling on n independent cells, the rate's constants in LDS as the production kernels hold
+// them.  what: 0 TimeUpdateMP, 1 Edot, 2 timescales (cooling time only: edot[i] = t_cool), 3 the CIE curve itself,
+// edot[i] = Lambda(T[i]) through the kernels' own curve_rate.
 // ---------------------------------------------------------------------------
-__global__ void k_cool_update(const CoolTestArgs a)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.n) return;
-  int err = 0;
-  const double *p = a.Pin + (long)i * a.nvar;
-  double *o = a.Pout + (long)i * a.nvar;
-  for (int v = 0; v < a.nvar; v++) o[v] = p[v];
-  o[1] = Cooling::time_update(a.cool, p[0], p[1], a.dt, a.gamma, err);
-  if (err) atomicOr(a.errword, err);
-}
-__global__ void k_cool_edot(const CoolTestArgs a)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.n) return;
-  a.edot[i] = Cooling::edot(a.cool, a.rho[i], a.T[i]);
-}
-// mp_only_cooling::timescales (cooling time only) of n independent cells: edot[i] = t_cool
-__global__ void k_cool_timescale(const CoolTestArgs a)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.n) return;
-  const double *p = a.Pin + (long)i * a.nvar;
-  a.edot[i] = Cooling::timescale(a.cool, p[0], p[1], a.gamma);
-}
-// the same seams for EP.cooling = 2, 4..7 (what: 0 TimeUpdateMP, 1 Edot, 2 timescales), and what = 3: the CIE curve
-// itself, edot[i] = Lambda(T[i]) through the kernels' own curve_rate (curve in LDS, as the production kernels hold it)
 template <int FORM>
-__global__ __launch_bounds__(256) void k_cool_form(const CoolTestArgs a, const CoolForm f, const int what)
+__global__ __launch_bounds__(256) void k_cool(const CoolTestArgs a, const CoolForm f, const int what)
 {
-  __shared__ double ccrv[(FORM == COOL_FORM_CURVE) ? 3 * PION_COOL_NT_MAX : 1];
-  CoolFormT<FORM> cool;
-  stage_form<FORM>(f, ccrv, cool);
+  __shared__ double clds[CoolOf<FORM>::lds];
+  typename CoolOf<FORM>::type cool;
+  stage_cool<FORM>(a.cool, f, clds, cool);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n) return;
   if (what == 0) {
@@ -198,26 +136,14 @@ __global__ __launch_bounds__(256) void k_cool_form(const CoolTestArgs a, const C
     else a.edot[i] = 0.0;
   }
 }
-int launch_cool_form(const CoolTestArgs &a, const CoolForm &f, int what, hipStream_t s)
+int launch_cool(const CoolTestArgs &a, const CoolForm &f, int what, hipStream_t s)
 {
-  if (what < 0 || what > 3 || (what == 3 && f.flag == 2)) return -1;
-  if (f.flag == 2) hipLaunchKernelGGL(k_cool_form<COOL_FORM_KI02>, dim3((a.n + 255) / 256), dim3(256), 0, s, a, f, what);
-  else hipLaunchKernelGGL(k_cool_form<COOL_FORM_CURVE>, dim3((a.n + 255) / 256), dim3(256), 0, s, a, f, what);
-  return (int)hipGetLastError();
-}
-int launch_cool_timescale(const CoolTestArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_cool_timescale, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
-}
-int launch_cool_update(const CoolTestArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_cool_update, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
-}
-int launch_cool_edot(const CoolTestArgs &a, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_cool_edot, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+  const int form = cool_form_of(f.flag);
+  if (what < 0 || what > 3 || (what == 3 && form != COOL_FORM_CURVE)) return -1;
+  const dim3 nb((a.n + 255) / 256);
+  if (form == COOL_FORM_KI02) hipLaunchKernelGGL(k_cool<COOL_FORM_KI02>, nb, dim3(256), 0, s, a, f, what);
+  else if (form == COOL_FORM_CURVE) hipLaunchKernelGGL(k_cool<COOL_FORM_CURVE>, nb, dim3(256), 0, s, a, f, what);
+  else hipLaunchKernelGGL(k_cool<COOL_FORM_TABLE>, nb, dim3(256), 0, s, a, f, what);
   return (int)hipGetLastError();
 }
 

@@ -145,91 +145,20 @@ __global__ __launch_bounds__(256) void k_cell_test(const CellTestArgs a)
 // energy component of dU changes, so the kernel leaves dE = PtoU(p_new)[ERG] - PtoU(P)[ERG] (the same two
 // PtoU evaluations the reference subtracts) for k_stage_rows2 to start its dU from.  The adaptive
 // Cash-Karp loop diverges from cell to cell: here it runs at full occupancy, outside the stage kernel.
+// The rate's constants reach LDS first (stage_cool, dev_cooling.h); one instance per form of the rate, that of the tables
+// (EP.cooling = 8) ignores f.
 // ---------------------------------------------------------------------------
-template <int EQ, int NTR>
-__global__ __launch_bounds__(256) void k_cooling_dE(const StageArgs a)
-{
-  typedef Eqn<EQ, NTR> E;
-  constexpr int NV = E::NV;
-  const unsigned gx = (a.g.ng[0] + 63) / 64, gy = (a.g.ng[1] + 3) / 4;
-  const unsigned np1 = (unsigned)(a.kz1 - a.kz0), np2 = (a.kz3 > a.kz2) ? (unsigned)(a.kz3 - a.kz2) : 0u;
-  const unsigned ntile = gx * gy * (np1 + np2);
-  // The rate tables (temperature grid, five rates and their slopes: 11 NT doubles, 17.6 KB at NT = 200) go to LDS
-  // first: an Edot is a bisection (8 dependent look-ups) plus 10 table reads, a Cash-Karp step six of those, and a
-  // thread is bound by the latency of that chain -- LDS answers several times sooner than the L1 / L2 path.
-  __shared__ double ctab[11 * PION_COOL_NT_MAX];
-  const int NT = a.cool.NT;
-  for (int i = threadIdx.x; i < NT; i += 256) ctab[i] = a.cool.T[i];
-  for (int i = threadIdx.x; i < 5 * NT; i += 256) {
-    ctab[NT + i] = a.cool.tab[i];
-    ctab[6 * NT + i] = a.cool.slope[i];
-  }
-  __syncthreads();
-  CoolDev cool = a.cool;
-  cool.T = ctab;
-  cool.tab = ctab + NT;
-  cool.slope = ctab + 6 * NT;
-  const unsigned t = (unsigned)xcd_tile(blockIdx.x, ntile);
-  if (t >= ntile) return;
-  const int ix = (int)((t % gx) * 64 + (threadIdx.x & 63));
-  const int iy = (int)(((t / gx) % gy) * 4 + (threadIdx.x >> 6));
-  const unsigned pz = t / (gx * gy);
-  const int iz = (pz < np1) ? a.kz0 + (int)pz : a.kz2 + (int)(pz - np1);
-  if (ix >= a.g.ng[0] || iy >= a.g.ng[1]) return;
-  const long nc = a.g.ncell;
-  // (a 2-D launch of the rows kernel: a.g.ng[1] rows per range and the "plane" of a strip is the first row of its
-  // range, rows_tiling.h "2-D row ranges")
-  const long c = (a.g.ndim == 2) ? (long)(ix + a.g.nbc[0]) + a.g.sy * (iy + iz + a.g.nbc[1])
-                                 : (long)(ix + a.g.nbc[0]) + a.g.sy * (iy + a.g.nbc[1]) + a.g.sz * (iz + a.g.nbc[2]);
-  double dE = 0.0;
-  if (a.flags[c] & 4 /*ISDOMAIN*/) {
-    const double g = a.fc.gamma;
-    int err = 0;
-#ifdef PION_FAST_MATH
-    // fast build: only the pressure changes, so PtoU(p_new)[ERG] - PtoU(P)[ERG] = (p_new - p) / (gamma - 1) -- the
-    // kinetic (and magnetic) energy the reference adds to both terms and subtracts again is not read at all (two
-    // variables instead of NV per cell; the difference to the reference form is the rounding of that cancellation)
-    const double ro = a.Pc[qRO * nc + c], pg = a.Pc[qPG * nc + c];
-    const double pnew = Cooling::time_update(cool, ro, pg, a.dt, g, err);
-    dE = (pnew - pg) / (g - 1.0);
-#else
-    double P0[NV], pn[NV], ui[NV], uf[NV];
-#pragma unroll
-    for (int v = 0; v < NV; v++) pn[v] = P0[v] = a.Pc[v * nc + c];
-    pn[qPG] = Cooling::time_update(cool, P0[qRO], P0[qPG], a.dt, g, err);
-    E::PtoU(P0, ui, g);
-    E::PtoU(pn, uf, g);
-    dE = uf[uERG] - ui[uERG];
-#endif
-    if (err) atomicOr(a.errword, err);
-  }
-  a.dE[c] = dE;
-}
-template <int EQ, int NTR>
-static int cooling_go(const StageArgs &a, hipStream_t s)
-{
-  const unsigned gx = (a.g.ng[0] + 63) / 64, gy = (a.g.ng[1] + 3) / 4;
-  const unsigned np = (unsigned)(a.kz1 - a.kz0) + ((a.kz3 > a.kz2) ? (unsigned)(a.kz3 - a.kz2) : 0u);
-  const unsigned ntile = gx * gy * np;
-  hipLaunchKernelGGL((k_cooling_dE<EQ, NTR>), dim3(((ntile + 7) / 8) * 8), dim3(256), 0, s, a);
-  return (int)hipGetLastError();
-}
-
-// The same launch for EP.cooling = 2, 4..7 (mp_only_cooling::Edot, mp_only_cooling.cpp:377-482).  The CIE curve of
-// flags 4..7 -- knots, values and spline coefficients, 3 n doubles, 6 KB at n = 256 -- goes to LDS as the tables do:
-// an Edot is a knot search and three dependent reads, a Cash-Karp step six of those.  KI02 stages nothing.  (A kernel
-// of its own with k_cooling_dE's cell code restated, so that the code of that one stays what it was.)
 template <int EQ, int NTR, int FORM>
-__global__ __launch_bounds__(256) void k_cooling_dE_form(const StageArgs a, const CoolForm f)
+__global__ __launch_bounds__(256) void k_cooling_dE(const StageArgs a, const CoolForm f)
 {
   typedef Eqn<EQ, NTR> E;
   constexpr int NV = E::NV;
   const unsigned gx = (a.g.ng[0] + 63) / 64, gy = (a.g.ng[1] + 3) / 4;
   const unsigned np1 = (unsigned)(a.kz1 - a.kz0), np2 = (a.kz3 > a.kz2) ? (unsigned)(a.kz3 - a.kz2) : 0u;
   const unsigned ntile = gx * gy * (np1 + np2);
-  __shared__ double ccrv[(FORM == COOL_FORM_CURVE) ? 3 * PION_COOL_NT_MAX : 1];
-  CoolFormT<FORM> cool;
-  stage_form<FORM>(f, ccrv, cool);
+  __shared__ double clds[CoolOf<FORM>::lds];
+  typename CoolOf<FORM>::type cool;
+  stage_cool<FORM>(a.cool, f, clds, cool);
   const unsigned t = (unsigned)xcd_tile(blockIdx.x, ntile);
   if (t >= ntile) return;
   const int ix = (int)((t % gx) * 64 + (threadIdx.x & 63));
@@ -266,20 +195,17 @@ __global__ __launch_bounds__(256) void k_cooling_dE_form(const StageArgs a, cons
   }
   a.dE[c] = dE;
 }
-static inline unsigned cooling_blocks(const StageArgs &a)
+template <int EQ, int NTR>
+static int cooling_go(const StageArgs &a, const CoolForm &f, hipStream_t s)
 {
   const unsigned gx = (a.g.ng[0] + 63) / 64, gy = (a.g.ng[1] + 3) / 4;
   const unsigned np = (unsigned)(a.kz1 - a.kz0) + ((a.kz3 > a.kz2) ? (unsigned)(a.kz3 - a.kz2) : 0u);
   const unsigned ntile = gx * gy * np;
-  return ((ntile + 7) / 8) * 8;
-}
-template <int EQ, int NTR>
-static int cooling_form_go(const StageArgs &a, const CoolForm &f, hipStream_t s)
-{
-  if (f.flag == 2)
-    hipLaunchKernelGGL((k_cooling_dE_form<EQ, NTR, COOL_FORM_KI02>), dim3(cooling_blocks(a)), dim3(256), 0, s, a, f);
-  else
-    hipLaunchKernelGGL((k_cooling_dE_form<EQ, NTR, COOL_FORM_CURVE>), dim3(cooling_blocks(a)), dim3(256), 0, s, a, f);
+  const dim3 nb(((ntile + 7) / 8) * 8);
+  const int form = cool_form_of(f.flag);
+  if (form == COOL_FORM_KI02) hipLaunchKernelGGL((k_cooling_dE<EQ, NTR, COOL_FORM_KI02>), nb, dim3(256), 0, s, a, f);
+  else if (form == COOL_FORM_CURVE) hipLaunchKernelGGL((k_cooling_dE<EQ, NTR, COOL_FORM_CURVE>), nb, dim3(256), 0, s, a, f);
+  else hipLaunchKernelGGL((k_cooling_dE<EQ, NTR, COOL_FORM_TABLE>), nb, dim3(256), 0, s, a, f);
   return (int)hipGetLastError();
 }
 
@@ -372,21 +298,12 @@ int PION_CAT(launch_stage_, PION_SUFFIX)(const StageArgs &a, hipStream_t s)
     default: return -1;
   }
 }
-int PION_CAT(launch_cooling_dE_, PION_SUFFIX)(const StageArgs &a, hipStream_t s)
+int PION_CAT(launch_cooling_dE_, PION_SUFFIX)(const StageArgs &a, const CoolForm &f, hipStream_t s)
 {
   switch (a.ntracer) {
-    case 0: return cooling_go<PION_EQ, 0>(a, s);
-    case 1: return cooling_go<PION_EQ, 1>(a, s);
-    case 2: return cooling_go<PION_EQ, 2>(a, s);
-    default: return -1;
-  }
-}
-int PION_CAT(launch_cooling_dE_form_, PION_SUFFIX)(const StageArgs &a, const CoolForm &f, hipStream_t s)
-{
-  switch (a.ntracer) {
-    case 0: return cooling_form_go<PION_EQ, 0>(a, f, s);
-    case 1: return cooling_form_go<PION_EQ, 1>(a, f, s);
-    case 2: return cooling_form_go<PION_EQ, 2>(a, f, s);
+    case 0: return cooling_go<PION_EQ, 0>(a, f, s);
+    case 1: return cooling_go<PION_EQ, 1>(a, f, s);
+    case 2: return cooling_go<PION_EQ, 2>(a, f, s);
     default: return -1;
   }
 }

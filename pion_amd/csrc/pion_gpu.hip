@@ -32,7 +32,7 @@ long impl::cell_id(const GridDesc &g, int ix, int iy, int iz)
 
 void impl::time_begin(Handle *h, int slot)
 {
-  if (!h->timing) return;
+  if (!h->timing || slot < 0) return;   // (slot -1: the test seams, which are not timed)
   hipEvent_t e;
   hipEventCreate(&e);
   hipEventRecord(e, h->stream);
@@ -731,11 +731,9 @@ int pion_gpu_interface_flux(void *handle, int n, int axis, double dt, const doub
   a.Pstar = dp;
   a.errword = h->derr;
   a.fc = make_fluxctx(h, dt);
-  int rc = h->cfg.strict_fp ? fp_strict::launch_flux_test(a, h->stream) : fp_fast::launch_flux_test(a, h->stream);
-  if (rc != 0) {
-    h->err = "interface-flux launch failed";
-    return PION_GPU_EDEVICE;
-  }
+  if (int rc = fp_launch(h, -1, "interface-flux launch failed", fp_strict::launch_flux_test, fp_fast::launch_flux_test, a,
+                         h->stream))
+    return rc;
   HCHECK(h, hipStreamSynchronize(h->stream));
   HCHECK(h, hipMemcpy(F, df, nb, hipMemcpyDeviceToHost));
   HCHECK(h, hipMemcpy(Pstar, dp, nb, hipMemcpyDeviceToHost));
@@ -776,11 +774,9 @@ int pion_gpu_cell_advance(void *handle, int n, double fv_dt, const double *P_in,
     HCHECK(h, hipMalloc(&bt.p, sizeof(double) * (size_t)n));
     a.dt = bt.p;
   }
-  const int rc = h->cfg.strict_fp ? fp_strict::launch_cell_test(a, h->stream) : fp_fast::launch_cell_test(a, h->stream);
-  if (rc != 0) {
-    h->err = "cell-update launch failed";
-    return PION_GPU_EDEVICE;
-  }
+  if (int rc = fp_launch(h, -1, "cell-update launch failed", fp_strict::launch_cell_test, fp_fast::launch_cell_test, a,
+                         h->stream))
+    return rc;
   HCHECK(h, hipStreamSynchronize(h->stream));
   if (dU) HCHECK(h, hipMemcpy(P_out, bo.p, nb, hipMemcpyDeviceToHost));
   if (dt_out) HCHECK(h, hipMemcpy(dt_out, bt.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
@@ -803,47 +799,26 @@ static int cool_go(Handle *h, int n, double dt, const double *Pin, double *Pout,
   a.gamma = h->cfg.gamma;
   a.errword = h->derr;
   a.cool = h->cool;
+  // TimeUpdateMP (Pin -> Pout), the cooling time of each state (Pin -> edot) or Edot (rho, T -> edot); edot: n doubles
+  const int what = !Pin ? 1 : (edot ? 2 : 0);
   DevBuf<double> b0, b1, b2;
-  double *&d0 = b0.p, *&d1 = b1.p, *&d2 = b2.p;
-  int rc;
-  if (Pin) {
-    const size_t nb = sizeof(double) * (size_t)n * a.nvar;
-    HCHECK(h, hipMalloc(&d0, nb));
-    HCHECK(h, hipMalloc(&d1, nb));
-    HCHECK(h, hipMemcpy(d0, Pin, nb, hipMemcpyHostToDevice));
-    a.Pin = d0;
-    a.Pout = d1;
-    if (edot) {  // cooling time of each state (edot = the output array, n doubles)
-      HCHECK(h, hipMalloc(&d2, sizeof(double) * (size_t)n));
-      a.edot = d2;
-      if (form) rc = h->cfg.strict_fp ? fp_strict::launch_cool_form(a, h->form, 2, h->stream) : fp_fast::launch_cool_form(a, h->form, 2, h->stream);
-      else rc = h->cfg.strict_fp ? fp_strict::launch_cool_timescale(a, h->stream) : fp_fast::launch_cool_timescale(a, h->stream);
-      HCHECK(h, hipStreamSynchronize(h->stream));
-      HCHECK(h, hipMemcpy(edot, d2, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    }
-    else {
-      if (form) rc = h->cfg.strict_fp ? fp_strict::launch_cool_form(a, h->form, 0, h->stream) : fp_fast::launch_cool_form(a, h->form, 0, h->stream);
-      else rc = h->cfg.strict_fp ? fp_strict::launch_cool_update(a, h->stream) : fp_fast::launch_cool_update(a, h->stream);
-      HCHECK(h, hipStreamSynchronize(h->stream));
-      HCHECK(h, hipMemcpy(Pout, d1, nb, hipMemcpyDeviceToHost));
-    }
-  }
-  else {
-    const size_t nb = sizeof(double) * (size_t)n;
-    HCHECK(h, hipMalloc(&d0, nb));
-    HCHECK(h, hipMalloc(&d1, nb));
-    HCHECK(h, hipMalloc(&d2, nb));
-    HCHECK(h, hipMemcpy(d0, rho, nb, hipMemcpyHostToDevice));
-    HCHECK(h, hipMemcpy(d1, T, nb, hipMemcpyHostToDevice));
-    a.rho = d0;
-    a.T = d1;
-    a.edot = d2;
-    if (form) rc = h->cfg.strict_fp ? fp_strict::launch_cool_form(a, h->form, 1, h->stream) : fp_fast::launch_cool_form(a, h->form, 1, h->stream);
-    else rc = h->cfg.strict_fp ? fp_strict::launch_cool_edot(a, h->stream) : fp_fast::launch_cool_edot(a, h->stream);
-    HCHECK(h, hipStreamSynchronize(h->stream));
-    HCHECK(h, hipMemcpy(edot, d2, nb, hipMemcpyDeviceToHost));
-  }
-  if (rc != 0) return PION_GPU_EDEVICE;
+  const size_t nb = sizeof(double) * (size_t)n * (Pin ? a.nvar : 1), ne = sizeof(double) * (size_t)n;
+  HCHECK(h, hipMalloc(&b0.p, nb));
+  HCHECK(h, hipMalloc(&b1.p, nb));
+  HCHECK(h, hipMalloc(&b2.p, ne));
+  HCHECK(h, hipMemcpy(b0.p, Pin ? Pin : rho, nb, hipMemcpyHostToDevice));
+  if (!Pin) HCHECK(h, hipMemcpy(b1.p, T, nb, hipMemcpyHostToDevice));
+  a.Pin = Pin ? b0.p : nullptr;
+  a.Pout = Pin ? b1.p : nullptr;
+  a.rho = Pin ? nullptr : b0.p;
+  a.T = Pin ? nullptr : b1.p;
+  a.edot = b2.p;
+  const int rc = fp_launch(h, -1, "cooling seam launch failed", fp_strict::launch_cool, fp_fast::launch_cool, a, h->form,
+                           what, h->stream);
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  if (what == 0) HCHECK(h, hipMemcpy(Pout, b1.p, nb, hipMemcpyDeviceToHost));
+  else HCHECK(h, hipMemcpy(edot, b2.p, ne, hipMemcpyDeviceToHost));
+  if (rc != 0) return rc;
   return check_errword(h);
 }
 int pion_gpu_cooling_update(void *handle, int n, double dt, const double *P_in, double *P_out)
@@ -879,11 +854,8 @@ int pion_gpu_cooling_curve_eval(void *handle, int n, const double *T, double *la
   a.edot = bl.p;
   CoolForm f = h->form;
   f.flag = PION_COOL_WSS09_CIE_ONLY_COOLING;   // (any of 4..7: the curve instance)
-  const int rc = h->cfg.strict_fp ? fp_strict::launch_cool_form(a, f, 3, h->stream) : fp_fast::launch_cool_form(a, f, 3, h->stream);
-  if (rc != 0) {
-    h->err = "cooling-curve launch failed";
-    return PION_GPU_EDEVICE;
-  }
+  if (int rc = fp_launch(h, -1, "cooling-curve launch failed", fp_strict::launch_cool, fp_fast::launch_cool, a, f, 3, h->stream))
+    return rc;
   HCHECK(h, hipStreamSynchronize(h->stream));
   HCHECK(h, hipMemcpy(lambda, bl.p, nb, hipMemcpyDeviceToHost));
   return 0;

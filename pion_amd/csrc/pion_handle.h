@@ -149,6 +149,18 @@ int check_errword(Handle *h);
 struct StageStep { double dt; int space_ooa, is_full_step; };   // dt: the stage's (= FV_dt)
 void stage_physics(const Handle *h, const StageStep &st, StageArgs &a);
 
+// one of kernels.h's launchers, in the handle's floating-point build and inside the timing slot (-1: none); a: what it
+// takes, the stream last
+template <class F, class... A>
+int fp_launch(Handle *h, int slot, const char *failed, F *strict, F *fast, const A &... a)
+{
+  time_begin(h, slot);
+  const int rc = h->cfg.strict_fp ? strict(a...) : fast(a...);
+  time_end(h, slot);
+  if (rc != 0) h->err = failed;
+  return (rc != 0) ? PION_GPU_EDEVICE : 0;
+}
+
 // get_mp_timescales_no_radiation (calc_timestep.cpp:445-459): EP.MP_timestep_limit 1, 2, 3 ask
 // mp_only_cooling::timescales for the cooling time (tc = true); 4 (recombination time only) gets 1e99
 // from it (mp_only_cooling.cpp:338), i.e. no limit; anything else is fatal there (EINVAL in create).

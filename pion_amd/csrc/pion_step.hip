@@ -80,17 +80,6 @@ DtArgs dt_args(const Handle *h, const double *Ph, const int do_mp)
   return a;
 }
 
-// one of kernels.h's launchers, in the handle's floating-point build and inside the timing slot
-template <class Args>
-int fp_launch(Handle *h, int slot, int (*strict)(const Args &, hipStream_t), int (*fast)(const Args &, hipStream_t),
-              const Args &a, hipStream_t s, const char *failed)
-{
-  time_begin(h, slot);
-  const int rc = h->cfg.strict_fp ? strict(a, s) : fast(a, s);
-  time_end(h, slot);
-  if (rc != 0) h->err = failed;
-  return (rc != 0) ? PION_GPU_EDEVICE : 0;
-}
 
 // One stage, or a part of one (PION_STAGE_WHOLE / _INTERIOR / _SLABBOUNDARY).  The split lets the halo
 // exchange of a slab run under the interior: the interior part reads no ghost plane of the slab axis (the last
@@ -104,18 +93,10 @@ static bool stage_can_split(const Handle *h)
          && h->g.ng[sa] > 2 * h->g.nbc[sa] && !(h->cfg.tm_ooa == 1 && h->cfg.sp_ooa == 1);
 }
 
-// min of the cooling time over the state the full step has just written (P), into ddt[1]: k_dt_mp
-static int launch_cooling_time(Handle *h, hipStream_t s)
+// min of the cooling time over the array d.Ph into ddt[1]: k_dt_mp
+static int launch_cooling_time(Handle *h, const DtArgs &d, hipStream_t s)
 {
-  const DtArgs d = dt_args(h, h->dP, 1);
-  if (cool_is_form(h->cfg)) {
-    time_begin(h, 3);
-    const int rc = h->cfg.strict_fp ? fp_strict::launch_dt_mp_form(d, h->form, s) : fp_fast::launch_dt_mp_form(d, h->form, s);
-    time_end(h, 3);
-    if (rc != 0) h->err = "cooling-time kernel launch failed";
-    return (rc != 0) ? PION_GPU_EDEVICE : 0;
-  }
-  return fp_launch(h, 3, fp_strict::launch_dt_mp, fp_fast::launch_dt_mp, d, s, "cooling-time kernel launch failed");
+  return fp_launch(h, 3, "cooling-time kernel launch failed", fp_strict::launch_dt_mp, fp_fast::launch_dt_mp, d, h->form, s);
 }
 
 // Does this handle admit the screened prepass?  3-D Cartesian grid run by k_stage_rows2 with HLLD; every face periodic,
@@ -232,7 +213,7 @@ int run_prepass(Handle *h, const StageStep &st, const StagePart &pt, const doubl
     p.scr_count = h->dscr_count;
   }
   h->last_prepass_screened = (p.hsum != nullptr);
-  return fp_launch(h, 1, fp_strict::launch_prepass, fp_fast::launch_prepass, p, pt.stream, "prepass launch failed");
+  return fp_launch(h, 1, "prepass launch failed", fp_strict::launch_prepass, fp_fast::launch_prepass, p, pt.stream);
 }
 
 // stencil state, start-of-step state and destination
@@ -377,7 +358,7 @@ int stage_end(Handle *h, const StageStep &st, const StagePart &pt, const StageEx
     // (a part launched on the side stream runs beside the interior part: the launch then follows where the compute
     // stream has joined both, pion_gpu_stage_part)
     if (pt.beside) h->dt_mp_pending = true;
-    else if (int rc = launch_cooling_time(h, pt.stream)) return rc;
+    else if (int rc = launch_cooling_time(h, dt_args(h, h->dP, 1), pt.stream)) return rc;
   }
   if (st.is_full_step && a.out == h->dPh) {
     // OA1/OA1: copy the result back to P ("P = Ph", time_integrator.cpp:938-939)
@@ -407,8 +388,9 @@ int stage_launch(Handle *h, const StageStep &st, const StagePart &pt)
   if (int rc = stage_ranges(h, pt, a)) return rc;
   stage_tiling(h, pt.r[0].n(), a);
   const bool form = cool_is_form(h->cfg);
-  if (form) {
-    // EP.cooling = 2, 4..7: the source always comes from its own launch, for the cell-per-thread kernel too (whole grid)
+  if (h->cfg.cooling != 0 && (form || a.use_march != 0)) {
+    // calc_noRT_microphysics_dU as its own launch (thread per cell, full occupancy): dE per cell.  EP.cooling = 2, 4..7
+    // take their source from it for the cell-per-thread kernel too, over the whole grid (k_stage integrates flag 8 itself)
     a.dE = h->ddE;
     StageArgs ac = a;
     if (a.use_march == 0) {
@@ -416,20 +398,8 @@ int stage_launch(Handle *h, const StageStep &st, const StagePart &pt)
       ac.kz1 = h->g.ng[2];
       ac.kz2 = ac.kz3 = 0;
     }
-    time_begin(h, 1);
-    const int rc = h->cfg.strict_fp ? fp_strict::launch_cooling_dE_form(ac, h->form, pt.stream)
-                                    : fp_fast::launch_cooling_dE_form(ac, h->form, pt.stream);
-    time_end(h, 1);
-    if (rc != 0) {
-      h->err = "cooling kernel launch failed";
-      return PION_GPU_EDEVICE;
-    }
-  }
-  else if (h->cfg.cooling != 0 && a.use_march != 0) {
-    // calc_noRT_microphysics_dU as its own launch (thread per cell, full occupancy): dE per cell
-    a.dE = h->ddE;
-    if (int rc = fp_launch(h, 1, fp_strict::launch_cooling_dE, fp_fast::launch_cooling_dE, a, pt.stream,
-                           "cooling kernel launch failed"))
+    if (int rc = fp_launch(h, 1, "cooling kernel launch failed", fp_strict::launch_cooling_dE, fp_fast::launch_cooling_dE,
+                           ac, h->form, pt.stream))
       return rc;
   }
   StageExtras x;
@@ -445,11 +415,11 @@ int stage_launch(Handle *h, const StageStep &st, const StagePart &pt)
   const char *const failed = "stage kernel launch failed (unsupported eqn/solver/tracer combination?)";
   h->launches_last_part = 0;
   if (form && a.use_march == 0) {
-    if (int rc = fp_launch(h, 0, fp_strict::launch_stage_dE, fp_fast::launch_stage_dE, a, pt.stream, failed)) return rc;
+    if (int rc = fp_launch(h, 0, failed, fp_strict::launch_stage_dE, fp_fast::launch_stage_dE, a, pt.stream)) return rc;
     h->launches_last_part = 1;
   }
   else if (!stage_windowed(h)) {
-    if (int rc = fp_launch(h, 0, fp_strict::launch_stage, fp_fast::launch_stage, a, pt.stream, failed)) return rc;
+    if (int rc = fp_launch(h, 0, failed, fp_strict::launch_stage, fp_fast::launch_stage, a, pt.stream)) return rc;
     h->launches_last_part = 1;
   }
   else {
@@ -461,7 +431,7 @@ int stage_launch(Handle *h, const StageStep &st, const StagePart &pt)
         int w_lo, w_hi;
         rows_window(r.lo, r.hi, nw, i, &w_lo, &w_hi);
         const StageArgs w = stage_window(h, a, w_lo, w_hi);
-        if (int rc = fp_launch(h, 0, fp_strict::launch_stage, fp_fast::launch_stage, w, pt.stream, failed)) return rc;
+        if (int rc = fp_launch(h, 0, failed, fp_strict::launch_stage, fp_fast::launch_stage, w, pt.stream)) return rc;
         h->launches_last_part++;
       }
     }
@@ -504,23 +474,13 @@ int pion_gpu_calc_dt_device(void *handle, void **dptr)
   if (!h->dt_cached) {
     // (after a full step through k_stage_rows2 the minima of the new state are already in ddt)
     HCHECK(h, hipMemcpyAsync(h->ddt, h->ddt_init, 2 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if (cool_is_form(h->cfg)) {
-      // EP.cooling = 2, 4..7: k_dt for the dynamics alone, then the cooling time of the same array from k_dt_mp_form
-      DtArgs d = a;
-      d.do_mp = 0;
-      if (int rc = fp_launch(h, 3, fp_strict::launch_dt, fp_fast::launch_dt, d, h->stream, "dt kernel launch failed"))
-        return rc;
-      if (a.do_mp) {
-        const int rc = h->cfg.strict_fp ? fp_strict::launch_dt_mp_form(a, h->form, h->stream)
-                                        : fp_fast::launch_dt_mp_form(a, h->form, h->stream);
-        if (rc != 0) {
-          h->err = "cooling-time kernel launch failed";
-          return PION_GPU_EDEVICE;
-        }
-      }
-    }
-    else if (int rc = fp_launch(h, 3, fp_strict::launch_dt, fp_fast::launch_dt, a, h->stream, "dt kernel launch failed"))
-      return rc;
+    // EP.cooling = 2, 4..7: k_dt, which carries the tabulated rate only, for the dynamics alone, then the cooling time of
+    // the same array from k_dt_mp
+    const bool form = cool_is_form(h->cfg);
+    DtArgs d = a;
+    if (form) d.do_mp = 0;
+    if (int rc = fp_launch(h, 3, "dt kernel launch failed", fp_strict::launch_dt, fp_fast::launch_dt, d, h->stream)) return rc;
+    if (int rc = (form && a.do_mp) ? launch_cooling_time(h, a, h->stream) : 0) return rc;
     h->dt_cached = true;
   }
   if (dptr) *dptr = h->ddt;
@@ -606,7 +566,7 @@ int pion_gpu_stage_part(void *handle, double dt_stage, int space_ooa, int is_ful
     HCHECK(h, hipStreamWaitEvent(h->stream, h->ev_bdone, 0));
     if (h->dt_mp_pending) {
       h->dt_mp_pending = false;
-      if (int rc2 = launch_cooling_time(h, h->stream)) return rc2;
+      if (int rc2 = launch_cooling_time(h, dt_args(h, h->dP, 1), h->stream)) return rc2;
     }
     return order_after_unpack(h);
   }

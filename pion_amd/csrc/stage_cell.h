@@ -1,5 +1,5 @@
 // stage_cell.h -- the body of the cell-per-thread stage kernel, included by kernels_fp.hip into k_stage and, with
-// PION_STAGE_DE defined, into k_stage_dE: there the microphysics source arrives as dE per cell from k_cooling_dE_form
+// PION_STAGE_DE defined, into k_stage_dE: there the microphysics source arrives as dE per cell from k_cooling_dE
 // (EP.cooling = 2, 4..7) instead of being integrated in place.  A textual include and not a function template, so
 // that k_stage compiles from exactly the text it had: its code is pinned (profiles/tools/isa_diff.py).
 // In scope: the template parameters EQ, NTR, SOLVER and the kernel argument `const StageArgs a`.

@@ -9,9 +9,11 @@ M3's initial state without its wind source, and a hot blast (tests/cooling_forms
 process:
     flag 8 (tables: the baseline), flag 6 on the 64-knot uniform curve (interval from the knot spacing), flag 7 on the
     9-knot curve (bisection), flag 2 (KI02: two exponentials and a root, no table).
-HIP events of the library's own timing slots around the cooling launch of each stage (k_cooling_dE / k_cooling_dE_form;
-Euler has no prepass, which shares the slot) and around the cooling-time launch behind each full step (k_dt_mp /
-k_dt_mp_form; timing is switched on after the first time step, so k_dt is not in it).  One warm-up step is not timed."""
+HIP events of the library's own timing slots around the cooling launch of each stage (k_cooling_dE<EQ,NTR,FORM>, FORM =
+table, curve or KI02 by the flag; k_cooling_dE / k_cooling_dE_form in a library from before the kernels were unified,
+which PION_GPU_LIB may name for an A/B run; Euler has no prepass, which shares the slot) and around the cooling-time
+launch behind each full step (k_dt_mp<FORM>, formerly k_dt_mp / k_dt_mp_form; timing is switched on after the first time
+step, so k_dt is not in it).  One warm-up step is not timed."""
 import argparse
 import json
 import os
