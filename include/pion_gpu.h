@@ -229,6 +229,26 @@ typedef struct pion_gpu_proj_field {
 } pion_gpu_proj_field;
 long pion_gpu_project_count(void *handle, int axis, int nfields);
 int pion_gpu_project(void *handle, int which, int axis, int nfields, const pion_gpu_proj_field *fields, void *dbuf);
+/* The same images of a slab-decomposed run, the sums carried from rank to rank (dev_project.h, "parts"): this handle
+ * holds the planes [plane_lo, plane_lo + n) of the slab axis (z in 3-D, R in (z,R); n = the handle's own ng of that axis)
+ * out of global_planes.  dimg is the image of the WHOLE domain, [nfields][NJ_global][NI_global] doubles in DEVICE memory,
+ * pion_gpu_project_part_count of them: in/out.  Rank 0 starts from +0.0 everywhere; every rank runs its part on what
+ * the rank below left, in increasing rank; after the rank with last = 1 the image is == pion_gpu_project on one handle
+ * of the whole domain.  3-D along z: the running sums are continued, only `last` multiplies by dx.  3-D along x, y: the
+ * rank's own rows are written at row offset plane_lo, the others are left as they are.  (z,R): every impact row below
+ * the rank's upper edge gains the segments of the rank's own rows; the geometry takes global row indices and
+ * global_xmin, the R origin of the whole grid; the slope of the rank's last own row reads the first upper slab ghost
+ * row of the array (the halo exchange has filled it), no other ghost cell is read; only `last` finishes.
+ * Enqueued on the compute stream, returns at once.  A part with plane_lo = 0, global_planes = n, last = 1 on a buffer of
+ * +0.0 is == pion_gpu_project.  EINVAL and a text: everything pion_gpu_project refuses; plane_lo < 0; plane_lo + n >
+ * global_planes; a global_xmin that is not finite; a null part or buffer. */
+typedef struct pion_gpu_proj_part {
+  int plane_lo, global_planes, last;
+  double global_xmin;
+} pion_gpu_proj_part;
+long pion_gpu_project_part_count(void *handle, int axis, int nfields, const pion_gpu_proj_part *part);
+int pion_gpu_project_part(void *handle, int which, int axis, int nfields, const pion_gpu_proj_field *fields,
+                          const pion_gpu_proj_part *part, void *dimg);
 /* adopt caller-owned device buffers (e.g. torch tensors) instead of internal ones;
  * both must hold nvar*ncell_all doubles */
 int pion_gpu_bind_device_state(void *handle, void *dP, void *dPh);

@@ -105,11 +105,35 @@ int pion_host_sim_set_output_filetype(void *sim, int type);
  *   step or time, the final state) is accompanied by <base>_proj_<rank, 4 digits>.<step, 8 digits>.fits; nfields = 0
  *   turns that off.  Cadence, the time-step clip, checkpoints and every dt are untouched.
  * EINVAL and a text, never an exit: everything pion_gpu_project refuses (1-D, spherical and 2-D Cartesian grids, a
- * line of sight along the axis of a cylindrical grid, NR == 1, a bad field, b != 0 without cooling); a sim with a slab
- * extent set or a communicator of more than one rank (the images of several ranks are not assembled); a path that
- * cannot be created. */
+ * line of sight along the axis of a cylindrical grid, NR == 1, a bad field, b != 0 without cooling); a path that cannot
+ * be created; one rank of a slab run that has a slab extent but no communicator of more than one rank, or such a
+ * communicator but no extent, or a communicator without the send / receive pair.
+ * One rank of a slab run with both (pion_host_sim_set_slab_extent, pion_host_sim_set_comm): the call is COLLECTIVE, every
+ *   rank makes it with the same arguments.  The image of the whole domain travels from rank 0 upwards, each rank
+ *   continuing the running sums over its own planes (pion_gpu_project_part; dev_project.h, "parts"); the last rank
+ *   writes the one file -- byte for byte the file a single-rank sim of the global problem writes, its header stating
+ *   the global NGrid / Xmin / Xmax and nothing rank-local -- and the other ranks create nothing.  Byte for byte holds
+ *   where dx and the slab axis' xmin are dyadic (every rank's xmin - plane_lo dx is then the global Xmin exactly, as
+ *   the slab decomposition of a (z,R) grid requires anyway); otherwise the header's Xmin and the Abel geometry are
+ *   evaluated with that difference, which may be an ulp off the single grid's.  The column sums of a 3-D grid use no
+ *   position and are bit for bit in any case.  The regular outputs
+ *   name it <base>_proj_0000.<step>.fits whatever the rank count.  A rank that fails passes the failure on: every rank
+ *   above it returns EINVAL, no file appears, no rank blocks. */
 int pion_host_sim_write_projection(void *sim, const char *path, int axis, int nfields, const pion_gpu_proj_field *fields);
 int pion_host_sim_set_projection_output(void *sim, int axis, int nfields, const pion_gpu_proj_field *fields);
+/* The rules of the images as host functions (pion_amd/csrc/dev_project.h), without a sim or a device: cfg describes the
+ * grid, A is a whole array [nvar][ncell_all] with its ghost cells.  What a backend table without projection entries gets.
+ *   pion_host_project_on_host:      every pixel by proj_column / abel_column, img = [nfields][NJ][NI]
+ *   pion_host_project_part_on_host: this grid as one rank's part (pion_gpu_project_part), added into the image of the
+ *                                   whole domain img = [nfields][NJ_global][NI_global], in/out
+ *   pion_host_project_part_refused: NULL, or the text with which pion_gpu_project_part refuses these arguments
+ * EINVAL for what is refused or null. */
+const char *pion_host_project_part_refused(const pion_gpu_config *cfg, int axis, int nfields, const pion_gpu_proj_field *fields,
+                                           const pion_gpu_proj_part *part, const void *img);
+int pion_host_project_on_host(const pion_gpu_config *cfg, int axis, int nfields, const pion_gpu_proj_field *fields,
+                              const double *A, double *img);
+int pion_host_project_part_on_host(const pion_gpu_config *cfg, int axis, int nfields, const pion_gpu_proj_field *fields,
+                                   const pion_gpu_proj_part *part, const double *A, double *img);
 typedef struct pion_host_snapshot_info {
   double t_start, t_finish, t_sim, min_timestep, last_dt;   /* SimPM.starttime, finishtime, simtime, min_timestep, last_dt */
   double opfreq_time, next_optime;

@@ -45,6 +45,19 @@ class ProjField(C.Structure):
     _fields_ = [("name", C.c_char * 16), ("a", C.c_int), ("var", C.c_int), ("coef", C.c_double), ("b", C.c_double)]
 
 
+class ProjPart(C.Structure):
+    """pion_gpu_proj_part (include/pion_gpu.h): a rank's planes of the slab axis in a slab run's image"""
+    _fields_ = [("plane_lo", C.c_int), ("global_planes", C.c_int), ("last", C.c_int), ("global_xmin", C.c_double)]
+
+
+def proj_part(part):
+    """an abi.ProjPart from one, or from (plane_lo, global_planes, last, global_xmin)"""
+    if isinstance(part, ProjPart):
+        return part
+    lo, n, last, xmin = part
+    return ProjPart(int(lo), int(n), int(last), float(xmin))
+
+
 def proj_fields(fields):
     """a ctypes array of ProjField from dicts / tuples (name, a[, var[, coef[, b]]]); defaults var -1, coef 1, b 0.
     A name longer than 15 bytes is handed over unterminated, so that the library refuses it."""

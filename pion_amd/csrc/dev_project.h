@@ -278,5 +278,80 @@ inline double abel_column(const GridDesc &g, const OutputCfg &o, const pion_gpu_
   return abel_finish(result);
 }
 
+// ---- parts: the image of a slab-decomposed run, the sums carried from rank to rank.  A rank holds the planes
+// [plane_lo, plane_lo + n) of the slab axis (z in 3-D, y/R in 2-D; n = g.ng of that axis) out of global_planes.  It
+// works into an image of the WHOLE domain that it receives from the rank below (rank 0: +0.0 everywhere) and hands to
+// the rank above; after the last rank (`last`) the image is == the one a single grid of the whole domain gives.
+//   3-D along z:      every pixel's running sum s is continued over the rank's planes in increasing index -- proj_add,
+//                     entered with the s of the rank below; only the last rank applies proj_times_dx.
+//   3-D along x, y:   a pixel lies wholly in one rank: the rank finishes its own image rows as proj_column does and
+//                     writes them at row offset plane_lo of the whole image; the other rows stay as received.
+//   cylindrical:      for every impact row j of the WHOLE grid below the rank's upper edge (j < plane_lo + n) the rank
+//                     adds the segments ir of its own rows with ir >= abel_start(j), in increasing ir, into the running
+//                     result[j] -- abel_add, unchanged.  abel_r, abel_b, abel_grid_max, abel_start, abel_weights and
+//                     abel_slope take GLOBAL row indices and the whole grid's R origin and NR (proj_part_grid); the
+//                     slope of the rank's last own row reads v of the next rank's first row from the first upper slab
+//                     ghost row (the halo exchange has filled it); the global last row takes the slope of the row before
+//                     it; only the last rank applies abel_finish and the b > grid_max zero.
+//                     Nothing else outside the on-grid cells is read: no x ghost, no lower slab ghost.
+// A part with plane_lo = 0, global_planes = n, last = 1 on an image of +0.0 takes exactly the steps of proj_column /
+// abel_column.
+struct ProjPart {
+  int plane_lo, global_planes, last;
+  double global_xmin;
+};
+inline const char *proj_refused_part(const GridDesc &g, const pion_gpu_proj_part *part)
+{
+  if (!part) return "project: no part";
+  const int n = g.ng[g.ndim - 1];
+  if (part->plane_lo < 0) return "project: a part's plane_lo is not negative";
+  if ((long)part->plane_lo + n > (long)part->global_planes) return "project: a part's planes end above global_planes";
+  if (!(std::fabs(part->global_xmin) <= 1.7976931348623157e308)) return "project: a part's global_xmin is finite";
+  return nullptr;
+}
+// the grid the Abel geometry functions are evaluated with: the whole grid's R origin (its NR is part.global_planes)
+PION_PRJ_HD GridDesc proj_part_grid(const GridDesc &g, const ProjPart &part)
+{
+  GridDesc gg = g;
+  if (g.cyl == 1) gg.xmin[1] = part.global_xmin;
+  return gg;
+}
+// the image of the whole domain: geometry of the rank's own cells, image rows of the whole grid
+PION_PRJ_HD bool proj_part_along_slab(const GridDesc &g, const int axis) { return g.cyl != 1 && axis == g.ndim - 1; }
+PION_PRJ_HD int proj_part_nj(const GridDesc &g, const ProjGeom &q, const int axis, const ProjPart &part)
+{
+  return proj_part_along_slab(g, axis) ? q.nj : part.global_planes;
+}
+PION_PRJ_HD long proj_part_count(const GridDesc &g, const ProjGeom &q, const int axis, const ProjPart &part, const int nfields)
+{
+  return (long)nfields * proj_part_nj(g, q, axis, part) * q.ni;
+}
+// 3-D along the slab axis: the pixel's sum continued from `carried`
+inline double proj_column_part(const GridDesc &g, const OutputCfg &o, const pion_gpu_proj_field &f, const ProjGeom &q,
+                               const ProjPart &part, const double *S, const long first, const double carried)
+{
+  double s = carried;
+  for (int k = 0; k < q.nsum; k++) s = proj_add(s, proj_value(g, o, f, S, first + k * q.ss));
+  return part.last ? proj_times_dx(g, s) : s;
+}
+// cylindrical: impact row j of the whole grid (j < plane_lo + n), column whose local row-0 cell is `first`; gg =
+// proj_part_grid(g, part)
+inline double abel_column_part(const GridDesc &g, const GridDesc &gg, const OutputCfg &o, const pion_gpu_proj_field &f,
+                               const ProjGeom &q, const ProjPart &part, const double *S, const long first, const int j,
+                               const double carried)
+{
+  const int nr = part.global_planes, lo = part.plane_lo, hi = part.plane_lo + q.nsum;
+  double result = carried;
+  const int ir0 = abel_start(gg, nr, j);
+  for (int ir = (ir0 > lo) ? ir0 : lo; ir < hi; ir++) {
+    const int m = (ir < nr - 1) ? ir : nr - 2;
+    const double s = abel_slope(gg, m, proj_value(g, o, f, S, first + (long)(m - lo) * q.ss),
+                                proj_value(g, o, f, S, first + (long)(m + 1 - lo) * q.ss));
+    result = abel_add(result, proj_value(g, o, f, S, first + (long)(ir - lo) * q.ss), s, abel_weights(gg, nr, j, ir));
+  }
+  if (!part.last) return result;
+  return (abel_b(gg, j) > abel_grid_max(gg, nr)) ? 0.0 : abel_finish(result);
+}
+
 }  // namespace pion
 #endif

@@ -485,11 +485,67 @@ int sim_control_gpu::write_fits(const char *path)
 }
 
 // ---- projected images (the rules: dev_project.h) -----------------------------------------------------------------
+// ---- dev_project.h's functions in a host loop, over a whole array A ([nvar][ncell], ghosts included): what a backend
+// table without projection entries gets, and the C view at the end of this file
+// the images of a single grid, [nfields][NJ][NI]
+static void project_on_host(const pion::GridDesc &g, const pion::OutputCfg &o, int axis, int nfields, const pion_gpu_proj_field *fields,
+                     const double *A, double *img)
+{
+  const pion::ProjGeom q = pion::proj_geom(g, axis);
+  for (int f = 0; f < nfields; f++)
+    for (long j = 0; j < q.nj; j++)
+      for (long i = 0; i < q.ni; i++) {
+        const long first = q.c0 + i * q.si + j * q.sj;
+        img[((long)f * q.nj + j) * q.ni + i] = (g.cyl == 1) ? pion::abel_column(g, o, fields[f], q, A, first, (int)j)
+                                                            : pion::proj_column(g, o, fields[f], q, axis, A, first);
+      }
+}
+// one rank's part, into the image of the whole domain [nfields][NJ_global][NI_global] (in/out)
+static void project_part_on_host(const pion::GridDesc &g, const pion::OutputCfg &o, int axis, int nfields,
+                          const pion_gpu_proj_field *fields, const pion::ProjPart &pp, const double *A, double *img)
+{
+  const pion::ProjGeom q = pion::proj_geom(g, axis);
+  const pion::GridDesc gg = pion::proj_part_grid(g, pp);
+  const bool along = pion::proj_part_along_slab(g, axis);
+  const long npix = (long)pion::proj_part_nj(g, q, axis, pp) * q.ni;
+  for (int f = 0; f < nfields; f++) {
+    double *out = img + (long)f * npix;
+    if (g.cyl == 1) {
+      for (long j = 0; j < pp.plane_lo + q.nsum; j++)   // the impact rows below this rank's upper edge
+        for (long i = 0; i < q.ni; i++)
+          out[j * q.ni + i] = pion::abel_column_part(g, gg, o, fields[f], q, pp, A, q.c0 + i * q.si, (int)j, out[j * q.ni + i]);
+      continue;
+    }
+    for (long j = 0; j < q.nj; j++)
+      for (long i = 0; i < q.ni; i++) {
+        const long first = q.c0 + i * q.si + j * q.sj;
+        double &px = out[(j + (along ? 0 : pp.plane_lo)) * q.ni + i];
+        px = along ? pion::proj_column_part(g, o, fields[f], q, pp, A, first, px)
+                   : pion::proj_column(g, o, fields[f], q, axis, A, first);
+      }
+  }
+}
+
+// one rank of a slab run whose images are assembled along the ranks: a slab extent AND a communicator of more than
+// one rank that has the send / receive pair
+bool sim_control_gpu::projection_collective() const
+{
+  return slab.set && comm_ && comm_->world() > 1 && comm_->has_relay();
+}
+
 int sim_control_gpu::projection_refused(int axis, int nfields, const pion_gpu_proj_field *fields, const char *who)
 {
   const char *why = nullptr;
-  if (slab.set || (comm_ && comm_->world() > 1))
-    why = "project: this sim is one rank of a slab run, and the images of more than one rank are not assembled";
+  if ((slab.set || (comm_ && comm_->world() > 1)) && !projection_collective()) {
+    if (!slab.set)
+      why = "project: this sim is one rank of a slab run without a slab extent (set_slab_extent), and its part of the image "
+            "cannot be placed";
+    else if (!comm_ || comm_->world() < 2)
+      why = "project: this sim is one rank of a slab run without a communicator of more than one rank, and the images of "
+            "more than one rank are assembled along the communicator";
+    else
+      why = "project: this sim is one rank of a slab run, and its communicator's send / receive is not supported";
+  }
   if (!why) why = pion::proj_refused_grid(grid_desc(cfg), axis);
   if (!why) why = pion::proj_refused_fields(pion::out_cfg(cfg), nfields, fields);
   if (!why) return 0;
@@ -510,6 +566,71 @@ int sim_control_gpu::set_projection_output(int axis, int nfields, const pion_gpu
   return 0;
 }
 
+// this sim's images -- a whole grid's, or (part) this rank's part added into `img` --, on the device where the backend
+// has the entries, else from a download by the functions above
+int sim_control_gpu::project_images(int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part *part,
+                                    long n, double *img)
+{
+  if (!part && be_->project_count && be_->project_to_host) {
+    if (be_->project_count(h_, axis, nfields) != n) {
+      io_error_ = "write_projection: the backend refuses: " + last_error();
+      return PION_GPU_EINVAL;
+    }
+    const int rc = be_->project_to_host(h_, axis, nfields, fields, img);
+    if (rc) io_error_ = "write_projection: project_to_host failed: " + last_error();
+    return rc;
+  }
+  if (part && be_->project_part_count && be_->project_part_to_host) {
+    if (be_->project_part_count(h_, axis, nfields, part) != n) {
+      io_error_ = "write_projection: the backend refuses: " + last_error();
+      return PION_GPU_EINVAL;
+    }
+    const int rc = be_->project_part_to_host(h_, axis, nfields, fields, part, img);
+    if (rc) io_error_ = "write_projection: project_part_to_host failed: " + last_error();
+    return rc;
+  }
+  const pion::GridDesc g = grid_desc(cfg);
+  std::vector<double> A((size_t)cfg.nvar * g.ncell);
+  if (int rc = be_->download(h_, 0, A.data())) {
+    io_error_ = "write_projection: download failed: " + last_error();
+    return rc;
+  }
+  if (!part) project_on_host(g, pion::out_cfg(cfg), axis, nfields, fields, A.data(), img);
+  else {
+    const pion::ProjPart pp = {part->plane_lo, part->global_planes, part->last, part->global_xmin};
+    project_part_on_host(g, pion::out_cfg(cfg), axis, nfields, fields, pp, A.data(), img);
+  }
+  return 0;
+}
+
+// One rank of a slab run (dev_project.h, "parts"): the image of the whole domain comes from the rank below, gains this
+// rank's part and goes to the rank above.  The invariant that keeps every rank from waiting for ever: whatever `rc`
+// this rank arrives with and whatever happens here, it ALWAYS takes the message of the rank below and ALWAYS sends one
+// to the rank above -- the image, or a failure.  Returns 0 with the image in `img` (complete on the last rank)
+int sim_control_gpu::relay_part(int rc, int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part &part,
+                                std::vector<double> &img)
+{
+  // (refused here: the length is unknown, and the message of the rank below is taken off the wire without a buffer)
+  const size_t bytes = rc ? 0 : img.size() * sizeof(double);
+  int below = 0;
+  const int rrc = comm_->recv_from_below(rc ? nullptr : img.data(), bytes, &below);
+  if (!rc && below) {
+    io_error_ = "write_projection: a rank below failed, no image is written";
+    rc = PION_GPU_EINVAL;
+  }
+  if (!rc && rrc) {
+    io_error_ = "write_projection: receiving the image of the rank below failed: " + comm_->last_error();
+    rc = rrc;
+  }
+  if (!rc) rc = project_images(axis, nfields, fields, &part, (long)img.size(), img.data());
+  const int src = comm_->send_to_above(rc ? nullptr : img.data(), bytes, rc ? 1 : 0);
+  if (!rc && src) {
+    io_error_ = "write_projection: handing the image to the rank above failed: " + comm_->last_error();
+    rc = src;
+  }
+  return rc;
+}
+
 int sim_control_gpu::write_projection(const char *path, int axis, int nfields, const pion_gpu_proj_field *fields)
 {
   io_error_.clear();
@@ -517,14 +638,40 @@ int sim_control_gpu::write_projection(const char *path, int axis, int nfields, c
     io_error_ = "write_projection: no path";
     return PION_GPU_EINVAL;
   }
-  if (int rc = projection_refused(axis, nfields, fields, "write_projection")) return rc;
+  // one rank of a slab run: the call is collective, and the last rank writes the one file
+  const bool chain = projection_collective();
   std::vector<snapshot_param> params;
   long nloc = 0;
-  if (int rc = snapshot_params(params, nloc)) return rc;
-  if (int rc = finish_halo()) {
-    io_error_ = "write_projection: finish_halo failed";
-    return rc;
+  int rc = projection_refused(axis, nfields, fields, "write_projection");
+  if (!rc) rc = snapshot_params(params, nloc);
+  if (!rc && (rc = finish_halo())) io_error_ = "write_projection: finish_halo failed";
+  if (rc && !chain) return rc;
+
+  // 1. the images, native doubles [nfields][NJ][NI] of the whole domain
+  const pion::GridDesc g = grid_desc(cfg);
+  pion::ProjGeom q = pion::ProjGeom();
+  std::vector<double> img;
+  if (!rc) {
+    q = pion::proj_geom(g, axis);
+    if (chain) q.nj = pion::proj_part_along_slab(g, axis) ? q.nj : slab.global_planes;
+    img.assign((size_t)pion::proj_count(q, nfields), 0.0);
   }
+  if (!chain) rc = project_images(axis, nfields, fields, nullptr, (long)img.size(), img.data());
+  else {
+    // global_xmin: the header's Xmin (snapshot_io.cpp: global_view), equal to the single grid's where dx and xmin are dyadic
+    const pion_gpu_proj_part part = {slab.plane_lo, slab.global_planes, comm_->rank() == comm_->world() - 1 ? 1 : 0,
+                                     cfg.xmin[cfg.ndim - 1] - slab.plane_lo * cfg.dx};
+    rc = relay_part(rc, axis, nfields, fields, part, img);
+    if (rc || !part.last) return rc;
+    // the header of a single-rank sim of the whole problem: nothing rank-local
+    for (snapshot_param &p : params) {
+      if (p.key == "pion_rank" || p.key == "pion_slab_lo") p.value = "0";
+      if (p.key == "pion_world") p.value = "1";
+      if (p.key == "pion_slab_n") p.value = std::to_string(slab.global_planes);
+    }
+  }
+  if (rc) return rc;
+  const long npix = (long)q.nj * q.ni, n = pion::proj_count(q, nfields);
   auto real = [](double x) {
     char b[64];
     snprintf(b, sizeof b, "%.17g", x);
@@ -537,38 +684,6 @@ int sim_control_gpu::write_projection(const char *path, int axis, int nfields, c
     params.push_back({k + "var", std::to_string(fields[i].var), 'i'});
     params.push_back({k + "coef", real(fields[i].coef), 'd'});
     params.push_back({k + "b", real(fields[i].b), 'd'});
-  }
-  const pion::GridDesc g = grid_desc(cfg);
-  const pion::OutputCfg o = pion::out_cfg(cfg);
-  const pion::ProjGeom q = pion::proj_geom(g, axis);
-  const long npix = (long)q.nj * q.ni, n = pion::proj_count(q, nfields);
-
-  // 1. the images, native doubles [nfields][NJ][NI]
-  std::vector<double> img((size_t)n);
-  if (be_->project_count && be_->project_to_host) {
-    if (be_->project_count(h_, axis, nfields) != n) {
-      io_error_ = "write_projection: the backend refuses: " + last_error();
-      return PION_GPU_EINVAL;
-    }
-    if (int rc = be_->project_to_host(h_, axis, nfields, fields, img.data())) {
-      io_error_ = "write_projection: project_to_host failed: " + last_error();
-      return rc;
-    }
-  }
-  else {
-    // no projection entries: array 0 whole, every pixel by dev_project.h's functions here
-    std::vector<double> A((size_t)cfg.nvar * g.ncell);
-    if (int rc = be_->download(h_, 0, A.data())) {
-      io_error_ = "write_projection: download failed: " + last_error();
-      return rc;
-    }
-    for (int f = 0; f < nfields; f++)
-      for (long j = 0; j < q.nj; j++)
-        for (long i = 0; i < q.ni; i++) {
-          const long first = q.c0 + i * q.si + j * q.sj;
-          img[(size_t)(f * npix + j * q.ni + i)] = (g.cyl == 1) ? pion::abel_column(g, o, fields[f], q, A.data(), first, (int)j)
-                                                               : pion::proj_column(g, o, fields[f], q, axis, A.data(), first);
-        }
   }
   // 2. the file: big-endian, every extension's header of the same length
   std::vector<unsigned long long> R((size_t)n);
@@ -587,7 +702,7 @@ int sim_control_gpu::write_projection(const char *path, int axis, int nfields, c
     io_error_ = "write_projection: cannot create " + tmp + ": " + strerror(errno);
     return PION_GPU_EINVAL;
   }
-  int rc = (ftruncate(fd, (off_t)total) != 0) ? PION_GPU_EINVAL : 0;   // (the padding reads as zero bytes)
+  rc = (ftruncate(fd, (off_t)total) != 0) ? PION_GPU_EINVAL : 0;   // (the padding reads as zero bytes)
   if (!rc && full_pwrite(fd, primary.data(), primary.size(), 0)) rc = PION_GPU_EINVAL;
   for (int i = 0; i < nfields && !rc; i++) {
     const long at = (long)primary.size() + i * stride;
@@ -603,6 +718,42 @@ int sim_control_gpu::write_projection(const char *path, int axis, int nfields, c
   }
   if (rc) unlink(tmp.c_str());
   return rc;
+}
+
+// ---- C view of dev_project.h's host functions (ctypes: tests; a caller that assembles images with a transport of its
+// own and no device): no sim, no backend -- a configuration and a whole array [nvar][ncell_all]
+extern "C" {
+// null, or the text with which pion_gpu_project_part refuses these arguments (`img`: the caller's image buffer)
+const char *pion_host_project_part_refused(const pion_gpu_config *cfg, int axis, int nfields, const pion_gpu_proj_field *fields,
+                                           const pion_gpu_proj_part *part, const void *img)
+{
+  if (!cfg) return "project: no configuration";
+  const pion::GridDesc g = grid_desc(*cfg);
+  const char *why = pion::proj_refused_grid(g, axis);
+  if (!why) why = pion::proj_refused_fields(pion::out_cfg(*cfg), nfields, fields);
+  if (!why) why = pion::proj_refused_part(g, part);
+  if (!why && !img) why = "project: no buffer";
+  return why;
+}
+// proj_column / abel_column over every pixel: img = [nfields][NJ][NI]
+int pion_host_project_on_host(const pion_gpu_config *cfg, int axis, int nfields, const pion_gpu_proj_field *fields,
+                              const double *A, double *img)
+{
+  if (!cfg || !A || !img) return PION_GPU_EINVAL;
+  const pion::GridDesc g = grid_desc(*cfg);
+  if (pion::proj_refused_grid(g, axis) || pion::proj_refused_fields(pion::out_cfg(*cfg), nfields, fields)) return PION_GPU_EINVAL;
+  project_on_host(g, pion::out_cfg(*cfg), axis, nfields, fields, A, img);
+  return 0;
+}
+// proj_column_part / abel_column_part: this grid's part added into img = [nfields][NJ_global][NI_global] (in/out)
+int pion_host_project_part_on_host(const pion_gpu_config *cfg, int axis, int nfields, const pion_gpu_proj_field *fields,
+                                   const pion_gpu_proj_part *part, const double *A, double *img)
+{
+  if (!A || pion_host_project_part_refused(cfg, axis, nfields, fields, part, img)) return PION_GPU_EINVAL;
+  const pion::ProjPart pp = {part->plane_lo, part->global_planes, part->last ? 1 : 0, part->global_xmin};
+  project_part_on_host(grid_desc(*cfg), pion::out_cfg(*cfg), axis, nfields, fields, pp, A, img);
+  return 0;
+}
 }
 
 }  // namespace pion_host

@@ -88,6 +88,16 @@ typedef struct pion_backend {
    *   project_to_host: project array P on the device and copy the images into `host`; complete on return */
   long (*project_count)(void *handle, int axis, int nfields);
   int (*project_to_host)(void *handle, int axis, int nfields, const pion_gpu_proj_field *fields, double *host);
+  /* A rank's part of a slab run's image (dev_project.h, "parts"; pion_gpu_project_part).  These two entries are read
+   * ONLY inside sim_control_gpu::write_projection of a sim that is one rank of a slab run: any other caller may hand the
+   * loop a table that ends before them.  Both NULL: the writer takes array 0 through download and runs dev_project.h's
+   * part functions in a host loop.
+   *   project_part_count:   doubles of the image of the WHOLE domain, < 0 for what pion_gpu_project_part refuses
+   *   project_part_to_host: `host` holds the image as the rank below left it (rank 0: zeros); copy it to the device,
+   *                         run this rank's part on array P, copy it back; complete on return */
+  long (*project_part_count)(void *handle, int axis, int nfields, const pion_gpu_proj_part *part);
+  int (*project_part_to_host)(void *handle, int axis, int nfields, const pion_gpu_proj_field *fields,
+                              const pion_gpu_proj_part *part, double *host);
 } pion_backend;
 
 /* the product's backend: libpion_gpu.so */

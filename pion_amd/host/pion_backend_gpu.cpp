@@ -201,6 +201,23 @@ int gpu_project_to_host(void *h, int axis, int nfields, const pion_gpu_proj_fiel
     return PION_GPU_EDEVICE;
   return hipStreamSynchronize(s) == hipSuccess ? 0 : PION_GPU_EDEVICE;
 }
+// a rank's part: the image travels host -> slot 0's device buffer -> (the part's kernel) -> host
+int gpu_project_part_to_host(void *h, int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part *part,
+                             double *host)
+{
+  const long n = pion_gpu_project_part_count(h, axis, nfields, part);
+  if (n < 0) return (int)n;
+  if (!host) return PION_GPU_EINVAL;
+  Staging *st;
+  if (int rc = staging_slot(h, 0, n, &st)) return rc;
+  hipStream_t s = compute_stream_of(h);
+  if (hipMemcpyAsync(st->dev[0], host, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
+    return PION_GPU_EDEVICE;
+  if (int rc = pion_gpu_project_part(h, 0, axis, nfields, fields, part, st->dev[0])) return rc;
+  if (hipMemcpyAsync(host, st->dev[0], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
+    return PION_GPU_EDEVICE;
+  return hipStreamSynchronize(s) == hipSuccess ? 0 : PION_GPU_EDEVICE;
+}
 void gpu_destroy(void *h)
 {
   Staging st;
@@ -249,6 +266,8 @@ const pion_backend k_gpu = {
     pion_gpu_unpack_fits_status,
     pion_gpu_project_count,
     gpu_project_to_host,
+    pion_gpu_project_part_count,
+    gpu_project_part_to_host,
 };
 
 }  // namespace

@@ -219,7 +219,8 @@ std::string sim_control_gpu::output_name(long step) const
 std::string sim_control_gpu::projection_name(long step) const
 {
   char b[64];
-  snprintf(b, sizeof b, "_proj_%04d.%08ld.fits", comm_ ? comm_->rank() : 0, step);
+  // the one file of a slab run (written by the last rank) carries rank 0000: the same name whatever the rank count
+  snprintf(b, sizeof b, "_proj_%04d.%08ld.fits", (comm_ && !projection_collective()) ? comm_->rank() : 0, step);
   return T.outfile + b;
 }
 

@@ -98,10 +98,13 @@ class sim_control_gpu {
   // and per field pion_proj_<n>_{a,var,coef,b}, and one double-precision IMAGE extension [NJ][NI] per field, EXTNAME =
   // the field's name, in units of code * dx.  Projected on the device (backend entries project_*), or -- a table
   // without them -- from a download by the same functions in a host loop.  EINVAL and a text: what pion_gpu_project
-  // refuses; a sim with a slab extent set (images of more than one rank are not assembled); a path that cannot be created
+  // refuses; a path that cannot be created; one rank of a slab run with only one of a slab extent and a communicator of
+  // more than one rank (or a communicator without send_to_above / recv_from_below).  With both the call is collective:
+  // the image of the whole domain is received from the rank below, gains this rank's part and is handed to the rank
+  // above; the last rank writes the one file, byte for byte the single-rank file of the global problem
   int write_projection(const char *path, int axis, int nfields, const pion_gpu_proj_field *fields);
   // from now on every regular output of output_data() is accompanied by <base>_proj_<rank, 4 digits>.<step, 8
-  // digits>.fits; nfields 0 turns it off again.  The same refusals, made here.  Cadence and time steps are untouched
+  // digits>.fits (the one file of a slab run: rank 0000); nfields 0 turns it off again.  The same refusals, made here.  Cadence and time steps are untouched
   int set_projection_output(int axis, int nfields, const pion_gpu_proj_field *fields);
   std::string projection_name(long step) const;
   // restart from the files that hold this sim's planes (written by any number of ranks); sets P, Ph, simtime,
@@ -148,6 +151,10 @@ class sim_control_gpu {
   int filetype_ = 0;             // PION_HOST_FILE_*
   int proj_axis_ = 0;            // set_projection_output: the images that accompany a regular output (none: empty)
   std::vector<pion_gpu_proj_field> proj_fields_;
+  bool projection_collective() const;   // one rank of a slab run whose images are assembled along the ranks
+  int project_images(int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part *part, long n, double *img);
+  int relay_part(int rc, int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part &part,
+                 std::vector<double> &img);
   int projection_refused(int axis, int nfields, const pion_gpu_proj_field *fields, const char *who);
   // snapshot_io.cpp: what both writers share
   int snapshot_params(std::vector<snapshot_param> &out, long &slab_n);

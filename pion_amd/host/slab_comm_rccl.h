@@ -52,6 +52,12 @@ class slab_comm_rccl : public slab_comm {
   int allreduce_min(double *t_dyn, double *t_mp) override;
   // new state uploaded (sim_control_gpu::Init): complete an exchange in flight, forget a pending request_min()
   int reset() override;
+  // the image relay (slab_comm.h): ncclSend / ncclRecv of a device buffer this object owns, on the communication
+  // stream (after attach()), first the two words {status, length}, then the data; the caller's memory is host memory,
+  // copied into / out of that buffer.  The stream is idle between steps, where write_projection calls these
+  bool has_relay() const override { return true; }
+  int recv_from_below(void *host, size_t bytes, int *status) override;
+  int send_to_above(const void *host, size_t bytes, int status) override;
 
   bool has_neighbours() const { return up_ >= 0 || down_ >= 0; }
   const std::string &last_error() const override { return err_; }
@@ -65,6 +71,9 @@ class slab_comm_rccl : public slab_comm {
   void *h_;         // pion_gpu handle
   int pending_;     // array of the exchange in flight, or -1
   bool requested_;  // request_min() issued, allreduce_min() not yet
+  void *relay_ = nullptr;      // device buffer of the image relay: 16 bytes of header, then the data
+  size_t relay_bytes_ = 0;
+  int relay_buffer(size_t bytes);
   std::string err_;
 };
 

@@ -59,6 +59,12 @@ slab_comm_shm::~slab_comm_shm()
 {
   if (seg_) munmap(seg_, seg_bytes_);
   if (rank_ == 0 && !name_.empty()) shm_unlink(name_.c_str());
+  // the image relay's channels: this rank's own [0] and the one of the rank above [1]
+  for (int k = 0; k < 2; k++)
+    if (img_seg_[k]) {
+      munmap(img_seg_[k], img_chan_bytes());
+      shm_unlink((name_ + "_img" + std::to_string(rank_ + k)).c_str());
+    }
   if (pinned_) {
     (void)hipHostFree(stage_lo_);
     (void)hipHostFree(stage_hi_);
@@ -234,6 +240,97 @@ int slab_comm_shm::reset()
 {
   requested_ = false;
   return finish();
+}
+
+// ---- the image relay.  Segment "<name>_img<r>": one Chan -- the channel rank r receives in, written by rank r - 1.
+// A message is a run of pieces; the first piece carries the status word and the message's length, and no data follows a
+// status != 0.  `written` and `consumed` count pieces: the writer fills the channel when consumed == written, the reader
+// empties it when written > consumed.  The counters of the halo mailboxes and of the reduction are not touched.
+namespace {
+constexpr size_t IMG_PIECE = 256 * 1024;
+}
+struct slab_comm_shm::Chan {
+  std::atomic<unsigned long long> written, consumed;
+  long long status, total;   // of the message this piece begins (first piece only)
+  char pad[64 - 2 * sizeof(std::atomic<unsigned long long>) - 2 * sizeof(long long)];
+  char data[IMG_PIECE];
+};
+size_t slab_comm_shm::img_chan_bytes() { return sizeof(Chan); }
+slab_comm_shm::Chan *slab_comm_shm::chan(int rank)
+{
+  char *&seg = img_seg_[rank - rank_];   // rank_: the channel this rank receives in; rank_ + 1: the one it sends in
+  if (!seg) {
+    const std::string n = name_ + "_img" + std::to_string(rank);
+    const int fd = shm_open(n.c_str(), O_CREAT | O_RDWR, 0600);   // (a fresh segment is zero-filled)
+    if (fd < 0 || ftruncate(fd, (off_t)sizeof(Chan)) != 0) {
+      err_ = "shm_open / ftruncate failed for " + n;
+      if (fd >= 0) close(fd);
+      return nullptr;
+    }
+    void *m = mmap(nullptr, sizeof(Chan), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+    close(fd);
+    if (m == MAP_FAILED) {
+      err_ = "mmap failed for " + n;
+      return nullptr;
+    }
+    seg = static_cast<char *>(m);
+  }
+  return reinterpret_cast<Chan *>(seg);
+}
+
+int slab_comm_shm::send_to_above(const void *host, size_t bytes, int status)
+{
+  if (rank_ >= world_ - 1) return 0;
+  if (!host && status == 0) {
+    err_ = "send_to_above: no buffer";
+    return PION_GPU_EINVAL;
+  }
+  Chan *c = chan(rank_ + 1);
+  if (!c) return PION_GPU_EDEVICE;
+  const char *src = static_cast<const char *>(host);
+  size_t done = 0;
+  bool first = true;
+  while (first || done < bytes) {
+    if (int rc = wait_until(&c->consumed, img_sent_, "the rank above to take the previous piece of the image")) return rc;
+    const size_t n = status ? 0 : ((bytes - done < IMG_PIECE) ? bytes - done : IMG_PIECE);
+    if (first) c->status = status, c->total = status ? 0 : (long long)bytes;
+    if (n) memcpy(c->data, src + done, n);
+    c->written.store(++img_sent_, std::memory_order_release);
+    done += n;
+    first = false;
+    if (status) break;
+  }
+  // the receiver has the whole message (and has mapped the segment) when this returns
+  return wait_until(&c->consumed, img_sent_, "the rank above to take the image");
+}
+
+int slab_comm_shm::recv_from_below(void *host, size_t bytes, int *status)
+{
+  if (status) *status = 0;
+  if (rank_ == 0) return 0;
+  Chan *c = chan(rank_);
+  if (!c) return PION_GPU_EDEVICE;
+  char *dst = static_cast<char *>(host);
+  size_t done = 0, total = 0;
+  bool first = true, fits = true;
+  while (first || done < total) {
+    if (int rc = wait_until(&c->written, img_taken_ + 1, "the image of the rank below")) return rc;
+    if (first) {
+      if (status) *status = (int)c->status;
+      total = (size_t)c->total;
+      fits = (c->status != 0) || (host && total == bytes);
+    }
+    const size_t n = (total - done < IMG_PIECE) ? total - done : IMG_PIECE;
+    if (fits && n) memcpy(dst + done, c->data, n);
+    c->consumed.store(++img_taken_, std::memory_order_release);
+    done += n;
+    first = false;
+  }
+  if (!fits) {
+    err_ = "recv_from_below: the message of the rank below has " + std::to_string(total) + " bytes, expected " + std::to_string(bytes);
+    return PION_GPU_EINVAL;
+  }
+  return 0;
 }
 
 }  // namespace pion_host

@@ -31,6 +31,14 @@ class slab_comm_shm : public slab_comm {
   int request_min() override;
   int allreduce_min(double *t_dyn, double *t_mp) override;
   int reset() override;
+  // the image relay (slab_comm.h): through segments of its own ("<name>_img<r>": the channel rank r receives in, used
+  // by the ranks r - 1 and r only, a message in pieces of at most IMG_PIECE bytes), so that neither a halo exchange in
+  // flight nor a pending request_min is disturbed; it needs no attach().  Either rank of a channel creates its segment
+  // and both unlink it when they are destroyed: a send or a receive returns only when the peer has mapped it, and a
+  // rank whose peer never came (a timeout) leaves nothing behind
+  bool has_relay() const override { return true; }
+  int recv_from_below(void *host, size_t bytes, int *status) override;
+  int send_to_above(const void *host, size_t bytes, int status) override;
   const std::string &last_error() const override { return err_; }
   int rank() const override { return rank_; }
   int world() const override { return world_; }
@@ -39,6 +47,9 @@ class slab_comm_shm : public slab_comm {
   struct Box;   // one mailbox (header + planes) inside the segment
   Box *box(int rank, int side) const;
   int wait_until(const volatile void *counter, unsigned long long want, const char *what);
+  struct Chan;  // one channel of the image relay
+  Chan *chan(int rank);
+  static size_t img_chan_bytes();
 
   int rank_, world_, up_, down_;
   std::string name_;
@@ -47,6 +58,8 @@ class slab_comm_shm : public slab_comm {
   long count_;                 // doubles per face
   size_t box_bytes_, seg_bytes_;
   char *seg_;                  // the mapped segment
+  char *img_seg_[2] = {nullptr, nullptr};   // the image relay's channels, mapped at the first receive [0] / send [1]
+  unsigned long long img_sent_ = 0, img_taken_ = 0;   // pieces this rank has written upwards / taken from below
   double *stage_lo_, *stage_hi_;   // pinned staging: my bottom / top on-grid planes (out), then the ghosts (in)
   bool pinned_;
   int pending_;                // array of the exchange in flight, or -1

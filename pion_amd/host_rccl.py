@@ -107,6 +107,11 @@ def load_host_library():
     if hasattr(h, "pion_host_sim_write_projection"):   # (likewise)
         h.pion_host_sim_write_projection.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
         h.pion_host_sim_set_projection_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(h, "pion_host_project_part_on_host"):   # (likewise)
+        h.pion_host_project_part_refused.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        h.pion_host_project_part_refused.restype = C.c_char_p
+        h.pion_host_project_on_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, _dp, _dp]
+        h.pion_host_project_part_on_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp, _dp]
     h.pion_host_comm_unique_id.argtypes = [C.c_void_p]
     h.pion_host_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     h.pion_host_comm_destroy.argtypes = [C.c_void_p]

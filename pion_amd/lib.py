@@ -101,6 +101,10 @@ def load_library():
         lib.pion_gpu_project_count.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.pion_gpu_project_count.restype = C.c_long
         lib.pion_gpu_project.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pion_gpu_project_part"):   # (likewise)
+        lib.pion_gpu_project_part_count.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        lib.pion_gpu_project_part_count.restype = C.c_long
+        lib.pion_gpu_project_part.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pion_gpu_interface_flux.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
     if hasattr(lib, "pion_gpu_cell_advance"):   # (likewise)
         lib.pion_gpu_cell_advance.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp]
@@ -133,6 +137,7 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_fits_images", "pion_gpu_fits_count", "pion_gpu_pack_fits",
     "pion_gpu_fits_prim_count", "pion_gpu_unpack_fits", "pion_gpu_unpack_fits_status",
     "pion_gpu_cell_advance", "pion_gpu_project_count", "pion_gpu_project",
+    "pion_gpu_project_part_count", "pion_gpu_project_part",
 ]
 
 
@@ -446,6 +451,39 @@ class GpuSim:
         import torch
         buf = torch.empty((max(n, 1),), dtype=torch.float64, device="cuda:%d" % torch.cuda.current_device())
         self._chk(self.lib.pion_gpu_project(self.h, int(which), int(axis), nf, arr, C.c_void_p(buf.data_ptr())), "project")
+        self.synchronize()
+        return buf.cpu().numpy().reshape(nf, -1, self.project_shape(axis)[1])
+
+    def project_part_count(self, axis, nfields, part):
+        """pion_gpu_project_part_count: doubles of the image of the WHOLE domain a project_part() call works in; part:
+        an abi.ProjPart or (plane_lo, global_planes, last, global_xmin).  Raises for what the call refuses"""
+        n = self.lib.pion_gpu_project_part_count(self.h, int(axis), int(nfields), C.byref(abi.proj_part(part)))
+        if n < 0:
+            raise PionGpuError("project_part_count", n, self._err())
+        return n
+
+    def project_part(self, axis, fields, part, which=0, dimg_ptr=None, image=None):
+        """pion_gpu_project_part: this handle's part of a slab run's image (the planes [plane_lo, plane_lo + n) of the
+        slab axis out of global_planes), added into the image of the whole domain that the rank below left.  With
+        dimg_ptr the image is that device buffer, in/out, enqueued on the compute stream.  Without it `image` is the
+        image so far as an ndarray [nfields][NJ_global][NI_global] (None: zeros, rank 0) and the new one is returned.
+        After the part with last = 1 the image is == project() on one handle of the whole domain."""
+        arr = fields if isinstance(fields, C.Array) else abi.proj_fields(fields)
+        nf = len(fields)
+        p = abi.proj_part(part)
+        if dimg_ptr is not None:
+            self._chk(self.lib.pion_gpu_project_part(self.h, int(which), int(axis), nf, arr, C.byref(p),
+                                                     C.c_void_p(dimg_ptr)), "project_part")
+            return None
+        n = self.project_part_count(axis, max(1, min(nf, abi.PROJ_MAX_FIELDS)), p)
+        import torch
+        dev = "cuda:%d" % torch.cuda.current_device()
+        if image is None:
+            buf = torch.zeros((n,), dtype=torch.float64, device=dev)
+        else:
+            buf = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float64).reshape(-1)).to(dev)
+        self._chk(self.lib.pion_gpu_project_part(self.h, int(which), int(axis), nf, arr, C.byref(p),
+                                                 C.c_void_p(buf.data_ptr())), "project_part")
         self.synchronize()
         return buf.cpu().numpy().reshape(nf, -1, self.project_shape(axis)[1])
 
