@@ -52,6 +52,13 @@ PDEV double ldu_once(const char *ubase, const unsigned off)
   return *(gp)((gc)uni(ubase) + off);
 #endif
 }
+// A loaded value that is dropped on this path: "used" here (no instruction), so that the wait for it stands on this
+// path.  A request left outstanding into a join makes every later write to its destination register wait for it, on
+// the other path as well, behind whatever that path has requested since.
+PDEV void drop_loaded(const double x)
+{
+  asm volatile("" : : "v"(x));
+}
 // sweep-frame state of the cell at uniform byte shift `sh` from the lane's cell
 template <int NV, bool MHD>
 PDEV void load_rot2(const char *Sb, const long ncb, const int ax, const long sh, const unsigned off, double *q)
@@ -437,8 +444,12 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
       // needs P0, a load would be waited for with nothing to overlap it.
       // PION_ROWS2_U0 = 2: the loads go out in the x task, AFTER the loads the x task itself waits for (loads return
       // in issue order), straight into dU's registers, and are converted in place after the x solve: a read of HBM
-      // that nothing waits for.
-      const bool u0 = PLAIN && !same_pc && !prime && a.plain_cells;
+      // that nothing waits for.  They go out in EVERY x task of the plain second-order instances (U0X), whether u0 holds
+      // or not (a.Pc is an array of the grid in every launch; without u0 the values are dropped and dU is zeroed behind
+      // the solve): under the run-time condition the compiler counts the loads outstanding at the join as on the path
+      // without them, and the waits for the x neighbours, nine too strict, became waits for these loads as well.
+      constexpr bool U0X = (PION_ROWS2_U0 == 2) && PLAIN && OAMODE == 2;
+      const bool u0 = ((PION_ROWS2_U0 == 2) ? U0X : PLAIN) && !same_pc && !prime && a.plain_cells;
 #if PION_ROWS2_U0 == 1
       if (u0) {
         const unsigned o = pin_v(off_r);
@@ -452,6 +463,7 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
 #endif
 #else
       const bool u0 = false;
+      constexpr bool U0X = false;
 #endif
       if (!PLAIN && !prime && a.dE) {
         // calc_noRT_microphysics_dU (time_integrator.cpp:438-489): only the energy changes; k_cooling
@@ -505,7 +517,7 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
               qp[v] = ldu(St + v * ncb + 8, off);
             }
 #if defined(PION_FAST_MATH) && PION_ROWS2_U0 == 2
-            if (u0) {
+            if constexpr (U0X) {
               // the start-of-step state, into dU's registers (converted after the solve)
               const char *const Pcb0 = reinterpret_cast<const char *>(a.Pc) + zt;
 #pragma unroll
@@ -554,29 +566,45 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
           st = sy;
           cl = lower ? c - sy : c;
           const long shc = lower ? -sy : 0, shb = lower ? -syb : 0;   // shift of cell A from the lane's cell (uniform)
-          if constexpr (MHD && SOLVER == FLUX_RS_HLLD) {
-            if (PF && pf_valid) hfl = pfh;
-            else {
-              hfl = ldub(Ht + shc, offb);
-              hfr = ldub(Ht + shc + sy, offb);
+          // ONE batch: every load of the task is requested before the first use of any of them -- the rows F and C, in
+          // lower mode M, the lower neighbour's B_n / psi, the two flags -- so that the task pays the way to memory once.
+          // (Requested where they are used -- C and M behind the arrangement of F into A / B -- they were a second,
+          // dependent round trip: the compiler moves no load up across the uniform branches on `lower`.)  The loads under
+          // a uniform condition go FIRST: at the join the compiler counts the loads outstanding as on the path with
+          // fewer of them, which is exact for everything requested behind the join.
+          double own[NV], F[NV], A[NV], B[NV], C[NV], M[NV];
+          const bool fetch = !(PF && pf_valid);
+          // (CYL: M stays behind the arrangement, a second trip to memory once per row group.  The cylindrical MHD
+          // instances are the ones that spill -- 96 bytes of scratch per lane in the plain second-order GLM instance --
+          // and with M in the batch they spill more, 124; with C alone in the batch 92.)
+          constexpr bool YBM = !CYL;
+          if (YBM && oa2 && lower) {
+            // the row below A, for A's slope (an upper face finds its row's slope carried in ysn)
+            load_rot2<NV, MHD>(St, ncb, 1, -2 * syb, pin_v(off_r), M);
+          }
+          if constexpr (MHD) {
+            if (fetch && !lower) {
+              const unsigned o = pin_v(off_r);
+              bnm = ldu(St + (long)rotvar<MHD>(1, qBN) * ncb - syb, o);
+              if constexpr (EQ == EQGLM) sim = ldu(St + (long)qSI * ncb - syb, o);
             }
           }
-          double own[NV], F[NV], A[NV], B[NV];
-          if (PF && pf_valid) {
+          if (!fetch) {
+            if constexpr (MHD && SOLVER == FLUX_RS_HLLD) hfl = pfh;
 #pragma unroll
             for (int v = 0; v < NV; v++) F[v] = pf[v];
             bnm = pfb;
             sim = pfs;
           }
           else {
-            load_rot2<NV, MHD>(St, ncb, 1, lower ? -syb : syb, off, F);
-            if constexpr (MHD) {
-              if (!lower) {
-                bnm = ldu(St + (long)rotvar<MHD>(1, qBN) * ncb - syb, off);
-                if constexpr (EQ == EQGLM) sim = ldu(St + (long)qSI * ncb - syb, off);
-              }
+            const unsigned o = pin_v(off_r), ob = pin_v(offb_r);
+            if constexpr (MHD && SOLVER == FLUX_RS_HLLD) {
+              hfl = ldub(Ht + shc, ob);
+              hfr = ldub(Ht + shc + sy, ob);
             }
+            load_rot2<NV, MHD>(St, ncb, 1, lower ? -syb : syb, o, F);
           }
+          if (oa2) load_rot2<NV, MHD>(St, ncb, 1, shb + 2 * syb, pin_v(off_r), C);   // the row above B, for B's slope
           to_sweep<NV, MHD>(1, q0, own);
           if (lower) {
 #pragma unroll
@@ -598,11 +626,9 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
               const int jA = jy_r - (lower ? 1 : 0);
               const double RA = cyl_R(a.g, jA), RB = cyl_R(a.g, jA + 1);
               const double cA = lower ? cy_m1 : cy_0, cB = lower ? cy_0 : cy_p1, cC = lower ? cy_p1 : cy_p2;
-              double C[NV], sB[NV];
-              load_rot2<NV, MHD>(St, ncb, 1, shb + 2 * syb, off, C);
+              double sB[NV];
               if (lower) {
-                double M[NV];
-                load_rot2<NV, MHD>(St, ncb, 1, -2 * syb, off, M);
+                if (!YBM) load_rot2<NV, MHD>(St, ncb, 1, -2 * syb, off, M);
                 cyl_slope3<NV>(M, A, B, cyl_Rcom(cyl_R(a.g, jA - 1), dx), cA, cB, true, ysn);
               }
               else {
@@ -628,12 +654,9 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
             }
           }
           else if (oa2) {
-            double C[NV], sB[NV];
-            load_rot2<NV, MHD>(St, ncb, 1, shb + 2 * syb, off, C);
+            double sB[NV];
             if (lower) {
-              // the slope of row j-1 (an upper face finds its row's slope carried in ysn)
-              double M[NV];
-              load_rot2<NV, MHD>(St, ncb, 1, -2 * syb, off, M);
+              // the slope of row j-1
               hslope3<NV>(M, A, B, dx, thr, ysn);
             }
             hslope3<NV>(A, B, C, dx, thr, sB);
@@ -800,6 +823,14 @@ __global__ __launch_bounds__(256, PION_ROWS2_MINWG(EQ)) void k_stage_rows2(const
 #pragma unroll
             for (int v = 0; v < NV; v++) P0[v] = dU[v];
             E::PtoU(P0, dU, g);
+          }
+          else if constexpr (U0X) {
+            // (not used: an internal-boundary grid, or stencil and start-of-step array are one)
+#pragma unroll
+            for (int v = 0; v < NV; v++) {
+              drop_loaded(dU[v]);
+              dU[v] = 0.0;
+            }
           }
 #endif
           apply_axis<EQ, NV>(dU, q0, bnm, sim, bnp, sip, Fm, f, dt, dx);

@@ -9,7 +9,7 @@ HERE=$(cd "$(dirname "$0")/../.." && pwd)
 SRC=${SRC:-$HERE/pion_amd/csrc}
 OUT=$HERE/ab/$NAME
 mkdir -p $OUT/src
-cp $SRC/*.h $SRC/*.hip $SRC/Makefile $OUT/src/
+cp $SRC/*.h $SRC/*.hip $SRC/*.cpp $SRC/Makefile $OUT/src/
 mkdir -p $OUT/include && cp $HERE/include/pion_gpu.h $OUT/include/
 # the Makefile refers to ../../include/pion_gpu.h
 mkdir -p $OUT/src/../../include 2>/dev/null || true

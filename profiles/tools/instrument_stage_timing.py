@@ -46,8 +46,10 @@ rep("""              qp[v] = ldu(St + v * ncb + 8, off);
             }
             tsB = stamp(true);
 """)
-rep("            hslope3<NV>(A, B, C, dx, thr, sB);", "            tsB = stamp(true);\n            hslope3<NV>(A, B, C, dx, thr, sB);")
-rep("              cyl_slope3<NV>(A, B, C, cA, cB, cC, true, sB);", "              tsB = stamp(true);\n              cyl_slope3<NV>(A, B, C, cA, cB, cC, true, sB);")
+# (the y task: behind its one batch, whose last request is row C's)
+rep("          if (oa2) load_rot2<NV, MHD>(St, ncb, 1, shb + 2 * syb, pin_v(off_r), C);   // the row above B, for B's slope\n",
+    "          if (oa2) load_rot2<NV, MHD>(St, ncb, 1, shb + 2 * syb, pin_v(off_r), C);   // the row above B, for B's slope\n"
+    "          if (oa2) tsB = stamp(true);\n")
 rep("            hslope3<NV>(zq0, qp1, qp2, dx, thr, sn);", "            tsB = stamp(true);\n            hslope3<NV>(zq0, qp1, qp2, dx, thr, sn);")
 rep("""          for (int v = 0; v < NV; v++) ZS2(r, NZ - NV + v) = f[v];
         }
@@ -65,16 +67,17 @@ rep("""            tmp = (t < tmp) ? t : tmp;
         }
       }
     }
-  }
-#undef ZS2
+    if constexpr (SCR) {
 """, """            tmp = (t < tmp) ? t : tmp;
           }
         }
       }
       tup += stamp(true) - sU;
     }
-  }
-#undef ZS2
+    if constexpr (SCR) {
+""")
+rep("""#undef ZS2
+""", """#undef ZS2
   {
     const unsigned long long te = stamp(false);
     if (lane == 0) {
