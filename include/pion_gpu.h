@@ -249,6 +249,58 @@ typedef struct pion_gpu_proj_part {
 long pion_gpu_project_part_count(void *handle, int axis, int nfields, const pion_gpu_proj_part *part);
 int pion_gpu_project_part(void *handle, int which, int axis, int nfields, const pion_gpu_proj_field *fields,
                           const pion_gpu_proj_part *part, void *dimg);
+/* Ray-traced column densities (pion_amd/csrc/dev_raytrace.h states the rules): the reference's short-characteristics
+ * tracer raytracer_USC (raytracing/raytracer_SC.cpp), which leaves per cell and source the column density TO the cell and
+ * the column THROUGH it in extra_data.  Here, per source, two arrays of the ON-GRID cells only, [nz][ny][nx] doubles:
+ *   col   what CI.get_col returns after a trace: column to the cell + column through it (the reference's Col_Src_<id>_T0)
+ *   dcol  the column through the cell, ds rho, ds rho (1 - y) or ds rho y with y = tracer opacity_var (ProcessCell, :855-1057)
+ * 2-D Cartesian, 2-D cylindrical (z,R) (the reference runs the same cell_cols_2d there) and 3-D Cartesian grids; a
+ * finite source anywhere, on or off the grid, or a source at infinity beyond one of the 2 ndim faces.  Both
+ * floating-point builds give the same bits.  Tracing only reads the state: a step after it is the step without it.
+ *   pion_gpu_add_rt_source  Add_Source / add_source_to_list (:1183-1314): moves a finite source to the nearest cell
+ *                           vertex per axis (centre_source_on_cell, :1934-1996) and reports the position used
+ *                           (pos_used, PION_MAX_DIM doubles, may be NULL); *id = 0, 1, ...  Allocates the source's two
+ *                           arrays.  PION_RT_KERNEL=levels in the environment at the handle's first source selects the
+ *                           launch-per-level kernel for finite sources (a cross-check; default: tiles).
+ *   pion_gpu_raytrace       RT_all_sources (sim_control/sim_init.cpp:806-829): every source in id order, from array
+ *                           `which` (0 = P, 1 = Ph; what pion_gpu_download(which) reads); enqueued on the compute
+ *                           stream, returns at once.  A handle without sources launches nothing.
+ *   pion_gpu_rt_columns     CI.get_col / get_cell_col: `what` = 0 col, 1 dcol of source id into a host array of
+ *                           pion_gpu_rt_count(handle, all planes) doubles; synchronises.
+ *   pion_gpu_rt_count       doubles of `planes` planes of the slab axis (x-y planes in 3-D, rows in 2-D) of one array
+ *   pion_gpu_pack_columns   the planes [plane_lo, plane_hi) of that array as big-endian doubles in the DEVICE buffer
+ *                           dbuf, as pion_gpu_pack_fits packs an image; enqueued, returns at once.
+ *   pion_gpu_rt_plan        host only, no device: the tile of the tiled kernel (cells per axis, counted from the source
+ *                           vertex outwards), its launches (tile-levels that hold tiles) and the launches of the
+ *                           per-level kernel (levels that hold cells) for `src` on the grid of cfg.  A source at
+ *                           infinity: tile 0, one launch.
+ *   pion_gpu_raytrace_host  host only: the rules of dev_raytrace.h in a host loop over P_soa (the layout of
+ *                           pion_gpu_upload, ghosts included; only on-grid cells are read) into col and dcol.
+ *   pion_gpu_rt_refused     host only: the text with which the calls above refuse (cfg, src), or NULL.
+ * EINVAL and a text: 1-D and spherical grids; a handle with a PION_BC_SLAB face; an opacity rule other than
+ * PION_RT_OPACITY_TOTAL, MINUS, TRACER (VSHELL, HALPHA, RR, HHE and MP need a microphysics object); opacity_var outside
+ * the tracers (MINUS, TRACER); more than PION_MAX_RT_SOURCES sources; a direction that is not a face of the grid; a
+ * position that is not finite; an unknown id, `what` or plane range; a NULL pointer. */
+#define PION_MAX_RT_SOURCES 4
+#define PION_RT_OPACITY_TOTAL 1   /* constants of raytracing/rad_src_info / constants.h: RT_OPACITY_* */
+#define PION_RT_OPACITY_MINUS 2
+#define PION_RT_OPACITY_TRACER 3
+typedef struct pion_gpu_rt_source {
+  double pos[PION_MAX_DIM]; /* finite source: position, physical units */
+  int at_infinity;          /* 1: parallel rays */
+  int dir;                  /* at infinity: the face the source lies beyond, 0..5 = XN XP YN YP ZN ZP */
+  int opacity;              /* PION_RT_OPACITY_* */
+  int opacity_var;          /* tracer index (0 = first tracer) for MINUS and TRACER */
+} pion_gpu_rt_source;
+int pion_gpu_add_rt_source(void *handle, const pion_gpu_rt_source *src, int *id, double *pos_used);
+int pion_gpu_raytrace(void *handle, int which);
+int pion_gpu_rt_columns(void *handle, int id, int what, double *host);
+long pion_gpu_rt_count(void *handle, int planes);
+int pion_gpu_pack_columns(void *handle, int id, int what, int plane_lo, int plane_hi, void *dbuf);
+int pion_gpu_rt_plan(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, int tile[3], long *launches, long *levels);
+int pion_gpu_raytrace_host(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const double *P_soa, double *col,
+                           double *dcol);
+const char *pion_gpu_rt_refused(const pion_gpu_config *cfg, const pion_gpu_rt_source *src);
 /* adopt caller-owned device buffers (e.g. torch tensors) instead of internal ones;
  * both must hold nvar*ncell_all doubles */
 int pion_gpu_bind_device_state(void *handle, void *dP, void *dPh);

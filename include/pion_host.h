@@ -121,6 +121,28 @@ int pion_host_sim_set_output_filetype(void *sim, int type);
  *   above it returns EINVAL, no file appears, no rank blocks. */
 int pion_host_sim_write_projection(void *sim, const char *path, int axis, int nfields, const pion_gpu_proj_field *fields);
 int pion_host_sim_set_projection_output(void *sim, int axis, int nfields, const pion_gpu_proj_field *fields);
+/* Ray-traced column densities (pion_gpu_raytrace; the rules: pion_amd/csrc/dev_raytrace.h, after the reference's
+ * short-characteristics tracer raytracing/raytracer_SC.cpp).
+ * pion_host_sim_add_rt_source: Add_Source (:1183-1314) for one radiation source, pion_gpu_add_rt_source on the loop's
+ *   handle; pos_used (PION_MAX_DIM doubles, may be NULL): the cell vertex a finite source was moved to.  A backend table
+ *   without the entry keeps the source in the sim.
+ * pion_host_sim_write_columns: a FITS file with the primary header of pion_host_sim_write_fits plus RT_Nsources and, per
+ *   source n, RT_position_<n>_<d> (d = 0, 1, 2; a source at infinity: -/+1e200 on its axis), RT_at_infty_<n>,
+ *   RT_Opacity__<n>, RT_Tau_var__<n> -- the reference's names (dataIO/dataio_base.cpp:1267-1282) --; then per source two
+ *   double-precision IMAGE extensions of the on-grid cells, EXTNAME Col_Src_<n>_T0 (the column to + through the cell,
+ *   what the reference writes under that name) and DCol_Src_<n>_T0 (the column through it), big-endian.  The columns
+ *   are traced from P as it stands, after the boundary update, on the device, and streamed a chunk of planes at a time;
+ *   a backend table without the entries downloads the state and runs pion_gpu_raytrace_host.  Written under a ".part"
+ *   name and renamed; pion_amd/fits.py reads it.
+ * pion_host_sim_set_column_output: from now on (on != 0) every regular output of pion_host_sim_time_int is accompanied
+ *   by <base>_cols_<rank, 4 digits>.<step, 8 digits>.fits; on = 0 turns that off.  Cadence, the time-step clip,
+ *   checkpoints, every dt and the regular outputs themselves are untouched: tracing only reads the state.
+ * EINVAL and a text, never an exit: everything pion_gpu_add_rt_source refuses; no source; a path that cannot be created;
+ * a sim that is one rank of several (a slab extent or a communicator of more than one rank): the columns of a slab run
+ * would have to be handed from rank to rank. */
+int pion_host_sim_add_rt_source(void *sim, const pion_gpu_rt_source *src, int *id, double *pos_used);
+int pion_host_sim_write_columns(void *sim, const char *path);
+int pion_host_sim_set_column_output(void *sim, int on);
 /* The rules of the images as host functions (pion_amd/csrc/dev_project.h), without a sim or a device: cfg describes the
  * grid, A is a whole array [nvar][ncell_all] with its ghost cells.  What a backend table without projection entries gets.
  *   pion_host_project_on_host:      every pixel by proj_column / abel_column, img = [nfields][NJ][NI]

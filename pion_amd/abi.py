@@ -71,6 +71,30 @@ def proj_fields(fields):
     return arr
 
 
+# radiation sources (pion_gpu_add_rt_source): the opacity rules covered, and the sources a handle takes
+RT_OPACITY_TOTAL, RT_OPACITY_MINUS, RT_OPACITY_TRACER = 1, 2, 3
+MAX_RT_SOURCES = 4
+
+
+class RtSource(C.Structure):
+    """pion_gpu_rt_source (include/pion_gpu.h)"""
+    _fields_ = [("pos", C.c_double * 3), ("at_infinity", C.c_int), ("dir", C.c_int), ("opacity", C.c_int),
+                ("opacity_var", C.c_int)]
+
+
+def rt_source(src=None, pos=(0.0, 0.0, 0.0), at_infinity=0, dir=0, opacity=RT_OPACITY_TOTAL, opacity_var=0):
+    """an abi.RtSource from one, from a dict of its fields, or from keywords"""
+    if isinstance(src, RtSource):
+        return src
+    if isinstance(src, dict):
+        return rt_source(None, **src)
+    s = RtSource()
+    pos = list(pos) + [0.0] * (3 - len(pos))
+    s.pos[0], s.pos[1], s.pos[2] = float(pos[0]), float(pos[1]), float(pos[2])
+    s.at_infinity, s.dir, s.opacity, s.opacity_var = int(at_infinity), int(dir), int(opacity), int(opacity_var)
+    return s
+
+
 class PionGpuConfig(C.Structure):
     _fields_ = [
         ("ndim", C.c_int), ("nvar", C.c_int), ("ntracer", C.c_int), ("eqntype", C.c_int),

@@ -429,6 +429,7 @@ void pion_gpu_destroy(void *handle)
   hipFree(h->ddt);
   hipFree(h->ddt_init);
   wind_free(h);
+  rt_free(h);
   hipFree(h->djet_idx);
   hipFree(h->djet_state);
   hipFree(h->dcoolT);

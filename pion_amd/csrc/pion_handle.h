@@ -1,7 +1,7 @@
 // pion_handle.h -- shared by the translation units of the C-ABI layer: the handle behind include/pion_gpu.h's opaque
 // pointer and the helpers every entry point uses (defined in pion_gpu.hip, used there, in pion_step.hip, in
-// pion_bc.hip, in pion_wind.hip and in pion_output.hip).  The kernels behind kernels.h's launchers are in
-// kernels_fp.hip, kernels_prepass.hip and kernels_dt.hip.
+// pion_bc.hip, in pion_wind.hip, in pion_output.hip, in pion_project.hip and in pion_raytrace.hip).  The kernels
+// behind kernels.h's launchers are in kernels_fp.hip, kernels_prepass.hip and kernels_dt.hip.
 #ifndef PION_HANDLE_H
 #define PION_HANDLE_H
 
@@ -107,6 +107,9 @@ struct Handle {
   // FITS read (pion_output.hip): rejected elements counted by k_unpack_fits since the last pion_gpu_unpack_fits_status;
   // allocated at the first unpack
   unsigned long long *dfits_bad = nullptr;
+  // radiation sources (pion_raytrace.hip): the sources and their column arrays, created by the first
+  // pion_gpu_add_rt_source; null: the handle traces nothing
+  struct RtState *rt = nullptr;
 };
 
 // the state arrays, the cell flags or the tables were written from outside the stages: what the last stage left
@@ -196,6 +199,8 @@ struct DevBuf {
 int wind_angle_check(Handle *h, double simtime);
 int wind_sources_update(Handle *h, double simtime);
 void wind_free(Handle *h);
+// The radiation sources (pion_raytrace.hip) as pion_gpu_destroy needs them: their memory freed
+void rt_free(Handle *h);
 
 // The boundary part of pion_gpu_create (pion_bc.hip): no face holds a state yet, the columns of the DMR2 boundary
 void bc_init(Handle *h);

@@ -38,6 +38,12 @@
 // -1e99, which fail the restart.  A backend without that entry takes the same dev_output.h functions in a host loop
 // (fits_convert_run) and goes through upload.
 //
+// Ray-traced column densities (sim_control_gpu::write_columns, defined in fits_io.cpp; the rules:
+// pion_amd/csrc/dev_raytrace.h) use the same writer too: the same primary header with RT_Nsources and, per source n,
+// RT_position_<n>_<d>, RT_at_infty_<n>, RT_Opacity__<n>, RT_Tau_var__<n> appended, then per source the images
+// Col_Src_<n>_T0 and DCol_Src_<n>_T0 of the on-grid cells, traced on the device and streamed image after image, a chunk
+// of planes at a time (backend entries raytrace / rt_count / columns_to_host_begin), or by pion_gpu_raytrace_host on a
+// downloaded array where the table has no such entries.
 // Projected images (sim_control_gpu::write_projection, defined in fits_io.cpp; the rules: pion_amd/csrc/dev_project.h)
 // use the same writer: the same primary header with pion_proj_axis and pion_proj_<n>_{a,var,coef,b} appended, then one
 // two-dimensional IMAGE extension per field (NAXIS1 = NI, NAXIS2 = NJ, EXTNAME = the field's name).  The images come

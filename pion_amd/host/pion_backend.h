@@ -98,6 +98,20 @@ typedef struct pion_backend {
   long (*project_part_count)(void *handle, int axis, int nfields, const pion_gpu_proj_part *part);
   int (*project_part_to_host)(void *handle, int axis, int nfields, const pion_gpu_proj_field *fields,
                               const pion_gpu_proj_part *part, double *host);
+  /* Ray-traced column densities (fits_io.h; the rules: pion_amd/csrc/dev_raytrace.h).  These four entries are read ONLY
+   * inside sim_control_gpu::add_rt_source and write_columns: a caller that never adds a radiation source may hand the
+   * loop a table that ends before them.  All NULL: the sim keeps the sources itself, and the writer takes array 0
+   * through download and runs pion_gpu_raytrace_host on it.
+   *   add_rt_source:         pion_gpu_add_rt_source
+   *   raytrace:              pion_gpu_raytrace: trace every source from array `which`; enqueued
+   *   rt_count:              doubles of `planes` planes of one column array
+   *   columns_to_host_begin: start packing (big-endian, pion_gpu_pack_columns) and copying the planes of array `what`
+   *                          (0 col, 1 dcol) of source `id` into staging slot `slot`; returns at once.  Arrival is
+   *                          ongrid_to_host_end's */
+  int (*add_rt_source)(void *handle, const pion_gpu_rt_source *src, int *id, double *pos_used);
+  int (*raytrace)(void *handle, int which);
+  long (*rt_count)(void *handle, int planes);
+  int (*columns_to_host_begin)(void *handle, int id, int what, int plane_lo, int plane_hi, int slot);
 } pion_backend;
 
 /* the product's backend: libpion_gpu.so */

@@ -218,6 +218,20 @@ int gpu_project_part_to_host(void *h, int axis, int nfields, const pion_gpu_proj
     return PION_GPU_EDEVICE;
   return hipStreamSynchronize(s) == hipSuccess ? 0 : PION_GPU_EDEVICE;
 }
+// a plane range of one column array: packed big-endian into the slot's device buffer, then copied
+int gpu_columns_to_host_begin(void *h, int id, int what, int plane_lo, int plane_hi, int slot)
+{
+  const long n = pion_gpu_rt_count(h, plane_hi - plane_lo);
+  Staging *st;
+  if (int rc = staging_slot(h, slot, n, &st)) return rc;
+  if (int rc = pion_gpu_pack_columns(h, id, what, plane_lo, plane_hi, st->dev[slot])) return rc;
+  hipStream_t s = compute_stream_of(h);
+  if (hipMemcpyAsync(st->host[slot], st->dev[slot], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
+    return PION_GPU_EDEVICE;
+  if (hipEventRecord(st->ev[slot], s) != hipSuccess) return PION_GPU_EDEVICE;
+  st->busy[slot] = true;
+  return 0;
+}
 void gpu_destroy(void *h)
 {
   Staging st;
@@ -268,6 +282,10 @@ const pion_backend k_gpu = {
     gpu_project_to_host,
     pion_gpu_project_part_count,
     gpu_project_part_to_host,
+    pion_gpu_add_rt_source,
+    pion_gpu_raytrace,
+    pion_gpu_rt_count,
+    gpu_columns_to_host_begin,
 };
 
 }  // namespace

@@ -224,6 +224,13 @@ std::string sim_control_gpu::projection_name(long step) const
   return T.outfile + b;
 }
 
+std::string sim_control_gpu::columns_name(long step) const
+{
+  char b[64];
+  snprintf(b, sizeof b, "_cols_%04d.%08ld.fits", comm_ ? comm_->rank() : 0, step);
+  return T.outfile + b;
+}
+
 int sim_control_gpu::write_output(const char *path)
 {
   return (filetype_ == PION_HOST_FILE_FITS) ? write_fits(path) : write_snapshot(path);
@@ -261,6 +268,8 @@ int sim_control_gpu::output_data()
   if (!proj_fields_.empty())
     if (int rc = write_projection(projection_name(T.timestep).c_str(), proj_axis_, (int)proj_fields_.size(), proj_fields_.data()))
       return rc;
+  if (column_output_)
+    if (int rc = write_columns(columns_name(T.timestep).c_str())) return rc;
   last_output_step_ = T.timestep;
   return 0;
 }
@@ -431,6 +440,30 @@ int pion_host_sim_set_projection_output(void *s, int axis, int nfields, const pi
   auto *c = static_cast<pion_host::sim_control_gpu *>(s);
   try {
     return io_result(c, c->set_projection_output(axis, nfields, fields));
+  }
+  catch (const std::exception &e) {
+    g_last_exception = e.what();
+    return PION_GPU_EINVAL;
+  }
+}
+int pion_host_sim_add_rt_source(void *s, const pion_gpu_rt_source *src, int *id, double *pos_used)
+{
+  if (!s || !src) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  return io_result(c, c->add_rt_source(*src, id, pos_used));
+}
+int pion_host_sim_set_column_output(void *s, int on)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  return io_result(c, c->set_column_output(on));
+}
+int pion_host_sim_write_columns(void *s, const char *path)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  try {
+    return io_result(c, c->write_columns(path));
   }
   catch (const std::exception &e) {
     g_last_exception = e.what();

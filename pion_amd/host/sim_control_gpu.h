@@ -107,6 +107,22 @@ class sim_control_gpu {
   // digits>.fits (the one file of a slab run: rank 0000); nfields 0 turns it off again.  The same refusals, made here.  Cadence and time steps are untouched
   int set_projection_output(int axis, int nfields, const pion_gpu_proj_field *fields);
   std::string projection_name(long step) const;
+  // Ray-traced column densities (pion_gpu_raytrace; the rules: pion_amd/csrc/dev_raytrace.h, after the reference's
+  // raytracer_USC).  add_rt_source: Add_Source for one radiation source -- on the backend's handle (entry
+  // add_rt_source), or, a table without it, kept here; pos_used (PION_MAX_DIM doubles, may be null): the cell vertex a
+  // finite source was moved to.  write_columns: a FITS file with write_fits' primary header plus RT_Nsources and, per
+  // source n, RT_position_<n>_<d>, RT_at_infty_<n>, RT_Opacity__<n>, RT_Tau_var__<n> (the reference's names,
+  // dataIO/dataio_base.cpp:1267-1282), and per source two double-precision IMAGE extensions of the on-grid cells,
+  // Col_Src_<n>_T0 (column to + through the cell) and DCol_Src_<n>_T0 (through it), traced from P as it stands (after
+  // the boundary update) and streamed a chunk of planes at a time; a table without the entries downloads array 0 and runs
+  // pion_gpu_raytrace_host.  EINVAL and a text: what pion_gpu_add_rt_source refuses; no sources; a sim that is one rank
+  // of several (a slab extent, or a communicator of more than one rank)
+  int add_rt_source(const pion_gpu_rt_source &src, int *id, double *pos_used);
+  int write_columns(const char *path);
+  // from now on every regular output of output_data() is accompanied by <base>_cols_<rank, 4 digits>.<step, 8
+  // digits>.fits; on = 0 turns it off again.  Cadence and time steps are untouched
+  int set_column_output(int on);
+  std::string columns_name(long step) const;
   // restart from the files that hold this sim's planes (written by any number of ranks); sets P, Ph, simtime,
   // timestep, last_dt, next_optime, starttime, finishtime and min_timestep, then assigns and updates the boundaries as
   // Init does.  Wind sources, jets and cooling tables are set up by the caller first, as before Init.
@@ -151,6 +167,10 @@ class sim_control_gpu {
   int filetype_ = 0;             // PION_HOST_FILE_*
   int proj_axis_ = 0;            // set_projection_output: the images that accompany a regular output (none: empty)
   std::vector<pion_gpu_proj_field> proj_fields_;
+  std::vector<pion_gpu_rt_source> rt_sources_, rt_moved_;   // add_rt_source: the sources as given, and at the positions used
+  bool rt_on_backend_ = false;                   // they live on the backend's handle too
+  bool column_output_ = false;                   // set_column_output
+  int columns_refused(const char *who);
   bool projection_collective() const;   // one rank of a slab run whose images are assembled along the ranks
   int project_images(int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part *part, long n, double *img);
   int relay_part(int rc, int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part &part,

@@ -107,6 +107,10 @@ def load_host_library():
     if hasattr(h, "pion_host_sim_write_projection"):   # (likewise)
         h.pion_host_sim_write_projection.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
         h.pion_host_sim_set_projection_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    if hasattr(h, "pion_host_sim_add_rt_source"):   # (likewise)
+        h.pion_host_sim_add_rt_source.argtypes = [C.c_void_p, C.POINTER(abi.RtSource), C.POINTER(C.c_int), _dp]
+        h.pion_host_sim_write_columns.argtypes = [C.c_void_p, C.c_char_p]
+        h.pion_host_sim_set_column_output.argtypes = [C.c_void_p, C.c_int]
     if hasattr(h, "pion_host_project_part_on_host"):   # (likewise)
         h.pion_host_project_part_refused.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         h.pion_host_project_part_refused.restype = C.c_char_p
@@ -271,6 +275,29 @@ class HostSim:
         rc = self.lib.pion_host_sim_set_projection_output(self.s, int(axis), len(fields), abi.proj_fields(fields))
         if rc != 0:
             raise ValueError("pion_host_sim_set_projection_output rc=%d: %s" % (rc, self.last_error()))
+
+    def add_rt_source(self, src):
+        """pion_host_sim_add_rt_source: a radiation source (an abi.RtSource, or what abi.rt_source takes) for the
+        ray-traced column densities; returns (id, position used) -- a finite source is moved to a cell vertex"""
+        i, pos = C.c_int(-1), (C.c_double * 3)()
+        rc = self.lib.pion_host_sim_add_rt_source(self.s, C.byref(abi.rt_source(src)), C.byref(i), pos)
+        if rc != 0:
+            raise ValueError("pion_host_sim_add_rt_source rc=%d: %s" % (rc, self.last_error()))
+        return i.value, tuple(pos)
+
+    def write_columns(self, path):
+        """the FITS file of the ray-traced columns of P, per source Col_Src_<id>_T0 and DCol_Src_<id>_T0
+        (pion_host_sim_write_columns); pion_amd.fits.read returns the images by name"""
+        rc = self.lib.pion_host_sim_write_columns(self.s, os.fsencode(path))
+        if rc != 0:
+            raise RuntimeError("pion_host_sim_write_columns rc=%d: %s" % (rc, self.last_error()))
+
+    def set_column_output(self, on=True):
+        """from now on every regular output of time_int is accompanied by <base>_cols_<rank>.<step>.fits
+        (pion_host_sim_set_column_output); on = False turns it off"""
+        rc = self.lib.pion_host_sim_set_column_output(self.s, 1 if on else 0)
+        if rc != 0:
+            raise ValueError("pion_host_sim_set_column_output rc=%d: %s" % (rc, self.last_error()))
 
     def set_output_filetype(self, filetype):
         """FILE_PIONRAW (the default) or FILE_FITS for the regular outputs of time_int; checkpoints stay PIONRAW2

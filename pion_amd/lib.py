@@ -105,6 +105,18 @@ def load_library():
         lib.pion_gpu_project_part_count.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         lib.pion_gpu_project_part_count.restype = C.c_long
         lib.pion_gpu_project_part.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pion_gpu_raytrace"):   # (likewise)
+        _cfgp, _srcp = C.POINTER(abi.PionGpuConfig), C.POINTER(abi.RtSource)
+        lib.pion_gpu_add_rt_source.argtypes = [C.c_void_p, _srcp, C.POINTER(C.c_int), _dp]
+        lib.pion_gpu_raytrace.argtypes = [C.c_void_p, C.c_int]
+        lib.pion_gpu_rt_columns.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        lib.pion_gpu_rt_count.argtypes = [C.c_void_p, C.c_int]
+        lib.pion_gpu_rt_count.restype = C.c_long
+        lib.pion_gpu_pack_columns.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        lib.pion_gpu_rt_plan.argtypes = [_cfgp, _srcp, C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_long)]
+        lib.pion_gpu_raytrace_host.argtypes = [_cfgp, _srcp, _dp, _dp, _dp]
+        lib.pion_gpu_rt_refused.argtypes = [_cfgp, _srcp]
+        lib.pion_gpu_rt_refused.restype = C.c_char_p
     lib.pion_gpu_interface_flux.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
     if hasattr(lib, "pion_gpu_cell_advance"):   # (likewise)
         lib.pion_gpu_cell_advance.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp]
@@ -138,7 +150,39 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_fits_prim_count", "pion_gpu_unpack_fits", "pion_gpu_unpack_fits_status",
     "pion_gpu_cell_advance", "pion_gpu_project_count", "pion_gpu_project",
     "pion_gpu_project_part_count", "pion_gpu_project_part",
+    "pion_gpu_add_rt_source", "pion_gpu_raytrace", "pion_gpu_rt_columns", "pion_gpu_rt_count",
+    "pion_gpu_pack_columns", "pion_gpu_rt_plan", "pion_gpu_raytrace_host", "pion_gpu_rt_refused",
 ]
+
+
+def rt_refused(cfg, src):
+    """pion_gpu_rt_refused: the text with which the ray tracer refuses `src` (an abi.RtSource or what abi.rt_source
+    takes) on the grid of `cfg`, or None.  Host only: needs no GPU."""
+    t = load_library().pion_gpu_rt_refused(C.byref(cfg), C.byref(abi.rt_source(src)))
+    return None if t is None else t.decode()
+
+
+def rt_plan(cfg, src):
+    """pion_gpu_rt_plan: (tile, launches, levels) -- the tile of the tiled kernel, its launches (tile-levels) and the
+    launches of the per-level kernel for `src` on the grid of `cfg`.  Host only: needs no GPU."""
+    tile, launches, levels = (C.c_int * 3)(), C.c_long(-1), C.c_long(-1)
+    rc = load_library().pion_gpu_rt_plan(C.byref(cfg), C.byref(abi.rt_source(src)), tile, C.byref(launches), C.byref(levels))
+    if rc != 0:
+        raise PionGpuError("rt_plan", rc, rt_refused(cfg, src) or "invalid arguments")
+    return tuple(tile), launches.value, levels.value
+
+
+def raytrace_host(cfg, src, P):
+    """pion_gpu_raytrace_host: (col, dcol), each [nz][ny][nx], of `src` on the host array P ([nvar][nz_all][ny_all]
+    [nx_all], ghosts included) by the device's own rules in a host loop.  Host only: needs no GPU."""
+    P = np.ascontiguousarray(P, dtype=np.float64).reshape(-1)
+    assert P.size == cfg.nvar * abi.ncell_all(cfg)
+    shape = (cfg.ng[2], cfg.ng[1], cfg.ng[0])
+    col, dcol = np.zeros(shape), np.zeros(shape)
+    rc = load_library().pion_gpu_raytrace_host(C.byref(cfg), C.byref(abi.rt_source(src)), _p(P), _p(col), _p(dcol))
+    if rc != 0:
+        raise PionGpuError("raytrace_host", rc, rt_refused(cfg, src) or "invalid arguments")
+    return col, dcol
 
 
 def rows_windows(cfg, lo=0, hi=None, limit=None):
@@ -427,6 +471,32 @@ class GpuSim:
         n = C.c_long(-1)
         self._chk(self.lib.pion_gpu_unpack_fits_status(self.h, C.byref(n)), "unpack_fits_status")
         return n.value
+
+    # --- ray-traced column densities
+    def add_rt_source(self, src):
+        """pion_gpu_add_rt_source: (id, pos_used) -- a finite source is moved to the nearest cell vertex per axis"""
+        sid, pos = C.c_int(-1), (C.c_double * 3)()
+        self._chk(self.lib.pion_gpu_add_rt_source(self.h, C.byref(abi.rt_source(src)), C.byref(sid), pos), "add_rt_source")
+        return sid.value, tuple(pos)
+
+    def raytrace(self, which=0):
+        """pion_gpu_raytrace: the columns of every source from array `which` (0 = P, 1 = Ph); enqueued"""
+        self._chk(self.lib.pion_gpu_raytrace(self.h, int(which)), "raytrace")
+
+    def rt_columns(self, sid, what=0):
+        """pion_gpu_rt_columns: col (what = 0) or dcol (1) of source sid, [nz][ny][nx]; synchronises"""
+        out = np.empty((self.cfg.ng[2], self.cfg.ng[1], self.cfg.ng[0]))
+        self._chk(self.lib.pion_gpu_rt_columns(self.h, int(sid), int(what), _p(out)), "rt_columns")
+        return out
+
+    def rt_count(self, planes):
+        """pion_gpu_rt_count: doubles of `planes` planes of the slab axis of one column array"""
+        return self.lib.pion_gpu_rt_count(self.h, int(planes))
+
+    def pack_columns(self, sid, what, plane_lo, plane_hi, dbuf_ptr):
+        """pion_gpu_pack_columns: the planes [plane_lo, plane_hi) of a column array as big-endian doubles at dbuf_ptr"""
+        self._chk(self.lib.pion_gpu_pack_columns(self.h, int(sid), int(what), int(plane_lo), int(plane_hi),
+                                                 C.c_void_p(dbuf_ptr)), "pack_columns")
 
     def project_count(self, axis, nfields):
         """pion_gpu_project_count: doubles one project() call writes, [nfields][NJ][NI]; raises for a grid or an axis
