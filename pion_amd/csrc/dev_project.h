@@ -3,7 +3,7 @@
 // the reference's perpendicular Abel integral (analysis/projection/perp_projection.cpp: calc_projection_column,
 // :404-487, with the slopes of the second loop of get_emission_absorption_data, :338-390, and the pixel list of
 // :225-252).  Plain __host__ __device__ functions of GridDesc and OutputCfg, written the way dev_output.h is: the
-// kernels of pion_project.hip run them on the device, the host writer (pion_amd/host/fits_io.cpp) runs the same
+// kernels of pion_project.hip run them on the device, the host writer (pion_amd/host/projection_io.cpp) runs the same
 // functions in a host loop for a backend without the projection entries.  The includer provides __host__ /
 // __device__, as for dev_output.h.
 //

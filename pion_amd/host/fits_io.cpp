@@ -9,18 +9,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
+#include <stdexcept>
 
-#ifndef __host__
-#define __host__
-#define __device__
-#endif
-#include "../csrc/dev_output.h"
-#include "../csrc/dev_project.h"
-#include "../csrc/dev_raytrace.h"
+#include "dev_rules.h"
 #include "sim_control_gpu.h"
-#include "slab_comm.h"
-#include "snapshot_io.h"
 
 namespace pion_host {
 
@@ -96,7 +88,8 @@ void hierarch(std::string &h, const std::string &name, const std::string &value,
   else card(h, "HIERARCH " + name + " = " + (type == 'd' ? fits_double(value) : value));
 }
 
-// the grid as dev_output.h's functions see it (pion_gpu_create's GridDesc)
+}  // namespace
+
 pion::GridDesc grid_desc(const pion_gpu_config &c)
 {
   pion::GridDesc g;
@@ -116,8 +109,6 @@ pion::GridDesc grid_desc(const pion_gpu_config &c)
   g.sph_vol = nullptr;
   return g;
 }
-
-}  // namespace
 
 std::string fits_primary_header(const std::vector<snapshot_param> &params)
 {
@@ -156,6 +147,22 @@ std::string fits_image_header(const char *extname, int ndim, const long *naxis)
   fixed_string(h, "EXTNAME", extname);
   finish(h);
   return h;
+}
+
+fits_layout::fits_layout(const std::string &primary_, const std::vector<std::string> &ext_, long run_bytes)
+    : primary(primary_), ext(ext_), data_padded(padded(run_bytes)),
+      stride((ext_.empty() ? 0 : (long)ext_[0].size()) + data_padded), total((long)primary_.size() + (long)ext_.size() * stride)
+{
+  for (const std::string &h : ext)
+    if (h.size() != ext[0].size()) throw std::logic_error("fits_layout: the extension headers differ in length");
+}
+
+int fits_layout::start(PartFile &f) const
+{
+  int rc = f.resize(total);
+  if (!rc) rc = f.write(primary.data(), primary.size(), 0);
+  for (size_t i = 0; i < ext.size() && !rc; i++) rc = f.write(ext[i].data(), ext[i].size(), header_at((long)i));
+  return rc;
 }
 
 // ---- the reader --------------------------------------------------------------------------------------------------
@@ -406,22 +413,14 @@ long fits_convert_run(const pion_gpu_config &cfg, int var, double *run, size_t n
 
 int sim_control_gpu::write_fits(const char *path)
 {
-  io_error_.clear();
-  if (!path || !*path) {
-    io_error_ = "write_fits: no path";
-    return PION_GPU_EINVAL;
-  }
+  if (int rc = path_refused("write_fits", path)) return rc;
   if (cfg.ntracer > pion::OUT_MAX_TRACERS) {
     io_error_ = "write_fits: only accepts <= 5 tracers (this sim has " + std::to_string(cfg.ntracer) + ")";
     return PION_GPU_EINVAL;
   }
   std::vector<snapshot_param> params;
   long nloc = 0;
-  if (int rc = snapshot_params(params, nloc)) return rc;
-  if (int rc = finish_halo()) {
-    io_error_ = "write_fits: finish_halo failed";
-    return rc;
-  }
+  if (int rc = writer_params("write_fits", params, nloc)) return rc;
   const pion::GridDesc g = grid_desc(cfg);
   const pion::OutputCfg o = pion::out_cfg(cfg);
   const pion::OutGeom q = pion::out_geom(g);
@@ -429,7 +428,6 @@ int sim_control_gpu::write_fits(const char *path)
   const long plane = (long)q.rows * q.nx;
   const long naxis[3] = {q.nx, (cfg.ndim == 3) ? (long)q.rows : nloc, nloc};
 
-  // 1. the header blocks; every extension's header has the same length
   const std::string primary = fits_primary_header(params);
   std::vector<std::string> ext((size_t)nimage);
   for (int i = 0; i < nimage; i++) {
@@ -438,25 +436,13 @@ int sim_control_gpu::write_fits(const char *path)
     ext[i] = fits_image_header(name, cfg.ndim, naxis);
   }
   const long run_bytes = nloc * plane * (long)sizeof(double);
-  const long stride = (long)ext[0].size() + padded(run_bytes);   // from one image's data to the next one's
-  const long off = (long)primary.size() + (long)ext[0].size();   // the first image's data
-  const long total = (long)primary.size() + nimage * stride;
+  const fits_layout L(primary, ext, run_bytes);
 
-  const std::string tmp = std::string(path) + ".part";
-  int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (fd < 0) {
-    io_error_ = "write_fits: cannot create " + tmp + ": " + strerror(errno);
-    return PION_GPU_EINVAL;
-  }
-  // 3. (first) the file at its full length: what no write below covers -- the padding after each data unit -- reads
-  // as zero bytes
-  int rc = (ftruncate(fd, (off_t)total) != 0) ? PION_GPU_EINVAL : 0;
-  if (!rc && full_pwrite(fd, primary.data(), primary.size(), 0)) rc = PION_GPU_EINVAL;
-  for (int i = 0; i < nimage && !rc; i++)
-    if (full_pwrite(fd, ext[i].data(), ext[i].size(), (off_t)((long)primary.size() + i * stride))) rc = PION_GPU_EINVAL;
-  // 2. the data
+  PartFile f("write_fits", path, io_error_);
+  if (!f.ok()) return PION_GPU_EINVAL;
+  int rc = L.start(f);
   if (!rc && be_->fits_to_host_begin && be_->fits_count && be_->ongrid_to_host_end)
-    rc = stream_runs(fd, true, nimage, nloc, plane, off, stride, "write_fits");
+    rc = stream_runs(f, true, nimage, nloc, plane, L.data_at(0), L.stride, "write_fits");
   else if (!rc) {
     // no streaming entries: array 0 whole, the images evaluated and swapped here
     std::vector<double> A((size_t)cfg.nvar * g.ncell);
@@ -471,472 +457,10 @@ int sim_control_gpu::write_fits(const char *path)
           const int jy = pion::out_row_jy(g, k, j);
           for (long ix = 0; ix < q.nx; ix++) R[(size_t)(b0 + ix)] = pion::out_be64(pion::out_value(g, o, im, A.data(), c0 + ix, jy));
         }
-      if (full_pwrite(fd, R.data(), (size_t)run_bytes, (off_t)(off + i * stride))) rc = PION_GPU_EINVAL;
+      rc = f.write(R.data(), (size_t)run_bytes, L.data_at(i));
     }
   }
-  if (rc && io_error_.empty()) io_error_ = "write_fits: writing " + tmp + " failed: " + strerror(errno);
-  close(fd);
-  // 4.
-  if (!rc && rename(tmp.c_str(), path) != 0) {
-    io_error_ = std::string("write_fits: cannot rename to ") + path + ": " + strerror(errno);
-    rc = PION_GPU_EINVAL;
-  }
-  if (rc) unlink(tmp.c_str());
-  return rc;
-}
-
-// ---- projected images (the rules: dev_project.h) -----------------------------------------------------------------
-// ---- dev_project.h's functions in a host loop, over a whole array A ([nvar][ncell], ghosts included): what a backend
-// table without projection entries gets, and the C view at the end of this file
-// the images of a single grid, [nfields][NJ][NI]
-static void project_on_host(const pion::GridDesc &g, const pion::OutputCfg &o, int axis, int nfields, const pion_gpu_proj_field *fields,
-                     const double *A, double *img)
-{
-  const pion::ProjGeom q = pion::proj_geom(g, axis);
-  for (int f = 0; f < nfields; f++)
-    for (long j = 0; j < q.nj; j++)
-      for (long i = 0; i < q.ni; i++) {
-        const long first = q.c0 + i * q.si + j * q.sj;
-        img[((long)f * q.nj + j) * q.ni + i] = (g.cyl == 1) ? pion::abel_column(g, o, fields[f], q, A, first, (int)j)
-                                                            : pion::proj_column(g, o, fields[f], q, axis, A, first);
-      }
-}
-// one rank's part, into the image of the whole domain [nfields][NJ_global][NI_global] (in/out)
-static void project_part_on_host(const pion::GridDesc &g, const pion::OutputCfg &o, int axis, int nfields,
-                          const pion_gpu_proj_field *fields, const pion::ProjPart &pp, const double *A, double *img)
-{
-  const pion::ProjGeom q = pion::proj_geom(g, axis);
-  const pion::GridDesc gg = pion::proj_part_grid(g, pp);
-  const bool along = pion::proj_part_along_slab(g, axis);
-  const long npix = (long)pion::proj_part_nj(g, q, axis, pp) * q.ni;
-  for (int f = 0; f < nfields; f++) {
-    double *out = img + (long)f * npix;
-    if (g.cyl == 1) {
-      for (long j = 0; j < pp.plane_lo + q.nsum; j++)   // the impact rows below this rank's upper edge
-        for (long i = 0; i < q.ni; i++)
-          out[j * q.ni + i] = pion::abel_column_part(g, gg, o, fields[f], q, pp, A, q.c0 + i * q.si, (int)j, out[j * q.ni + i]);
-      continue;
-    }
-    for (long j = 0; j < q.nj; j++)
-      for (long i = 0; i < q.ni; i++) {
-        const long first = q.c0 + i * q.si + j * q.sj;
-        double &px = out[(j + (along ? 0 : pp.plane_lo)) * q.ni + i];
-        px = along ? pion::proj_column_part(g, o, fields[f], q, pp, A, first, px)
-                   : pion::proj_column(g, o, fields[f], q, axis, A, first);
-      }
-  }
-}
-
-// one rank of a slab run whose images are assembled along the ranks: a slab extent AND a communicator of more than
-// one rank that has the send / receive pair
-bool sim_control_gpu::projection_collective() const
-{
-  return slab.set && comm_ && comm_->world() > 1 && comm_->has_relay();
-}
-
-int sim_control_gpu::projection_refused(int axis, int nfields, const pion_gpu_proj_field *fields, const char *who)
-{
-  const char *why = nullptr;
-  if ((slab.set || (comm_ && comm_->world() > 1)) && !projection_collective()) {
-    if (!slab.set)
-      why = "project: this sim is one rank of a slab run without a slab extent (set_slab_extent), and its part of the image "
-            "cannot be placed";
-    else if (!comm_ || comm_->world() < 2)
-      why = "project: this sim is one rank of a slab run without a communicator of more than one rank, and the images of "
-            "more than one rank are assembled along the communicator";
-    else
-      why = "project: this sim is one rank of a slab run, and its communicator's send / receive is not supported";
-  }
-  if (!why) why = pion::proj_refused_grid(grid_desc(cfg), axis);
-  if (!why) why = pion::proj_refused_fields(pion::out_cfg(cfg), nfields, fields);
-  if (!why) return 0;
-  io_error_ = std::string(who) + ": " + why;
-  return PION_GPU_EINVAL;
-}
-
-int sim_control_gpu::set_projection_output(int axis, int nfields, const pion_gpu_proj_field *fields)
-{
-  io_error_.clear();
-  if (nfields == 0) {
-    proj_fields_.clear();
-    return 0;
-  }
-  if (int rc = projection_refused(axis, nfields, fields, "set_projection_output")) return rc;
-  proj_axis_ = axis;
-  proj_fields_.assign(fields, fields + nfields);
-  return 0;
-}
-
-// this sim's images -- a whole grid's, or (part) this rank's part added into `img` --, on the device where the backend
-// has the entries, else from a download by the functions above
-int sim_control_gpu::project_images(int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part *part,
-                                    long n, double *img)
-{
-  if (!part && be_->project_count && be_->project_to_host) {
-    if (be_->project_count(h_, axis, nfields) != n) {
-      io_error_ = "write_projection: the backend refuses: " + last_error();
-      return PION_GPU_EINVAL;
-    }
-    const int rc = be_->project_to_host(h_, axis, nfields, fields, img);
-    if (rc) io_error_ = "write_projection: project_to_host failed: " + last_error();
-    return rc;
-  }
-  if (part && be_->project_part_count && be_->project_part_to_host) {
-    if (be_->project_part_count(h_, axis, nfields, part) != n) {
-      io_error_ = "write_projection: the backend refuses: " + last_error();
-      return PION_GPU_EINVAL;
-    }
-    const int rc = be_->project_part_to_host(h_, axis, nfields, fields, part, img);
-    if (rc) io_error_ = "write_projection: project_part_to_host failed: " + last_error();
-    return rc;
-  }
-  const pion::GridDesc g = grid_desc(cfg);
-  std::vector<double> A((size_t)cfg.nvar * g.ncell);
-  if (int rc = be_->download(h_, 0, A.data())) {
-    io_error_ = "write_projection: download failed: " + last_error();
-    return rc;
-  }
-  if (!part) project_on_host(g, pion::out_cfg(cfg), axis, nfields, fields, A.data(), img);
-  else {
-    const pion::ProjPart pp = {part->plane_lo, part->global_planes, part->last, part->global_xmin};
-    project_part_on_host(g, pion::out_cfg(cfg), axis, nfields, fields, pp, A.data(), img);
-  }
-  return 0;
-}
-
-// One rank of a slab run (dev_project.h, "parts"): the image of the whole domain comes from the rank below, gains this
-// rank's part and goes to the rank above.  The invariant that keeps every rank from waiting for ever: whatever `rc`
-// this rank arrives with and whatever happens here, it ALWAYS takes the message of the rank below and ALWAYS sends one
-// to the rank above -- the image, or a failure.  Returns 0 with the image in `img` (complete on the last rank)
-int sim_control_gpu::relay_part(int rc, int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part &part,
-                                std::vector<double> &img)
-{
-  // (refused here: the length is unknown, and the message of the rank below is taken off the wire without a buffer)
-  const size_t bytes = rc ? 0 : img.size() * sizeof(double);
-  int below = 0;
-  const int rrc = comm_->recv_from_below(rc ? nullptr : img.data(), bytes, &below);
-  if (!rc && below) {
-    io_error_ = "write_projection: a rank below failed, no image is written";
-    rc = PION_GPU_EINVAL;
-  }
-  if (!rc && rrc) {
-    io_error_ = "write_projection: receiving the image of the rank below failed: " + comm_->last_error();
-    rc = rrc;
-  }
-  if (!rc) rc = project_images(axis, nfields, fields, &part, (long)img.size(), img.data());
-  const int src = comm_->send_to_above(rc ? nullptr : img.data(), bytes, rc ? 1 : 0);
-  if (!rc && src) {
-    io_error_ = "write_projection: handing the image to the rank above failed: " + comm_->last_error();
-    rc = src;
-  }
-  return rc;
-}
-
-int sim_control_gpu::write_projection(const char *path, int axis, int nfields, const pion_gpu_proj_field *fields)
-{
-  io_error_.clear();
-  if (!path || !*path) {
-    io_error_ = "write_projection: no path";
-    return PION_GPU_EINVAL;
-  }
-  // one rank of a slab run: the call is collective, and the last rank writes the one file
-  const bool chain = projection_collective();
-  std::vector<snapshot_param> params;
-  long nloc = 0;
-  int rc = projection_refused(axis, nfields, fields, "write_projection");
-  if (!rc) rc = snapshot_params(params, nloc);
-  if (!rc && (rc = finish_halo())) io_error_ = "write_projection: finish_halo failed";
-  if (rc && !chain) return rc;
-
-  // 1. the images, native doubles [nfields][NJ][NI] of the whole domain
-  const pion::GridDesc g = grid_desc(cfg);
-  pion::ProjGeom q = pion::ProjGeom();
-  std::vector<double> img;
-  if (!rc) {
-    q = pion::proj_geom(g, axis);
-    if (chain) q.nj = pion::proj_part_along_slab(g, axis) ? q.nj : slab.global_planes;
-    img.assign((size_t)pion::proj_count(q, nfields), 0.0);
-  }
-  if (!chain) rc = project_images(axis, nfields, fields, nullptr, (long)img.size(), img.data());
-  else {
-    // global_xmin: the header's Xmin (snapshot_io.cpp: global_view), equal to the single grid's where dx and xmin are dyadic
-    const pion_gpu_proj_part part = {slab.plane_lo, slab.global_planes, comm_->rank() == comm_->world() - 1 ? 1 : 0,
-                                     cfg.xmin[cfg.ndim - 1] - slab.plane_lo * cfg.dx};
-    rc = relay_part(rc, axis, nfields, fields, part, img);
-    if (rc || !part.last) return rc;
-    // the header of a single-rank sim of the whole problem: nothing rank-local
-    for (snapshot_param &p : params) {
-      if (p.key == "pion_rank" || p.key == "pion_slab_lo") p.value = "0";
-      if (p.key == "pion_world") p.value = "1";
-      if (p.key == "pion_slab_n") p.value = std::to_string(slab.global_planes);
-    }
-  }
-  if (rc) return rc;
-  const long npix = (long)q.nj * q.ni, n = pion::proj_count(q, nfields);
-  auto real = [](double x) {
-    char b[64];
-    snprintf(b, sizeof b, "%.17g", x);
-    return std::string(b);
-  };
-  params.push_back({"pion_proj_axis", std::to_string(axis), 'i'});
-  for (int i = 0; i < nfields; i++) {
-    const std::string k = "pion_proj_" + std::to_string(i) + "_";
-    params.push_back({k + "a", std::to_string(fields[i].a), 'i'});
-    params.push_back({k + "var", std::to_string(fields[i].var), 'i'});
-    params.push_back({k + "coef", real(fields[i].coef), 'd'});
-    params.push_back({k + "b", real(fields[i].b), 'd'});
-  }
-  // 2. the file: big-endian, every extension's header of the same length
-  std::vector<unsigned long long> R((size_t)n);
-  for (long k = 0; k < n; k++) R[(size_t)k] = pion::out_be64(img[(size_t)k]);
-  const std::string primary = fits_primary_header(params);
-  const long naxis[2] = {q.ni, q.nj};
-  std::vector<std::string> ext((size_t)nfields);
-  for (int i = 0; i < nfields; i++) ext[(size_t)i] = fits_image_header(fields[i].name, 2, naxis);
-  const long run_bytes = npix * (long)sizeof(double);
-  const long stride = (long)ext[0].size() + padded(run_bytes);
-  const long total = (long)primary.size() + nfields * stride;
-
-  const std::string tmp = std::string(path) + ".part";
-  int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (fd < 0) {
-    io_error_ = "write_projection: cannot create " + tmp + ": " + strerror(errno);
-    return PION_GPU_EINVAL;
-  }
-  rc = (ftruncate(fd, (off_t)total) != 0) ? PION_GPU_EINVAL : 0;   // (the padding reads as zero bytes)
-  if (!rc && full_pwrite(fd, primary.data(), primary.size(), 0)) rc = PION_GPU_EINVAL;
-  for (int i = 0; i < nfields && !rc; i++) {
-    const long at = (long)primary.size() + i * stride;
-    if (full_pwrite(fd, ext[(size_t)i].data(), ext[(size_t)i].size(), (off_t)at)) rc = PION_GPU_EINVAL;
-    if (!rc && full_pwrite(fd, R.data() + (size_t)i * npix, (size_t)run_bytes, (off_t)(at + (long)ext[(size_t)i].size())))
-      rc = PION_GPU_EINVAL;
-  }
-  if (rc) io_error_ = "write_projection: writing " + tmp + " failed: " + strerror(errno);
-  close(fd);
-  if (!rc && rename(tmp.c_str(), path) != 0) {
-    io_error_ = std::string("write_projection: cannot rename to ") + path + ": " + strerror(errno);
-    rc = PION_GPU_EINVAL;
-  }
-  if (rc) unlink(tmp.c_str());
-  return rc;
-}
-
-// ---- ray-traced column densities (the rules: dev_raytrace.h) -------------------------------------------------------
-int sim_control_gpu::columns_refused(const char *who)
-{
-  const char *why = nullptr;
-  if (slab.set || (comm_ && comm_->world() > 1))
-    why = "raytrace: this sim is one rank of a slab run, and columns are not handed from rank to rank";
-  if (!why) return 0;
-  io_error_ = std::string(who) + ": " + why;
-  return PION_GPU_EINVAL;
-}
-
-int sim_control_gpu::add_rt_source(const pion_gpu_rt_source &src, int *id, double *pos_used)
-{
-  io_error_.clear();
-  if (int rc = columns_refused("add_rt_source")) return rc;
-  if (const char *why = pion::rt_refused(cfg, &src)) {
-    io_error_ = std::string("add_rt_source: ") + why;
-    return PION_GPU_EINVAL;
-  }
-  if (rt_sources_.size() >= PION_MAX_RT_SOURCES) {
-    io_error_ = "add_rt_source: raytrace: more than PION_MAX_RT_SOURCES (4) sources";
-    return PION_GPU_EINVAL;
-  }
-  pion_gpu_rt_source moved = src;
-  double used[PION_MAX_DIM];
-  if (be_->add_rt_source) {
-    int i = -1;
-    if (int rc = be_->add_rt_source(h_, &src, &i, used)) {
-      io_error_ = "add_rt_source: the backend refuses: " + last_error();
-      return rc;
-    }
-    rt_on_backend_ = true;
-  }
-  else (void)pion::rt_make_source(cfg, src, used);
-  for (int a = 0; a < PION_MAX_DIM; a++) {
-    moved.pos[a] = used[a];
-    if (pos_used) pos_used[a] = used[a];
-  }
-  rt_sources_.push_back(src);
-  rt_moved_.push_back(moved);
-  if (id) *id = (int)rt_sources_.size() - 1;
-  return 0;
-}
-
-int sim_control_gpu::set_column_output(int on)
-{
-  io_error_.clear();
-  if (!on) {
-    column_output_ = false;
-    return 0;
-  }
-  if (int rc = columns_refused("set_column_output")) return rc;
-  if (rt_sources_.empty()) {
-    io_error_ = "set_column_output: raytrace: the sim has no radiation source (add_rt_source)";
-    return PION_GPU_EINVAL;
-  }
-  column_output_ = true;
-  return 0;
-}
-
-int sim_control_gpu::write_columns(const char *path)
-{
-  io_error_.clear();
-  if (!path || !*path) {
-    io_error_ = "write_columns: no path";
-    return PION_GPU_EINVAL;
-  }
-  if (int rc = columns_refused("write_columns")) return rc;
-  if (rt_sources_.empty()) {
-    io_error_ = "write_columns: raytrace: the sim has no radiation source (add_rt_source)";
-    return PION_GPU_EINVAL;
-  }
-  std::vector<snapshot_param> params;
-  long nloc = 0;
-  if (int rc = snapshot_params(params, nloc)) return rc;
-  if (int rc = finish_halo()) {
-    io_error_ = "write_columns: finish_halo failed";
-    return rc;
-  }
-  const pion::GridDesc g = grid_desc(cfg);
-  const pion::OutGeom q = pion::out_geom(g);
-  const int nsrc = (int)rt_sources_.size(), nimage = 2 * nsrc;
-  const long plane = (long)q.rows * q.nx;
-  const long naxis[3] = {q.nx, (cfg.ndim == 3) ? (long)q.rows : nloc, nloc};
-
-  // the sources, under the reference's names (set_rt_src_params, dataio_base.cpp:1267-1282)
-  auto real = [](double x) {
-    char b[64];
-    snprintf(b, sizeof b, "%.17g", x);
-    return std::string(b);
-  };
-  params.push_back({"RT_Nsources", std::to_string(nsrc), 'i'});
-  for (int n = 0; n < nsrc; n++) {
-    const pion_gpu_rt_source &s = rt_moved_[(size_t)n];
-    const std::string k = std::to_string(n);
-    std::string pos;
-    for (int a = 0; a < PION_MAX_DIM; a++) {
-      double p = s.pos[a];
-      if (s.at_infinity) p = (a == s.dir / 2) ? ((s.dir & 1) ? 1.0e200 : -1.0e200) : 0.0;
-      pos += (a ? " " : "") + real(p);
-    }
-    params.push_back({"RT_position_" + k + "_", pos, 'd'});
-    params.push_back({"RT_at_infty_" + k, std::to_string(s.at_infinity ? 1 : 0), 'i'});
-    params.push_back({"RT_Opacity__" + k, std::to_string(s.opacity), 'i'});
-    params.push_back({"RT_Tau_var__" + k, std::to_string(s.opacity_var), 'i'});
-  }
-
-  const std::string primary = fits_primary_header(params);
-  std::vector<std::string> ext((size_t)nimage);
-  for (int i = 0; i < nimage; i++) {
-    const std::string name = std::string((i & 1) ? "DCol_Src_" : "Col_Src_") + std::to_string(i / 2) + "_T0";
-    ext[(size_t)i] = fits_image_header(name.c_str(), cfg.ndim, naxis);
-  }
-  const long run_bytes = nloc * plane * (long)sizeof(double);
-  const long stride = (long)ext[0].size() + padded(run_bytes);
-  const long off = (long)primary.size() + (long)ext[0].size();
-  const long total = (long)primary.size() + nimage * stride;
-
-  const std::string tmp = std::string(path) + ".part";
-  int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (fd < 0) {
-    io_error_ = "write_columns: cannot create " + tmp + ": " + strerror(errno);
-    return PION_GPU_EINVAL;
-  }
-  int rc = (ftruncate(fd, (off_t)total) != 0) ? PION_GPU_EINVAL : 0;   // (the padding reads as zero bytes)
-  if (!rc && full_pwrite(fd, primary.data(), primary.size(), 0)) rc = PION_GPU_EINVAL;
-  for (int i = 0; i < nimage && !rc; i++)
-    if (full_pwrite(fd, ext[(size_t)i].data(), ext[(size_t)i].size(), (off_t)((long)primary.size() + i * stride))) rc = PION_GPU_EINVAL;
-
-  if (!rc && rt_on_backend_ && be_->raytrace && be_->rt_count && be_->columns_to_host_begin && be_->ongrid_to_host_end) {
-    // traced on the device; then image after image, a chunk of planes at a time: the pack and the copy of the next
-    // chunk are enqueued while this one is written
-    long cp = (64L << 20) / (long)sizeof(double) / std::max(1L, be_->rt_count(h_, 1));
-    if (const char *e = getenv("PION_SNAPSHOT_CHUNK_PLANES"))
-      if (atol(e) > 0) cp = atol(e);
-    cp = std::max(1L, std::min(cp, nloc));
-    const long nchunk = (nloc + cp - 1) / cp, njob = nimage * nchunk;
-    auto begin = [&](long job) {
-      const long i = job / nchunk, a = (job % nchunk) * cp;
-      return be_->columns_to_host_begin(h_, (int)(i / 2), (int)(i & 1), (int)a, (int)std::min(nloc, a + cp), (int)(job & 1));
-    };
-    rc = be_->raytrace(h_, 0);
-    if (!rc) rc = begin(0);
-    for (long job = 0; job < njob && !rc; job++) {
-      if (job + 1 < njob) rc = begin(job + 1);
-      const double *src = nullptr;
-      if (!rc) rc = be_->ongrid_to_host_end(h_, (int)(job & 1), &src);
-      if (rc) break;
-      const long i = job / nchunk, a = (job % nchunk) * cp, b = std::min(nloc, a + cp);
-      if (full_pwrite(fd, src, (size_t)((b - a) * plane) * sizeof(double), (off_t)(off + i * stride + a * plane * (long)sizeof(double))))
-        rc = PION_GPU_EINVAL;
-    }
-    if (rc && io_error_.empty() && !last_error().empty()) io_error_ = "write_columns: tracing or staging the planes failed: " + last_error();
-  }
-  else if (!rc) {
-    // no entries: array 0 whole, traced by the same rules in a host loop, swapped here
-    std::vector<double> A((size_t)cfg.nvar * g.ncell), col((size_t)(nloc * plane)), dcol((size_t)(nloc * plane));
-    std::vector<unsigned long long> R((size_t)(nloc * plane));
-    rc = be_->download(h_, 0, A.data());
-    if (rc) io_error_ = "write_columns: download failed: " + last_error();
-    for (int n = 0; n < nsrc && !rc; n++) {
-      if (pion_gpu_raytrace_host(&cfg, &rt_sources_[(size_t)n], A.data(), col.data(), dcol.data())) {
-        io_error_ = "write_columns: pion_gpu_raytrace_host refuses the source";
-        rc = PION_GPU_EINVAL;
-      }
-      for (int w = 0; w < 2 && !rc; w++) {
-        const std::vector<double> &src = w ? dcol : col;
-        for (size_t k = 0; k < R.size(); k++) R[k] = pion::out_be64(src[k]);
-        if (full_pwrite(fd, R.data(), (size_t)run_bytes, (off_t)(off + (2 * n + w) * stride))) rc = PION_GPU_EINVAL;
-      }
-    }
-  }
-  if (rc && io_error_.empty()) io_error_ = "write_columns: writing " + tmp + " failed: " + strerror(errno);
-  close(fd);
-  if (!rc && rename(tmp.c_str(), path) != 0) {
-    io_error_ = std::string("write_columns: cannot rename to ") + path + ": " + strerror(errno);
-    rc = PION_GPU_EINVAL;
-  }
-  if (rc) unlink(tmp.c_str());
-  return rc;
-}
-
-// ---- C view of dev_project.h's host functions (ctypes: tests; a caller that assembles images with a transport of its
-// own and no device): no sim, no backend -- a configuration and a whole array [nvar][ncell_all]
-extern "C" {
-// null, or the text with which pion_gpu_project_part refuses these arguments (`img`: the caller's image buffer)
-const char *pion_host_project_part_refused(const pion_gpu_config *cfg, int axis, int nfields, const pion_gpu_proj_field *fields,
-                                           const pion_gpu_proj_part *part, const void *img)
-{
-  if (!cfg) return "project: no configuration";
-  const pion::GridDesc g = grid_desc(*cfg);
-  const char *why = pion::proj_refused_grid(g, axis);
-  if (!why) why = pion::proj_refused_fields(pion::out_cfg(*cfg), nfields, fields);
-  if (!why) why = pion::proj_refused_part(g, part);
-  if (!why && !img) why = "project: no buffer";
-  return why;
-}
-// proj_column / abel_column over every pixel: img = [nfields][NJ][NI]
-int pion_host_project_on_host(const pion_gpu_config *cfg, int axis, int nfields, const pion_gpu_proj_field *fields,
-                              const double *A, double *img)
-{
-  if (!cfg || !A || !img) return PION_GPU_EINVAL;
-  const pion::GridDesc g = grid_desc(*cfg);
-  if (pion::proj_refused_grid(g, axis) || pion::proj_refused_fields(pion::out_cfg(*cfg), nfields, fields)) return PION_GPU_EINVAL;
-  project_on_host(g, pion::out_cfg(*cfg), axis, nfields, fields, A, img);
-  return 0;
-}
-// proj_column_part / abel_column_part: this grid's part added into img = [nfields][NJ_global][NI_global] (in/out)
-int pion_host_project_part_on_host(const pion_gpu_config *cfg, int axis, int nfields, const pion_gpu_proj_field *fields,
-                                   const pion_gpu_proj_part *part, const double *A, double *img)
-{
-  if (!A || pion_host_project_part_refused(cfg, axis, nfields, fields, part, img)) return PION_GPU_EINVAL;
-  const pion::ProjPart pp = {part->plane_lo, part->global_planes, part->last ? 1 : 0, part->global_xmin};
-  project_part_on_host(grid_desc(*cfg), pion::out_cfg(*cfg), axis, nfields, fields, pp, A, img);
-  return 0;
-}
+  return f.commit(rc);
 }
 
 }  // namespace pion_host

@@ -18,7 +18,7 @@
 // chunk of whole planes at a time through the PIONRAW2 writer's loop (stream_runs): host memory is two chunks.  A
 // backend without those entries (the test oracle's table) downloads array 0 whole and evaluates the same
 // dev_output.h functions in a host loop.  Every rank writes its own file; nothing is collective.  The file is written
-// under a ".part" name and renamed.
+// under a ".part" name and renamed (out_file.h).
 //
 // Read back (sim_control_gpu::read_fits, the reference's DataIOFits::ReadHeader / ReadData / read_fits_image,
 // dataio_fits.cpp:340-385, 433-548, 865-929), again without CFITSIO.  The reader walks 2880-byte blocks and
@@ -38,17 +38,9 @@
 // -1e99, which fail the restart.  A backend without that entry takes the same dev_output.h functions in a host loop
 // (fits_convert_run) and goes through upload.
 //
-// Ray-traced column densities (sim_control_gpu::write_columns, defined in fits_io.cpp; the rules:
-// pion_amd/csrc/dev_raytrace.h) use the same writer too: the same primary header with RT_Nsources and, per source n,
-// RT_position_<n>_<d>, RT_at_infty_<n>, RT_Opacity__<n>, RT_Tau_var__<n> appended, then per source the images
-// Col_Src_<n>_T0 and DCol_Src_<n>_T0 of the on-grid cells, traced on the device and streamed image after image, a chunk
-// of planes at a time (backend entries raytrace / rt_count / columns_to_host_begin), or by pion_gpu_raytrace_host on a
-// downloaded array where the table has no such entries.
-// Projected images (sim_control_gpu::write_projection, defined in fits_io.cpp; the rules: pion_amd/csrc/dev_project.h)
-// use the same writer: the same primary header with pion_proj_axis and pion_proj_<n>_{a,var,coef,b} appended, then one
-// two-dimensional IMAGE extension per field (NAXIS1 = NI, NAXIS2 = NJ, EXTNAME = the field's name).  The images come
-// from the backend's project_* entries; a table without them downloads array 0 and runs dev_project.h's functions in a
-// host loop.  An image is small, so it is written whole, under a ".part" name and renamed.
+// The other files of this format -- projected images (projection_io.cpp) and ray-traced column densities
+// (columns_io.cpp) -- have the same shape: one primary header, N image headers of one length and N data units of one
+// length.  fits_layout states where each lies and starts a file of that shape.
 #ifndef PION_FITS_IO_H
 #define PION_FITS_IO_H
 
@@ -56,6 +48,7 @@
 #include <vector>
 
 #include "../../include/pion_host.h"
+#include "out_file.h"
 #include "snapshot_io.h"
 
 namespace pion_host {
@@ -63,6 +56,21 @@ namespace pion_host {
 // the header blocks of the primary HDU for these parameters, and of one image extension: multiples of 2880 bytes
 std::string fits_primary_header(const std::vector<snapshot_param> &params);
 std::string fits_image_header(const char *extname, int ndim, const long *naxis);
+
+// A file of one primary header and ext.size() image extensions, each with run_bytes of data zero-padded to a multiple
+// of 2880: where the pieces lie.  Every extension header must have the same length (fits_image_header gives that for
+// one ndim): the one stride from image to image rests on it, and the constructor checks it
+struct fits_layout {
+  fits_layout(const std::string &primary, const std::vector<std::string> &ext, long run_bytes);
+  long header_at(long i) const { return (long)primary.size() + i * stride; }
+  long data_at(long i) const { return header_at(i) + (stride - data_padded); }
+  // The file at its full length first -- what no write covers, the padding after each data unit, reads as zero bytes
+  // --, then every header.  The data follow.  0 or PION_GPU_EINVAL, as PartFile::write
+  int start(PartFile &f) const;
+  const std::string &primary;
+  const std::vector<std::string> &ext;
+  const long data_padded, stride, total;   // stride: from one image's header (or data) to the next one's
+};
 
 // Header of a FITS file of this writer's kind: hd as snapshot_read_header fills it (info.data_offset = 0).  image_off
 // (may be null): per primitive variable, the byte its image's data unit starts at, or -1 where the file has no image

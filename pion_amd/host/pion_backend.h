@@ -80,7 +80,7 @@ typedef struct pion_backend {
   int (*fits_from_host)(void *handle, int plane_lo, int plane_hi, int slot, int (*fill)(void *ctx, double *host),
                         void *ctx);
   int (*fits_read_status)(void *handle, long *nbad);
-  /* Projected images (fits_io.h; the rules: pion_amd/csrc/dev_project.h): the images of pion_gpu_project, native
+  /* Projected images (projection_io.cpp; the rules: pion_amd/csrc/dev_project.h): the images of pion_gpu_project, native
    * doubles [nfields][NJ][NI].  These two entries are read ONLY inside sim_control_gpu::write_projection: a caller
    * that never writes a projection may hand the loop a table that ends before them.  Both NULL: the writer takes
    * array 0 through download and runs dev_project.h's functions in a host loop.
@@ -98,7 +98,7 @@ typedef struct pion_backend {
   long (*project_part_count)(void *handle, int axis, int nfields, const pion_gpu_proj_part *part);
   int (*project_part_to_host)(void *handle, int axis, int nfields, const pion_gpu_proj_field *fields,
                               const pion_gpu_proj_part *part, double *host);
-  /* Ray-traced column densities (fits_io.h; the rules: pion_amd/csrc/dev_raytrace.h).  These four entries are read ONLY
+  /* Ray-traced column densities (columns_io.cpp; the rules: pion_amd/csrc/dev_raytrace.h).  These four entries are read ONLY
    * inside sim_control_gpu::add_rt_source and write_columns: a caller that never adds a radiation source may hand the
    * loop a table that ends before them.  All NULL: the sim keeps the sources itself, and the writer takes array 0
    * through download and runs pion_gpu_raytrace_host on it.

@@ -15,6 +15,7 @@
 #ifndef PION_SIM_CONTROL_GPU_H
 #define PION_SIM_CONTROL_GPU_H
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -24,6 +25,7 @@
 namespace pion_host {
 
 struct snapshot_param;   // snapshot_io.h
+class PartFile;          // out_file.h
 class slab_comm;   // slab_comm.h: slab_comm_rccl (RCCL over xGMI) or slab_comm_shm (host-staged)
 
 // the slice of SimParams (sim_params.h:200-285) the time loop itself reads/writes
@@ -93,7 +95,7 @@ class sim_control_gpu {
   int write_fits(const char *path);
   // the PIONRAW2 file (snapshot_io.h) of this sim's on-grid cells; completes a halo exchange in flight first
   int write_snapshot(const char *path);
-  // Projected images (fits_io.h; the rules: pion_amd/csrc/dev_project.h, after the reference's
+  // Projected images (projection_io.cpp; the rules: pion_amd/csrc/dev_project.h, after the reference's
   // analysis/projection/perp_projection.cpp:404-487): a FITS file with write_fits' primary header plus pion_proj_axis
   // and per field pion_proj_<n>_{a,var,coef,b}, and one double-precision IMAGE extension [NJ][NI] per field, EXTNAME =
   // the field's name, in units of code * dx.  Projected on the device (backend entries project_*), or -- a table
@@ -107,7 +109,7 @@ class sim_control_gpu {
   // digits>.fits (the one file of a slab run: rank 0000); nfields 0 turns it off again.  The same refusals, made here.  Cadence and time steps are untouched
   int set_projection_output(int axis, int nfields, const pion_gpu_proj_field *fields);
   std::string projection_name(long step) const;
-  // Ray-traced column densities (pion_gpu_raytrace; the rules: pion_amd/csrc/dev_raytrace.h, after the reference's
+  // Ray-traced column densities (columns_io.cpp; pion_gpu_raytrace; the rules: pion_amd/csrc/dev_raytrace.h, after the reference's
   // raytracer_USC).  add_rt_source: Add_Source for one radiation source -- on the backend's handle (entry
   // add_rt_source), or, a table without it, kept here; pos_used (PION_MAX_DIM doubles, may be null): the cell vertex a
   // finite source was moved to.  write_columns: a FITS file with write_fits' primary header plus RT_Nsources and, per
@@ -170,15 +172,20 @@ class sim_control_gpu {
   std::vector<pion_gpu_rt_source> rt_sources_, rt_moved_;   // add_rt_source: the sources as given, and at the positions used
   bool rt_on_backend_ = false;                   // they live on the backend's handle too
   bool column_output_ = false;                   // set_column_output
+  // columns_io.cpp
   int columns_refused(const char *who);
+  // projection_io.cpp
   bool projection_collective() const;   // one rank of a slab run whose images are assembled along the ranks
   int project_images(int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part *part, long n, double *img);
   int relay_part(int rc, int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part &part,
                  std::vector<double> &img);
   int projection_refused(int axis, int nfields, const pion_gpu_proj_field *fields, const char *who);
-  // snapshot_io.cpp: what both writers share
+  // snapshot_io.cpp: what the four writers share (the file itself: out_file.h)
+  int path_refused(const char *who, const char *path);
   int snapshot_params(std::vector<snapshot_param> &out, long &slab_n);
-  int stream_runs(int fd, bool fits, int nrun, long nloc, long plane, long off, long stride, const char *who);
+  int writer_params(const char *who, std::vector<snapshot_param> &out, long &slab_n);
+  int stream_jobs(long njob, const std::function<int(long, int)> &begin, const std::function<int(long, const double *)> &put);
+  int stream_runs(PartFile &f, bool fits, int nrun, long nloc, long plane, long off, long stride, const char *who);
   // and what both restarts share: everything but the header reader and the meaning of an element
   int read_files(const char *const *paths, int npaths, bool fits);
 };

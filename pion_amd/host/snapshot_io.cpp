@@ -14,6 +14,7 @@
 #include <sstream>
 
 #include "fits_io.h"
+#include "out_file.h"
 #include "sim_control_gpu.h"
 #include "slab_comm.h"
 
@@ -49,13 +50,6 @@ int bc_type(const std::string &s)
 }
 const char *const BC_KEYS[6] = {"BC_XN", "BC_XP", "BC_YN", "BC_YP", "BC_ZN", "BC_ZP"};
 
-std::string fmt_d(double x)
-{
-  char b[64];
-  snprintf(b, sizeof b, "%.17g", x);
-  return b;
-}
-
 // geometry of the on-grid data of one sim / one file
 struct Shape {
   int sa;            // slab axis (-1: 1-D, the one row is the one plane)
@@ -90,17 +84,6 @@ struct Fd {
     if (fd >= 0) close(fd);
   }
 };
-
-// planes per chunk: the largest number that fits CHUNK_BYTES, at least one; PION_SNAPSHOT_CHUNK_PLANES forces it
-long chunk_planes(long doubles_per_plane_all_vars, long planes)
-{
-  long c = CHUNK_BYTES / (long)sizeof(double) / std::max(1L, doubles_per_plane_all_vars);
-  if (const char *e = getenv("PION_SNAPSHOT_CHUNK_PLANES")) {
-    const long f = atol(e);
-    if (f > 0) c = f;
-  }
-  return std::max(1L, std::min(c, planes));
-}
 
 bool get(const snapshot_header &hd, const char *key, std::string &v, std::string &err)
 {
@@ -154,16 +137,14 @@ bool get_int(const snapshot_header &hd, const char *key, int &out, std::string &
 
 }  // namespace
 
-int full_pwrite(int fd, const void *p, size_t n, off_t off)
+long chunk_planes(long doubles_per_plane_all_runs, long planes)
 {
-  const char *c = (const char *)p;
-  while (n > 0) {
-    const ssize_t w = pwrite(fd, c, n, off);
-    if (w < 0 && errno == EINTR) continue;
-    if (w <= 0) return -1;
-    c += w, off += w, n -= (size_t)w;
+  long c = CHUNK_BYTES / (long)sizeof(double) / std::max(1L, doubles_per_plane_all_runs);
+  if (const char *e = getenv("PION_SNAPSHOT_CHUNK_PLANES")) {
+    const long f = atol(e);
+    if (f > 0) c = f;
   }
-  return 0;
+  return std::max(1L, std::min(c, planes));
 }
 
 bool equalD(const double a, const double b)
@@ -325,8 +306,17 @@ int global_view(const sim_control_gpu &sim, Global &G, std::string &err)
 }
 }  // namespace
 
+// how every writer opens: the text of the last failure cleared, a null or empty path refused
+int sim_control_gpu::path_refused(const char *who, const char *path)
+{
+  io_error_.clear();
+  if (path && *path) return 0;
+  io_error_ = std::string(who) + ": no path";
+  return PION_GPU_EINVAL;
+}
+
 // every parameter a file of this sim carries, in snapshot_header_keys() order (pion_data_offset, the PIONRAW2 file's
-// own, excepted): the one list both writers use
+// own, excepted): the one list every writer uses
 int sim_control_gpu::snapshot_params(std::vector<snapshot_param> &out, long &slab_n)
 {
   Global G;
@@ -370,51 +360,60 @@ int sim_control_gpu::snapshot_params(std::vector<snapshot_param> &out, long &sla
   return 0;
 }
 
-// The streamed write loop of both files.  The planes [0, nloc) leave the backend a chunk of whole planes at a time:
-// pack and copy of chunk i+1 are enqueued while chunk i is pwrite()n, one run per variable (PIONRAW2) or image (FITS),
-// run r of a chunk at off + r * stride + (its first plane's byte offset inside a run).  A chunk is the largest number
-// of planes whose runs fit one staging slot.
-int sim_control_gpu::stream_runs(int fd, bool fits, int nrun, long nloc, long plane, long off, long stride, const char *who)
+// what every writer does before it reads the state: the parameters, and a halo exchange in flight completed
+int sim_control_gpu::writer_params(const char *who, std::vector<snapshot_param> &out, long &slab_n)
 {
-  long (*const count)(void *, int) = fits ? be_->fits_count : be_->ongrid_count;
-  auto begin = [&](long lo, long hi, int slot) {
-    return fits ? be_->fits_to_host_begin(h_, (int)lo, (int)hi, slot) : be_->ongrid_to_host_begin(h_, 0, (int)lo, (int)hi, slot);
-  };
-  const long cp = chunk_planes(count(h_, 1), nloc);
-  const long nchunk = (nloc + cp - 1) / cp;
-  int rc = begin(0, std::min(cp, nloc), 0);
-  for (long i = 0; i < nchunk && !rc; i++) {
-    const long a = i * cp, b = std::min(nloc, a + cp);
-    if (i + 1 < nchunk) rc = begin(b, std::min(nloc, b + cp), (int)((i + 1) & 1));
+  if (int rc = snapshot_params(out, slab_n)) return rc;
+  const int rc = finish_halo();
+  if (rc) io_error_ = std::string(who) + ": finish_halo failed";
+  return rc;
+}
+
+// The streamed loop of every writer whose data leave the backend through its two staging slots: job after job, begin(job,
+// slot) enqueues the pack and the copy of one, ongrid_to_host_end waits for it, put(job, src) writes it.  Job + 1 is
+// begun BEFORE job is ended: its pack and copy run while this code writes -- the overlap the slots exist for
+int sim_control_gpu::stream_jobs(long njob, const std::function<int(long, int)> &begin,
+                                 const std::function<int(long, const double *)> &put)
+{
+  int rc = begin(0, 0);
+  for (long job = 0; job < njob && !rc; job++) {
+    if (job + 1 < njob) rc = begin(job + 1, (int)((job + 1) & 1));
     const double *src = nullptr;
-    if (!rc) rc = be_->ongrid_to_host_end(h_, (int)(i & 1), &src);
-    if (rc) {
-      io_error_ = std::string(who) + ": staging the planes failed: " + last_error();
-      break;
-    }
-    const size_t n = (size_t)(b - a) * plane;
-    for (int v = 0; v < nrun && !rc; v++)
-      if (full_pwrite(fd, src + (size_t)v * n, n * sizeof(double), (off_t)(off + (long)v * stride + a * plane * (long)sizeof(double))))
-        rc = PION_GPU_EINVAL;
+    if (!rc) rc = be_->ongrid_to_host_end(h_, (int)(job & 1), &src);
+    if (!rc) rc = put(job, src);
   }
+  return rc;
+}
+
+// The planes [0, nloc) of a snapshot, chunk-major: a job is a chunk of whole planes and holds all the runs, one per
+// variable (PIONRAW2) or image (FITS), run r of a chunk at off + r * stride + (its first plane's byte offset inside a
+// run).  A chunk is the largest number of planes whose runs fit one staging slot.
+int sim_control_gpu::stream_runs(PartFile &f, bool fits, int nrun, long nloc, long plane, long off, long stride, const char *who)
+{
+  const long cp = chunk_planes((fits ? be_->fits_count : be_->ongrid_count)(h_, 1), nloc);
+  auto begin = [&](long i, int slot) {
+    const long a = i * cp, b = std::min(nloc, a + cp);
+    return fits ? be_->fits_to_host_begin(h_, (int)a, (int)b, slot) : be_->ongrid_to_host_begin(h_, 0, (int)a, (int)b, slot);
+  };
+  auto put = [&](long i, const double *src) {
+    const long a = i * cp;
+    const size_t n = (size_t)(std::min(nloc, a + cp) - a) * plane;
+    int rc = 0;
+    for (int v = 0; v < nrun && !rc; v++)
+      rc = f.write(src + (size_t)v * n, n * sizeof(double), off + (long)v * stride + a * plane * (long)sizeof(double));
+    return rc;
+  };
+  const int rc = stream_jobs((nloc + cp - 1) / cp, begin, put);
   if (rc && io_error_.empty()) io_error_ = std::string(who) + ": staging the planes failed: " + last_error();
   return rc;
 }
 
 int sim_control_gpu::write_snapshot(const char *path)
 {
-  io_error_.clear();
-  if (!path || !*path) {
-    io_error_ = "write_snapshot: no path";
-    return PION_GPU_EINVAL;
-  }
+  if (int rc = path_refused("write_snapshot", path)) return rc;
   std::vector<snapshot_param> params;
   long nloc = 0;
-  if (int rc = snapshot_params(params, nloc)) return rc;
-  if (int rc = finish_halo()) {
-    io_error_ = "write_snapshot: finish_halo failed";
-    return rc;
-  }
+  if (int rc = writer_params("write_snapshot", params, nloc)) return rc;
   const Shape s = shape_of(cfg);
   const long plane = s.plane();
 
@@ -425,19 +424,12 @@ int sim_control_gpu::write_snapshot(const char *path)
   head += "pion_data_offset " + std::to_string(off) + "\n";
   head.resize((size_t)off, '\n');
 
-  // written under a temporary name and renamed: a checkpoint that replaces an older one is whole or absent
-  const std::string tmp = std::string(path) + ".part";
-  Fd f;
-  f.fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-  if (f.fd < 0) {
-    io_error_ = "write_snapshot: cannot create " + tmp + ": " + strerror(errno);
-    return PION_GPU_EINVAL;
-  }
-  int rc = 0;
-  if (full_pwrite(f.fd, head.data(), head.size(), 0)) rc = PION_GPU_EINVAL;
+  PartFile f("write_snapshot", path, io_error_);
+  if (!f.ok()) return PION_GPU_EINVAL;
+  int rc = f.write(head.data(), head.size(), 0);
   const size_t run = (size_t)nloc * plane;   // doubles of one variable in the file
   if (!rc && be_->ongrid_to_host_begin && be_->ongrid_to_host_end && be_->ongrid_count)
-    rc = stream_runs(f.fd, false, cfg.nvar, nloc, plane, off, (long)(run * sizeof(double)), "write_snapshot");
+    rc = stream_runs(f, false, cfg.nvar, nloc, plane, off, (long)(run * sizeof(double)), "write_snapshot");
   else if (!rc) {
     // no streaming entries: the whole array with its ghosts, stripped here
     const long nb = cfg.nbc, nxa = cfg.ng[0] + 2 * nb, nya = (cfg.ndim >= 2) ? cfg.ng[1] + 2 * nb : 1,
@@ -454,18 +446,10 @@ int sim_control_gpu::write_snapshot(const char *path)
           memcpy(&R[o], &A[c0], (size_t)cfg.ng[0] * sizeof(double));
           o += cfg.ng[0];
         }
-      if (full_pwrite(f.fd, R.data(), run * sizeof(double), off + (off_t)((size_t)v * run * sizeof(double)))) rc = PION_GPU_EINVAL;
+      rc = f.write(R.data(), run * sizeof(double), off + (long)((size_t)v * run * sizeof(double)));
     }
   }
-  if (rc && io_error_.empty()) io_error_ = "write_snapshot: writing " + tmp + " failed: " + strerror(errno);
-  close(f.fd);
-  f.fd = -1;
-  if (!rc && rename(tmp.c_str(), path) != 0) {
-    io_error_ = std::string("write_snapshot: cannot rename to ") + path + ": " + strerror(errno);
-    rc = PION_GPU_EINVAL;
-  }
-  if (rc) unlink(tmp.c_str());
-  return rc;
+  return f.commit(rc);
 }
 
 namespace {

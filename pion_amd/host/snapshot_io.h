@@ -21,9 +21,10 @@
 // oracle's table) goes through its whole-array download / upload, ghosts stripped / embedded here.
 //
 // The members sim_control_gpu::write_snapshot / read_snapshot are defined in snapshot_io.cpp, and with them what the
-// FITS writer and reader (fits_io.h) share: the list of parameters (snapshot_params), the streamed write loop
-// (stream_runs), the checks of a header (snapshot_header_from_kv) and the whole restart but the meaning of a file
-// element (read_files).
+// other writers (fits_io.cpp, projection_io.cpp, columns_io.cpp) and the FITS reader share: how a writer opens
+// (path_refused, writer_params with the list of parameters, snapshot_params), the streamed write loop (stream_jobs; its
+// chunk-major caller stream_runs; the size of a chunk, chunk_planes), the checks of a header (snapshot_header_from_kv)
+// and the whole restart but the meaning of a file element (read_files).  The file a writer writes into: out_file.h.
 #ifndef PION_SNAPSHOT_IO_H
 #define PION_SNAPSHOT_IO_H
 
@@ -62,8 +63,9 @@ struct snapshot_param {
   char type;
 };
 
-// all n bytes at offset off, or -1
-int full_pwrite(int fd, const void *p, size_t n, off_t off);
+// planes per chunk of a streamed file: the largest number that fits one 64 MiB staging slot, at least one and at most
+// `planes`; PION_SNAPSHOT_CHUNK_PLANES in the environment forces it
+long chunk_planes(long doubles_per_plane_all_runs, long planes);
 
 }  // namespace pion_host
 #endif
