@@ -21,7 +21,8 @@ def _cpu(cfg):
     return CpuSim(cfg, "orc")
 
 
-def run_pair(cfg, P, nsteps, strict=True, tol=0.0, first_dt_limit=None, setup=None):
+def run_pair(cfg, P, nsteps, strict=True, tol=0.0, first_dt_limit=None, setup=None, after=None):
+    """after(g): called with the device handle once the last step has been compared, before the handles close"""
     with _gpu(cfg) as g, _cpu(cfg) as o:
         if setup:
             setup(g)
@@ -48,6 +49,8 @@ def run_pair(cfg, P, nsteps, strict=True, tol=0.0, first_dt_limit=None, setup=No
             else:
                 scale = np.abs(b).reshape(cfg.nvar, -1).max(axis=1).reshape(-1, 1, 1, 1) + 1e-300
                 assert np.max(np.abs(a - b) / scale) <= tol, np.max(np.abs(a - b) / scale)
+        if after:
+            after(g)
 
 
 HD_SOLVERS = [abi.FLUX_RSroe, abi.FLUX_RSroe_pv, abi.FLUX_FVS, abi.FLUX_RS_HLL]

@@ -5,7 +5,8 @@ k_stage_rows2 runs.  Here nx = 70 (one full tile + an 8-cell remainder) and nx =
 6-cell remainder), ny not a multiple of the rows per wavefront, and data with gradients across every
 tile seam.  Strict build: bit-exact.  Fast (benchmarked) build: cell-wise within 1e-11 of each
 variable's scale per step, on problems where the reference itself is well conditioned
-(tests/test_reference_conditioning.py)."""
+(tests/test_reference_conditioning.py).
+Every 2-D instance (Cartesian, cylindrical, cell-per-thread) at the smallest such shape: test_gpu_instances_2d.py."""
 import numpy as np
 import pytest
 
