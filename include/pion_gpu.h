@@ -277,7 +277,8 @@ int pion_gpu_project_part(void *handle, int which, int axis, int nfields, const 
  *   pion_gpu_raytrace_host  host only: the rules of dev_raytrace.h in a host loop over P_soa (the layout of
  *                           pion_gpu_upload, ghosts included; only on-grid cells are read) into col and dcol.
  *   pion_gpu_rt_refused     host only: the text with which the calls above refuse (cfg, src), or NULL.
- * EINVAL and a text: 1-D and spherical grids; a handle with a PION_BC_SLAB face; an opacity rule other than
+ * EINVAL and a text: 1-D and spherical grids; a handle with a PION_BC_SLAB face (a slab of a decomposed run is traced
+ * through the part calls below); an opacity rule other than
  * PION_RT_OPACITY_TOTAL, MINUS, TRACER (VSHELL, HALPHA, RR, HHE and MP need a microphysics object); opacity_var outside
  * the tracers (MINUS, TRACER); more than PION_MAX_RT_SOURCES sources; a direction that is not a face of the grid; a
  * position that is not finite; an unknown id, `what` or plane range; a NULL pointer. */
@@ -301,6 +302,50 @@ int pion_gpu_rt_plan(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, 
 int pion_gpu_raytrace_host(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const double *P_soa, double *col,
                            double *dcol);
 const char *pion_gpu_rt_refused(const pion_gpu_config *cfg, const pion_gpu_rt_source *src);
+/* The ray tracer in a slab run, columns handed from rank to rank (dev_raytrace.h: "a part", rt_role).  The handle
+ * holds the planes [plane_lo, plane_lo + n) of the slab axis (z in 3-D, y in 2-D; n = the handle's own ng of that axis)
+ * out of global_planes; global_xmin is the whole domain's xmin of that axis.  One plane of col per internal face and
+ * source crosses: pion_gpu_rt_count(handle, 1) doubles.  Traced in the order of the chain -- receive, trace, send, from
+ * the rank that holds the source outwards -- the ranks' arrays are == the planes of one handle of the whole domain.
+ * Received columns are not clamped at 0 (the reference does, RT_MPI_boundaries.cpp:352,364).
+ *   pion_gpu_add_rt_source_part  pion_gpu_add_rt_source for a part: accepted on a handle with PION_BC_SLAB faces of the
+ *                           slab axis, and on a whole-domain handle (plane_lo = 0, global_planes = n), where it equals
+ *                           pion_gpu_add_rt_source.  pos and pos_used are positions of the WHOLE domain; the vertex
+ *                           along the slab axis is found from global_xmin on every rank.
+ *   pion_gpu_rt_chain       host only: the rank's role for `src`.  *recv_side = PION_RT_RECV_NONE, _BELOW or _ABOVE;
+ *                           *send_lo, *send_hi = 1 where the rank's lowest / highest own plane goes to the neighbour
+ *                           below / above.  A source at infinity across the slab axis: no message at all.
+ *   pion_gpu_raytrace_part  traces source id alone from array `which`.  dface_in: the plane received (DEVICE memory;
+ *                           may be NULL where recv_side is NONE, is not read there); dface_out_lo, dface_out_hi: DEVICE
+ *                           buffers that take the rank's lowest and highest own plane of col afterwards (either may be
+ *                           NULL: not written).  Enqueued on the compute stream, returns at once.
+ *   pion_gpu_raytrace_host_part  host only: the same functions in a host loop; face_in as above, in host memory.
+ *   pion_gpu_rt_plan_part   host only: for a finite source the launches of the tiled kernel on this part (tile-levels
+ *                           that hold tiles), the workgroups of one launch -- the tiles of [klo / tile, khi / tile] per
+ *                           axis and side, klo and khi the nearest and farthest on-grid cell -- and what that count
+ *                           would be with tiles counted from the vertex.  A source at infinity: 1, 0, 0.
+ *   pion_gpu_rt_part_refused  host only: the text with which the calls above refuse (cfg, src, part), or NULL.
+ * pion_gpu_raytrace refuses a handle that has part sources and a slab face: it cannot know the faces.
+ * EINVAL and a text: everything pion_gpu_add_rt_source refuses except the slab face of the slab axis; plane_lo < 0;
+ * plane_lo + n > global_planes; a global_xmin that is not finite; a null part; a NULL dface_in where a plane is received;
+ * pion_gpu_raytrace_part for a source that was added without a part on a handle with a slab face. */
+#define PION_RT_RECV_NONE 0
+#define PION_RT_RECV_BELOW 1
+#define PION_RT_RECV_ABOVE 2
+typedef struct pion_gpu_rt_part {
+  int plane_lo, global_planes;
+  double global_xmin;
+} pion_gpu_rt_part;
+int pion_gpu_add_rt_source_part(void *handle, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part, int *id,
+                                double *pos_used);
+int pion_gpu_rt_chain(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part,
+                      int *recv_side, int *send_lo, int *send_hi);
+int pion_gpu_raytrace_part(void *handle, int which, int id, const void *dface_in, void *dface_out_lo, void *dface_out_hi);
+int pion_gpu_raytrace_host_part(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part,
+                                const double *P_soa, const double *face_in, double *col, double *dcol);
+int pion_gpu_rt_plan_part(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part,
+                          long *launches, long *workgroups, long *workgroups_from_vertex);
+const char *pion_gpu_rt_part_refused(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part);
 /* adopt caller-owned device buffers (e.g. torch tensors) instead of internal ones;
  * both must hold nvar*ncell_all doubles */
 int pion_gpu_bind_device_state(void *handle, void *dP, void *dPh);

@@ -137,9 +137,17 @@ int pion_host_sim_set_projection_output(void *sim, int axis, int nfields, const 
  * pion_host_sim_set_column_output: from now on (on != 0) every regular output of pion_host_sim_time_int is accompanied
  *   by <base>_cols_<rank, 4 digits>.<step, 8 digits>.fits; on = 0 turns that off.  Cadence, the time-step clip,
  *   checkpoints, every dt and the regular outputs themselves are untouched: tracing only reads the state.
+ * One rank of a slab run (pion_host_sim_set_slab_extent AND a communicator of more than one rank that relays both ways,
+ *   both set before the first source): the three calls are collective.  Sources are given at positions of the WHOLE
+ *   domain, and pos_used is that position on every rank.  write_columns takes the sources in id order: receive the plane
+ *   of col the rank's role names (pion_gpu_rt_chain), trace, send the own lowest / highest plane on -- one plane per
+ *   internal face and source, away from the source.  Every rank writes its own file (<base>_cols_<rank>...) with its own
+ *   planes: the header of its FITS snapshot plus the RT_* keys, the images == those planes of the single-rank file.  A
+ *   rank that fails passes the failure on and the ranks then agree: every rank returns EINVAL, no file appears, no rank
+ *   blocks.
  * EINVAL and a text, never an exit: everything pion_gpu_add_rt_source refuses; no source; a path that cannot be created;
- * a sim that is one rank of several (a slab extent or a communicator of more than one rank): the columns of a slab run
- * would have to be handed from rank to rank. */
+ * one rank of a slab run with only one of a slab extent and such a communicator, or one that became a rank after its
+ * sources were added. */
 int pion_host_sim_add_rt_source(void *sim, const pion_gpu_rt_source *src, int *id, double *pos_used);
 int pion_host_sim_write_columns(void *sim, const char *path);
 int pion_host_sim_set_column_output(void *sim, int on);

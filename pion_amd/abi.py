@@ -95,6 +95,23 @@ def rt_source(src=None, pos=(0.0, 0.0, 0.0), at_infinity=0, dir=0, opacity=RT_OP
     return s
 
 
+# a rank's role in the chain of a slab run's trace (pion_gpu_rt_chain): the side a plane is received from
+RT_RECV_NONE, RT_RECV_BELOW, RT_RECV_ABOVE = 0, 1, 2
+
+
+class RtPart(C.Structure):
+    """pion_gpu_rt_part (include/pion_gpu.h): a rank's planes of the slab axis in a slab run's trace"""
+    _fields_ = [("plane_lo", C.c_int), ("global_planes", C.c_int), ("global_xmin", C.c_double)]
+
+
+def rt_part(part):
+    """an abi.RtPart from one, or from (plane_lo, global_planes, global_xmin)"""
+    if isinstance(part, RtPart):
+        return part
+    lo, n, xmin = part
+    return RtPart(int(lo), int(n), float(xmin))
+
+
 class PionGpuConfig(C.Structure):
     _fields_ = [
         ("ndim", C.c_int), ("nvar", C.c_int), ("ntracer", C.c_int), ("eqntype", C.c_int),

@@ -16,11 +16,16 @@
 //      2627-2682): rt_col2cell_2d / rt_col2cell_3d give the column TO the cell and the path length ds through it from
 //      the finished columns of up to four neighbours one step nearer the source along the axis of the largest
 //      distance.  A neighbour that is not an on-grid cell contributes 0 (ProcessCell 887-898 and the null-pointer
-//      branches of col2cell_*): the caller's `colat` returns 0.0 there.
+//      branches of col2cell_*): the caller's `colat` returns 0.0 there.  One exception, in a part of a decomposed run
+//      (rt_role): a cell one plane beyond the slab face that looks towards the source, inside the grid on the other
+//      axes, gives the column the neighbouring rank handed over -- unclamped (the reference clamps what it receives at
+//      0, RT_MPI_boundaries.cpp:352,364; here a decomposed run gives the bits of the single grid).  A cell of that
+//      plane that is off the grid on another axis still gives 0.0.
 // ---- the column THROUGH the cell (ProcessCell 855-1057): rt_dcol, ds rho, ds rho (1 - y), ds rho y.
 //      col = col_to_cell + dcol is what CI.get_col returns afterwards.
 // ---- a source at infinity (trace_parallel_rays 695-792): ds = dx and col is the running sum along the axis from the
-//      face the source lies beyond, the additions one after the other in ray order: col = col_before + dcol.
+//      face the source lies beyond, the additions one after the other in ray order: col = col_before + dcol.  In a
+//      part, along the slab axis, the sum starts from the plane handed over instead of 0.
 // ---- the dependency.  With k_a = (d_a - 1) / 2 the cells of one level L = sum_a k_a read only cells of lower levels
 //      in their own octant: rt_plan_of describes the levels and, for tiles of RT_TILE cells counted from the source
 //      vertex outwards (tile index t_a = k_a / tile_a), the tile-levels T = sum_a t_a with the same property.
@@ -50,14 +55,16 @@ struct RtSrc {
   double taumin;    // set_TauMin_for_source, 1323-1336
 };
 
-// ---- what is refused: null, or the text of the refusal
-inline const char *rt_refused(const pion_gpu_config &c, const pion_gpu_rt_source *s)
+// ---- what is refused: null, or the text of the refusal.  slab_ok: the caller describes the handle as a part of a
+// decomposed domain (RtPart below), so a PION_BC_SLAB face of the slab axis is no reason to refuse.
+inline const char *rt_refused_as(const pion_gpu_config &c, const pion_gpu_rt_source *s, const bool slab_ok)
 {
   if (!s) return "raytrace: no source";
   if (c.ndim == 1 || c.coord_sys == 3) return "raytrace: 1-D and spherical grids are not traced";
   if (c.ndim < 2 || c.ndim > 3) return "raytrace: a grid has 2 or 3 dimensions";
   for (int d = 0; d < 2 * c.ndim; d++)
-    if (c.bc_type[d] == PION_BC_SLAB) return "raytrace: a slab of a decomposed run is not traced (columns are not handed from rank to rank)";
+    if (c.bc_type[d] == PION_BC_SLAB && !(slab_ok && d / 2 == c.ndim - 1))
+      return "raytrace: a slab of a decomposed run is not traced (columns are not handed from rank to rank)";
   if (s->opacity < PION_RT_OPACITY_TOTAL || s->opacity > PION_RT_OPACITY_TRACER)
     return "raytrace: the opacity rule needs a microphysics object (TOTAL, MINUS and TRACER are covered)";
   if (s->opacity != PION_RT_OPACITY_TOTAL && (s->opacity_var < 0 || s->opacity_var >= c.ntracer))
@@ -69,6 +76,19 @@ inline const char *rt_refused(const pion_gpu_config &c, const pion_gpu_rt_source
     for (int a = 0; a < c.ndim; a++)
       if (!(std::fabs(s->pos[a]) <= 1.0e100)) return "raytrace: the position of a finite source is finite";
   }
+  return nullptr;
+}
+inline const char *rt_refused(const pion_gpu_config &c, const pion_gpu_rt_source *s) { return rt_refused_as(c, s, false); }
+
+// a part: the handle holds the planes [plane_lo, plane_lo + n) of the slab axis (z in 3-D, y in 2-D; n = the handle's own
+// ng of that axis) out of global_planes, and the whole domain starts at global_xmin along that axis.
+inline const char *rt_part_refused(const pion_gpu_config &c, const pion_gpu_rt_source *s, const pion_gpu_rt_part *part)
+{
+  if (const char *e = rt_refused_as(c, s, true)) return e;
+  if (!part) return "raytrace: no part";
+  if (part->plane_lo < 0 || part->plane_lo + (long)c.ng[c.ndim - 1] > part->global_planes)
+    return "raytrace: the part's planes lie outside the whole domain";
+  if (!(std::fabs(part->global_xmin) <= 1.0e100)) return "raytrace: the part's global_xmin is not finite";
   return nullptr;
 }
 
@@ -103,7 +123,12 @@ inline double rt_centre_on_vertex(const double pos_in, const double xmin, const 
 
 // add_source_to_list (1217-1314) without the cell pointer: the moved position and the kernel's view of the source.
 // cell_interface::get_ipos_vec (cell_interface.cpp:553-571) gives the integer position.
-inline RtSrc rt_make_source(const pion_gpu_config &c, const pion_gpu_rt_source &s, double pos_used[3])
+// A part (null: the grid of c is the whole domain): the position is one of the WHOLE domain.  Along the slab axis the
+// vertex is found from global_xmin, exactly as on the whole grid, and then shifted by 2 plane_lo into the integer units
+// of the slab; it is never found from the slab's own xmin, so that no two ranks can settle on different vertices.
+// pos_used is the whole-domain position on every rank.
+inline RtSrc rt_make_source(const pion_gpu_config &c, const pion_gpu_rt_source &s, double pos_used[3],
+                            const pion_gpu_rt_part *part = nullptr)
 {
   RtSrc r;
   r.at_infinity = s.at_infinity ? 1 : 0;
@@ -116,13 +141,48 @@ inline RtSrc rt_make_source(const pion_gpu_config &c, const pion_gpu_rt_source &
     r.ipos[a] = 0;
     double p = (a < c.ndim) ? s.pos[a] : 0.0;
     if (a < c.ndim && !r.at_infinity) {
-      p = rt_centre_on_vertex(p, c.xmin[a], c.dx);
-      r.ipos[a] = static_cast<int>((1.0 + 1.0e-12) * ((p - c.xmin[a]) / (0.5 * c.dx)));
+      const bool slab_axis = part && a == c.ndim - 1;
+      const double xmin = slab_axis ? part->global_xmin : c.xmin[a];
+      p = rt_centre_on_vertex(p, xmin, c.dx);
+      r.ipos[a] = static_cast<int>((1.0 + 1.0e-12) * ((p - xmin) / (0.5 * c.dx)));
       // (a vertex by construction; an odd number here could only come from a position beyond 2^52 cells)
       if (r.ipos[a] & 1) r.ipos[a] += (r.ipos[a] > 0) ? 1 : -1;
+      if (slab_axis) r.ipos[a] -= 2 * part->plane_lo;
     }
     if (pos_used) pos_used[a] = p;
   }
+  return r;
+}
+
+// ---- roles in the chain of a decomposed run.  The columns of a plane are finished by the rank that holds it; a cell
+// reads cells one step nearer the source along the axis of its largest distance and 0 or 1 step along the others, so one
+// plane of col per internal face is all that crosses.  The rank whose planes hold the source's vertex plane v
+// (plane_lo <= v < plane_lo + n; a source beyond the domain: rank 0 or the last rank) receives nothing and sends both
+// ways; a rank above it receives from below and sends upwards, a rank below it the other way round.  A vertex on an
+// internal face: the cells beside it have d = 1 and never read across it, the message is sent all the same.  A source at
+// infinity along the slab axis starts from the rank at the face it lies beyond; across the slab axis nothing crosses.
+// recv_side: PION_RT_RECV_NONE / _BELOW / _ABOVE; send_lo, send_hi: 1 where the neighbour below / above is sent to.
+struct RtRole { int recv_side, send_lo, send_hi; };
+
+inline RtRole rt_role(const pion_gpu_config &c, const pion_gpu_rt_source &s, const pion_gpu_rt_part &part)
+{
+  RtRole r = {PION_RT_RECV_NONE, 0, 0};
+  const int n = c.ng[c.ndim - 1];
+  const bool first = part.plane_lo == 0, last = part.plane_lo + n == part.global_planes;
+  int where;   // -1: the rank's planes lie below the one that starts the chain, 0: it starts it, 1: above
+  if (s.at_infinity) {
+    if (s.dir / 2 != c.ndim - 1) return r;
+    where = (s.dir & 1) ? (last ? 0 : -1) : (first ? 0 : 1);
+  }
+  else {
+    const RtSrc k = rt_make_source(c, s, nullptr, &part);
+    const int v = k.ipos[c.ndim - 1] / 2;   // in the slab's own planes
+    where = (v < 0 && !first) ? 1 : (v >= n && !last) ? -1 : 0;
+  }
+  if (where > 0) r.recv_side = PION_RT_RECV_BELOW;
+  if (where < 0) r.recv_side = PION_RT_RECV_ABOVE;
+  r.send_lo = where <= 0 && !first;
+  r.send_hi = where >= 0 && !last;
   return r;
 }
 

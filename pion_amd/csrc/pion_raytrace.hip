@@ -24,6 +24,14 @@
 //                  other in ray order (no scan: the association is the sequential one).
 //   k_pack_columns big-endian copy of a plane range for the FITS writer.
 // Cell ids and buffer indices are long; launch grids are checked against 2^31 - 1.
+//
+// A slab of a decomposed run (dev_raytrace.h, "a part"; pion_gpu_add_rt_source_part, pion_gpu_raytrace_part): every
+// source's col array has one spare plane below and one above the on-grid planes, and the plane the neighbouring rank
+// handed over is copied into the one that looks towards the source before the launches.  The kernels are given the
+// first on-grid plane, so their loads stay as they are, and "readable" (rt_readable) is on-grid or in that spare plane.
+// k_rt_levels and the host loop read it through ColGlobal, k_rt_par_yz starts its sum from it, and k_rt_tiles finds it
+// inside the first tile that holds cells or in that tile's halo (see there).  The rank's lowest and highest own plane
+// leave by copies on the same stream after the launches.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -38,7 +46,9 @@ using namespace pion::impl;
 namespace pion::impl {
 struct RtState {
   std::vector<RtSrc> src;
-  std::vector<double *> dcols;   // per source [2][nz][ny][nx]: col, dcol
+  std::vector<double *> dcols;   // per source: a spare plane, col [nz][ny][nx], a spare plane, dcol [nz][ny][nx]
+  std::vector<int> part;         // added with a part (pion_gpu_add_rt_source_part)
+  std::vector<RtRole> role;      // its role in the chain (no part: receives nothing, sends nothing)
   int levels = 0;                // finite sources run k_rt_levels
 };
 }  // namespace pion::impl
@@ -53,6 +63,9 @@ struct RtGeom {
   long sy, sz;   // all-cell strides
   long ncell;    // cells per variable, ghosts included
   double dx;
+  // a part of a decomposed run: the plane of the slab axis (z in 3-D, y in 2-D) one below (glo) or one above (ghi) the
+  // on-grid planes holds the columns the neighbouring rank handed over.  The column array has both spare planes.
+  int glo, ghi;
 };
 
 RtGeom rt_geom(const GridDesc &g)
@@ -68,6 +81,14 @@ RtGeom rt_geom(const GridDesc &g)
   q.off0 = g.nbc[0] + g.sy * g.nbc[1] + g.sz * g.nbc[2];
   q.ncell = g.ncell;
   q.dx = g.dx;
+  q.glo = q.ghi = 0;
+  return q;
+}
+RtGeom rt_geom(const GridDesc &g, const int recv_side)
+{
+  RtGeom q = rt_geom(g);
+  q.glo = recv_side == PION_RT_RECV_BELOW;
+  q.ghi = recv_side == PION_RT_RECV_ABOVE;
   return q;
 }
 
@@ -84,13 +105,20 @@ __host__ __device__ inline bool rt_ongrid(const RtGeom &q, const int ix, const i
   return ix >= 0 && ix < q.nx && iy >= 0 && iy < q.ny && iz >= 0 && iz < q.nz;
 }
 
+// on the grid, or in the spare plane that holds what was received (rt_col_id is valid there: plane -1 or n)
+__host__ __device__ inline bool rt_readable(const RtGeom &q, const int ix, const int iy, const int iz)
+{
+  if (q.ndim == 3) return ix >= 0 && ix < q.nx && iy >= 0 && iy < q.ny && iz >= -q.glo && iz < q.nz + q.ghi;
+  return ix >= 0 && ix < q.nx && iy >= -q.glo && iy < q.ny + q.ghi && iz == 0;
+}
+
 // the finished column of a neighbour in the column array itself
 struct ColGlobal {
   const double *col;
   const RtGeom *q;
   __host__ __device__ double operator()(const int ix, const int iy, const int iz) const
   {
-    return rt_ongrid(*q, ix, iy, iz) ? col[rt_col_id(*q, ix, iy, iz)] : 0.0;
+    return rt_readable(*q, ix, iy, iz) ? col[rt_col_id(*q, ix, iy, iz)] : 0.0;
   }
 };
 
@@ -128,9 +156,9 @@ k_rt_levels(const double *__restrict__ P, double *col, double *__restrict__ dcol
   rt_cell(P, q, s, ix, iy, iz, colat, &col[c], &dcol[c]);
 }
 
-// the tiles of one axis as a launch sees them: side 0 holds tiles 0 .. nt0 - 1, side 1 tiles 0 .. nt1 - 1 (a side
-// without on-grid cells holds none; tiles below the first on-grid k are empty and return)
-struct RtTileAxis { int nt0, nt1; };
+// the tiles of one axis as a launch sees them: side 0 holds tiles lo0 .. lo0 + nt0 - 1, side 1 tiles lo1 .. lo1 + nt1 - 1,
+// the tiles of [klo / tile, khi / tile] (a side without on-grid cells holds none)
+struct RtTileAxis { int lo0, nt0, lo1, nt1; };
 
 template <int TX, int TY, int TZ>
 __global__ void __launch_bounds__(64)
@@ -150,8 +178,8 @@ k_rt_tiles(const double *__restrict__ P, double *col, double *__restrict__ dcol,
   b /= 2;
   const int jy = (int)(b % nty), jz = (int)(b / nty);
   if (jz >= ntz) return;
-  const int sidey = (jy < ay.nt0) ? 0 : 1, ty = sidey ? jy - ay.nt0 : jy;
-  const int sidez = (jz < az.nt0) ? 0 : 1, tz = sidez ? jz - az.nt0 : jz;
+  const int sidey = (jy < ay.nt0) ? 0 : 1, ty = sidey ? ay.lo1 + jy - ay.nt0 : ay.lo0 + jy;
+  const int sidez = (jz < az.nt0) ? 0 : 1, tz = sidez ? az.lo1 + jz - az.nt0 : az.lo0 + jz;
   const long tx = T - ty - tz;
   if (tx < 0 || tx > p.khi[0][sidex] / TX || p.khi[0][sidex] < p.klo[0][sidex]) return;
   const int k0x = (int)tx * TX, k0y = ty * TY, k0z = tz * TZ;
@@ -162,6 +190,16 @@ k_rt_tiles(const double *__restrict__ P, double *col, double *__restrict__ dcol,
 
   const int lane = (int)threadIdx.x;
   const bool tracer = s.opacity != PION_RT_OPACITY_TOTAL;
+
+  // The plane received from the neighbouring rank (q.glo, q.ghi).  Tiles are counted from the source vertex, so that
+  // plane lies in general INSIDE the first tile that holds on-grid cells (slot eg of the slab axis), and in the tile's
+  // halo only where the slab's face falls on a tile boundary (eg = -1: the halo loads below read it as readable).
+  constexpr int TS = (TZ > 1) ? TZ : TY;                      // the tile along the slab axis
+  constexpr int NG = (TZ > 1) ? TX * TY : TX, GIT = (NG + 63) / 64;
+  const int sides = (TZ > 1) ? sidez : sidey, k0s = (TZ > 1) ? k0z : k0y;
+  const int kg = q.glo ? -1 - p.v[TZ > 1 ? 2 : 1] : p.v[TZ > 1 ? 2 : 1] - 1 - ((TZ > 1) ? q.nz : q.ny);
+  const int eg = kg - k0s;
+  const bool ghost_in = (q.glo || q.ghi) && sides == (q.glo ? 1 : 0) && eg >= 0 && eg < TS;
 
   // Every global load of the tile is issued before the first one is used: the loops below have constant trip counts and
   // are unrolled, and a lane without a cell loads from a valid address (on-grid cell 0) and discards the value, so
@@ -180,9 +218,21 @@ k_rt_tiles(const double *__restrict__ P, double *col, double *__restrict__ dcol,
     else { ex = 1 + (e - NHX - NHY) % TX; ey = 1 + (e - NHX - NHY) / TX; }
     const int kx = k0x + ex - 1, ky = k0y + ey - 1, kz = k0z + ez - OZ;
     const int ix = rt_k_to_i(p.v[0], sidex, kx), iy = rt_k_to_i(p.v[1], sidey, ky), iz = rt_k_to_i(p.v[2], sidez, kz);
-    const bool on = e < NH && kx >= 0 && ky >= 0 && kz >= 0 && rt_ongrid(q, ix, iy, iz);
+    const bool on = e < NH && kx >= 0 && ky >= 0 && kz >= 0 && rt_readable(q, ix, iy, iz);
     const double v = col[on ? rt_col_id(q, ix, iy, iz) : 0L];
     hv[it] = on ? v : 0.0;
+  }
+  //    the received plane inside the tile: the same way, from on-grid cell 0 where there is none
+  double gv[GIT];
+#pragma unroll
+  for (int it = 0; it < GIT; it++) {
+    const int e = lane + 64 * it;
+    const int ex = e % TX, ey = (TZ > 1) ? e / TX : eg, ez = (TZ > 1) ? eg : 0;
+    const int ix = rt_k_to_i(p.v[0], sidex, k0x + ex), iy = rt_k_to_i(p.v[1], sidey, k0y + ey),
+              iz = rt_k_to_i(p.v[2], sidez, k0z + ez);
+    const bool on = ghost_in && e < NG && rt_readable(q, ix, iy, iz);
+    const double v = col[on ? rt_col_id(q, ix, iy, iz) : 0L];
+    gv[it] = on ? v : 0.0;
   }
   // 2. rho and the tracer: consecutive lanes along x
   double rv[CIT], yv[CIT];
@@ -214,7 +264,14 @@ k_rt_tiles(const double *__restrict__ P, double *col, double *__restrict__ dcol,
     const int ex = e % TX, ey = (e / TX) % TY, ez = e / (TX * TY);
     srho[ez][ey][ex] = rv[it];
     sy_[ez][ey][ex] = yv[it];
-    scol[ez + OZ][ey + 1][ex + 1] = 0.0;   // a cell of the tile that is off the grid contributes 0
+    // a cell of the tile that is off the grid contributes 0; the received plane's slots are written below
+    if (!(ghost_in && ((TZ > 1) ? ez : ey) == eg)) scol[ez + OZ][ey + 1][ex + 1] = 0.0;
+  }
+#pragma unroll
+  for (int it = 0; it < GIT; it++) {
+    const int e = lane + 64 * it;
+    const int ex = e % TX, ey = (TZ > 1) ? e / TX : eg, ez = (TZ > 1) ? eg : 0;
+    if (ghost_in && e < NG) scol[ez + OZ][ey + 1][ex + 1] = gv[it];
   }
   __syncthreads();
 
@@ -261,8 +318,8 @@ k_rt_tiles(const double *__restrict__ P, double *col, double *__restrict__ dcol,
 // source beyond the upper face)
 constexpr int PAR_WAVES = 4;
 __global__ void __launch_bounds__(64 * PAR_WAVES)
-k_rt_par_yz(const double *__restrict__ P, double *__restrict__ col, double *__restrict__ dcol, const RtGeom q,
-            const RtSrc s, const int axis)
+k_rt_par_yz(const double *__restrict__ P, double *col, double *__restrict__ dcol, const RtGeom q, const RtSrc s,
+            const int axis)
 {
   // columns: (x, the other axis); x fastest
   const int nother = (axis == 1) ? q.nz : q.ny;
@@ -274,7 +331,10 @@ k_rt_par_yz(const double *__restrict__ P, double *__restrict__ col, double *__re
   const int ix = (int)(u - (long)j * nseg) * 64 + (int)(threadIdx.x & 63);
   if (ix >= q.nx) return;
   const bool up = (s.dir & 1) == 0;   // source beyond the lower face: rays run towards increasing index
-  double N = 0.0;
+  // a part: the sum starts from the plane received (the spare plane before the first cell), not from 0
+  const int kb = up ? -1 : n;
+  const bool recv = up ? q.glo : q.ghi;
+  double N = recv ? col[rt_col_id(q, ix, (axis == 1) ? kb : j, (axis == 1) ? j : kb)] : 0.0;
   for (int m = 0; m < n; m++) {
     const int k = up ? m : n - 1 - m;
     const int iy = (axis == 1) ? k : j, iz = (axis == 1) ? j : k;
@@ -366,14 +426,28 @@ bool grid_fits(Handle *h, const long nblk)
 RtTileAxis tile_axis(const RtPlan &p, const int a)
 {
   RtTileAxis t;
-  t.nt0 = (p.khi[a][0] >= p.klo[a][0]) ? p.khi[a][0] / p.tile[a] + 1 : 0;
-  t.nt1 = (p.khi[a][1] >= p.klo[a][1]) ? p.khi[a][1] / p.tile[a] + 1 : 0;
+  t.lo0 = p.klo[a][0] / p.tile[a];
+  t.lo1 = p.klo[a][1] / p.tile[a];
+  t.nt0 = (p.khi[a][0] >= p.klo[a][0]) ? p.khi[a][0] / p.tile[a] - t.lo0 + 1 : 0;
+  t.nt1 = (p.khi[a][1] >= p.klo[a][1]) ? p.khi[a][1] / p.tile[a] - t.lo1 + 1 : 0;
   return t;
 }
 
-int trace_source(Handle *h, const RtSrc &s, const double *P, double *col, double *dcol, long *launches)
+// workgroups of one launch of k_rt_tiles; untrimmed: counted from the vertex (khi / tile + 1 tiles per side)
+long tile_workgroups(const RtPlan &p, const bool trimmed)
 {
-  const RtGeom q = rt_geom(h->g);
+  long n = 2;
+  for (int a = 1; a < 3; a++) {
+    const RtTileAxis t = tile_axis(p, a);
+    n *= trimmed ? t.nt0 + t.nt1 : (t.nt0 ? t.lo0 + t.nt0 : 0) + (t.nt1 ? t.lo1 + t.nt1 : 0);
+  }
+  return n;
+}
+
+// col points at the first on-grid plane of the source's array; the spare planes lie before and behind the on-grid ones
+int trace_source(Handle *h, const RtSrc &s, const int recv_side, const double *P, double *col, double *dcol, long *launches)
+{
+  const RtGeom q = rt_geom(h->g, recv_side);
   if (s.at_infinity) {
     const int axis = s.dir / 2;
     if (axis == 0) {
@@ -421,6 +495,9 @@ int trace_source(Handle *h, const RtSrc &s, const double *P, double *col, double
 int slab_planes(const Handle *h) { return h->g.ng[h->g.ndim - 1]; }
 long plane_cells(const Handle *h) { return (h->g.ndim == 3) ? (long)h->g.ng[0] * h->g.ng[1] : (long)h->g.ng[0]; }
 
+double *rt_col_of(const Handle *h, const int id) { return h->rt->dcols[id] + plane_cells(h); }
+double *rt_dcol_of(const Handle *h, const int id) { return h->rt->dcols[id] + 2 * plane_cells(h) + rt_geom(h->g).n; }
+
 // id and `what` of a column array, or null with the text set
 double *column_array(Handle *h, const int id, const int what)
 {
@@ -428,7 +505,7 @@ double *column_array(Handle *h, const int id, const int what)
     h->err = "raytrace: no such source or array (what: 0 col, 1 dcol)";
     return nullptr;
   }
-  return h->rt->dcols[id] + (long)what * rt_geom(h->g).n;
+  return what ? rt_dcol_of(h, id) : rt_col_of(h, id);
 }
 
 }  // namespace
@@ -440,6 +517,9 @@ void impl::rt_free(Handle *h)
   delete h->rt;
   h->rt = nullptr;
 }
+
+static int raytrace_host(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part,
+                         const double *P_soa, const double *face_in, double *col_out, double *dcol);
 
 extern "C" {
 
@@ -453,6 +533,42 @@ const char *pion_gpu_rt_refused(const pion_gpu_config *cfg, const pion_gpu_rt_so
   return rt_refused(*cfg, src);
 }
 
+const char *pion_gpu_rt_part_refused(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part)
+{
+  if (!cfg) return "raytrace: no configuration";
+  if (cfg->ndim < 1 || cfg->ndim > 3 || cfg->nbc < 0 || cfg->ntracer < 0 || cfg->ntracer > cfg->nvar || !(cfg->dx > 0.0))
+    return "raytrace: malformed configuration";
+  for (int a = 0; a < cfg->ndim; a++)
+    if (cfg->ng[a] < 1) return "raytrace: malformed configuration";
+  return rt_part_refused(*cfg, src, part);
+}
+
+static int add_source(Handle *h, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part, int *id, double *pos_used)
+{
+  if (h->rt && h->rt->src.size() >= PION_MAX_RT_SOURCES) {
+    h->err = "raytrace: more than PION_MAX_RT_SOURCES (4) sources";
+    return PION_GPU_EINVAL;
+  }
+  double *d = nullptr;
+  const size_t bytes = sizeof(double) * (2 * (size_t)rt_geom(h->g).n + 2 * (size_t)plane_cells(h));
+  if (hipMalloc((void **)&d, bytes) != hipSuccess) {
+    h->err = "raytrace: no device memory for the column arrays";
+    return PION_GPU_ENOMEM;
+  }
+  HCHECK(h, hipMemsetAsync(d, 0, bytes, h->stream));
+  if (!h->rt) {
+    h->rt = new RtState;
+    if (const char *e = getenv("PION_RT_KERNEL")) h->rt->levels = (strcmp(e, "levels") == 0) ? 1 : 0;
+  }
+  h->rt->src.push_back(rt_make_source(h->cfg, *src, pos_used, part));
+  h->rt->dcols.push_back(d);
+  h->rt->part.push_back(part ? 1 : 0);
+  const RtRole none = {PION_RT_RECV_NONE, 0, 0};
+  h->rt->role.push_back(part ? rt_role(h->cfg, *src, *part) : none);
+  if (id) *id = (int)h->rt->src.size() - 1;
+  return 0;
+}
+
 int pion_gpu_add_rt_source(void *handle, const pion_gpu_rt_source *src, int *id, double *pos_used)
 {
   Handle *h = use(handle);
@@ -461,25 +577,37 @@ int pion_gpu_add_rt_source(void *handle, const pion_gpu_rt_source *src, int *id,
     h->err = e;
     return PION_GPU_EINVAL;
   }
-  if (h->rt && h->rt->src.size() >= PION_MAX_RT_SOURCES) {
-    h->err = "raytrace: more than PION_MAX_RT_SOURCES (4) sources";
+  return add_source(h, src, nullptr, id, pos_used);
+}
+
+int pion_gpu_add_rt_source_part(void *handle, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part, int *id,
+                                double *pos_used)
+{
+  Handle *h = use(handle);
+  if (!h) return PION_GPU_EINVAL;
+  if (const char *e = pion_gpu_rt_part_refused(&h->cfg, src, part)) {
+    h->err = e;
     return PION_GPU_EINVAL;
   }
-  double *d = nullptr;
-  const long n = rt_geom(h->g).n;
-  if (hipMalloc((void **)&d, sizeof(double) * 2 * (size_t)n) != hipSuccess) {
-    h->err = "raytrace: no device memory for the column arrays";
-    return PION_GPU_ENOMEM;
-  }
-  HCHECK(h, hipMemsetAsync(d, 0, sizeof(double) * 2 * (size_t)n, h->stream));
-  if (!h->rt) {
-    h->rt = new RtState;
-    if (const char *e = getenv("PION_RT_KERNEL")) h->rt->levels = (strcmp(e, "levels") == 0) ? 1 : 0;
-  }
-  h->rt->src.push_back(rt_make_source(h->cfg, *src, pos_used));
-  h->rt->dcols.push_back(d);
-  if (id) *id = (int)h->rt->src.size() - 1;
+  return add_source(h, src, part, id, pos_used);
+}
+
+int pion_gpu_rt_chain(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part,
+                      int *recv_side, int *send_lo, int *send_hi)
+{
+  if (pion_gpu_rt_part_refused(cfg, src, part)) return PION_GPU_EINVAL;
+  const RtRole r = rt_role(*cfg, *src, *part);
+  if (recv_side) *recv_side = r.recv_side;
+  if (send_lo) *send_lo = r.send_lo;
+  if (send_hi) *send_hi = r.send_hi;
   return 0;
+}
+
+static bool has_slab_face(const Handle *h)
+{
+  for (int d = 0; d < 2 * h->cfg.ndim; d++)
+    if (h->cfg.bc_type[d] == PION_BC_SLAB) return true;
+  return false;
 }
 
 int pion_gpu_raytrace(void *handle, int which)
@@ -491,11 +619,50 @@ int pion_gpu_raytrace(void *handle, int which)
     h->err = "raytrace: which is 0 (P) or 1 (Ph)";
     return PION_GPU_EINVAL;
   }
+  if (has_slab_face(h)) {
+    h->err = "raytrace: a slab of a decomposed run is traced source by source with the planes of its neighbours (pion_gpu_raytrace_part)";
+    return PION_GPU_EINVAL;
+  }
   const double *P = (which == 1 && h->ph_valid) ? h->dPh : h->dP;
-  const long n = rt_geom(h->g).n;
   long launches = 0;
   for (size_t i = 0; i < h->rt->src.size(); i++)
-    if (int rc = trace_source(h, h->rt->src[i], P, h->rt->dcols[i], h->rt->dcols[i] + n, &launches)) return rc;
+    if (int rc = trace_source(h, h->rt->src[i], PION_RT_RECV_NONE, P, rt_col_of(h, (int)i), rt_dcol_of(h, (int)i), &launches))
+      return rc;
+  return 0;
+}
+
+int pion_gpu_raytrace_part(void *handle, int which, int id, const void *dface_in, void *dface_out_lo, void *dface_out_hi)
+{
+  Handle *h = use(handle);
+  if (!h) return PION_GPU_EINVAL;
+  if (which < 0 || which > 1) {
+    h->err = "raytrace: which is 0 (P) or 1 (Ph)";
+    return PION_GPU_EINVAL;
+  }
+  if (!column_array(h, id, 0)) return PION_GPU_EINVAL;
+  if (!h->rt->part[id] && has_slab_face(h)) {   // (cannot happen: such a source is refused when it is added)
+    h->err = "raytrace: the source was added without a part";
+    return PION_GPU_EINVAL;
+  }
+  const RtRole role = h->rt->role[id];
+  if (role.recv_side != PION_RT_RECV_NONE && !dface_in) {
+    h->err = "raytrace: the source's chain hands this part a plane, and there is no buffer of it";
+    return PION_GPU_EINVAL;
+  }
+  const double *P = (which == 1 && h->ph_valid) ? h->dPh : h->dP;
+  const size_t pbytes = sizeof(double) * (size_t)plane_cells(h);
+  const long n = rt_geom(h->g).n, pc = plane_cells(h);
+  double *col = rt_col_of(h, id);
+  // the received plane goes into the spare plane beyond the face that looks towards the source
+  if (role.recv_side == PION_RT_RECV_BELOW)
+    HCHECK(h, hipMemcpyAsync(col - pc, dface_in, pbytes, hipMemcpyDeviceToDevice, h->stream));
+  if (role.recv_side == PION_RT_RECV_ABOVE)
+    HCHECK(h, hipMemcpyAsync(col + n, dface_in, pbytes, hipMemcpyDeviceToDevice, h->stream));
+  long launches = 0;
+  if (int rc = trace_source(h, h->rt->src[id], role.recv_side, P, col, rt_dcol_of(h, id), &launches)) return rc;
+  // the rank's lowest and highest own plane, for the neighbours
+  if (dface_out_lo) HCHECK(h, hipMemcpyAsync(dface_out_lo, col, pbytes, hipMemcpyDeviceToDevice, h->stream));
+  if (dface_out_hi) HCHECK(h, hipMemcpyAsync(dface_out_hi, col + n - pc, pbytes, hipMemcpyDeviceToDevice, h->stream));
   return 0;
 }
 
@@ -559,10 +726,48 @@ int pion_gpu_rt_plan(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, 
   return 0;
 }
 
+int pion_gpu_rt_plan_part(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part,
+                          long *launches, long *workgroups, long *workgroups_from_vertex)
+{
+  if (pion_gpu_rt_part_refused(cfg, src, part)) return PION_GPU_EINVAL;
+  const RtSrc s = rt_make_source(*cfg, *src, nullptr, part);
+  int ng[3];
+  for (int a = 0; a < 3; a++) ng[a] = (a < cfg->ndim) ? cfg->ng[a] : 1;
+  long l = 1, w = 0, w0 = 0;
+  if (!s.at_infinity) {
+    const RtPlan p = rt_plan_of(cfg->ndim, ng, s);
+    l = p.tlevel_hi - p.tlevel_lo + 1;
+    w = tile_workgroups(p, true);
+    w0 = tile_workgroups(p, false);
+  }
+  if (launches) *launches = l;
+  if (workgroups) *workgroups = w;
+  if (workgroups_from_vertex) *workgroups_from_vertex = w0;
+  return 0;
+}
+
 int pion_gpu_raytrace_host(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const double *P_soa, double *col,
                            double *dcol)
 {
-  if (pion_gpu_rt_refused(cfg, src) || !P_soa || !col || !dcol) return PION_GPU_EINVAL;
+  if (pion_gpu_rt_refused(cfg, src)) return PION_GPU_EINVAL;
+  return raytrace_host(cfg, src, nullptr, P_soa, nullptr, col, dcol);
+}
+
+int pion_gpu_raytrace_host_part(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part,
+                                const double *P_soa, const double *face_in, double *col, double *dcol)
+{
+  if (pion_gpu_rt_part_refused(cfg, src, part)) return PION_GPU_EINVAL;
+  return raytrace_host(cfg, src, part, P_soa, face_in, col, dcol);
+}
+
+}  // extern "C"
+
+// the host loop of both: col and dcol hold the on-grid cells only; with a part the columns are traced in an array that
+// has the two spare planes and copied out
+static int raytrace_host(const pion_gpu_config *cfg, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part,
+                         const double *P_soa, const double *face_in, double *col_out, double *dcol)
+{
+  if (!P_soa || !col_out || !dcol) return PION_GPU_EINVAL;
   GridDesc g;
   g.ndim = cfg->ndim;
   g.ncell = 1;
@@ -575,8 +780,23 @@ int pion_gpu_raytrace_host(const pion_gpu_config *cfg, const pion_gpu_rt_source 
   g.sy = g.nga[0];
   g.sz = (long)g.nga[0] * g.nga[1];
   g.dx = cfg->dx;
-  const RtGeom q = rt_geom(g);
-  const RtSrc s = rt_make_source(*cfg, *src, nullptr);
+  const RtRole none = {PION_RT_RECV_NONE, 0, 0};
+  const RtRole role = part ? rt_role(*cfg, *src, *part) : none;
+  if (role.recv_side != PION_RT_RECV_NONE && !face_in) return PION_GPU_EINVAL;
+  const RtGeom q = rt_geom(g, role.recv_side);
+  const RtSrc s = rt_make_source(*cfg, *src, nullptr, part);
+  const long pc = (g.ndim == 3) ? (long)g.ng[0] * g.ng[1] : (long)g.ng[0];
+  std::vector<double> with_spares;
+  double *col = col_out;
+  if (role.recv_side != PION_RT_RECV_NONE) {
+    with_spares.assign((size_t)(q.n + 2 * pc), 0.0);
+    col = with_spares.data() + pc;
+    memcpy(role.recv_side == PION_RT_RECV_BELOW ? col - pc : col + q.n, face_in, sizeof(double) * (size_t)pc);
+  }
+  const auto finish = [&]() {
+    if (col != col_out) memcpy(col_out, col, sizeof(double) * (size_t)q.n);
+    return 0;
+  };
   if (s.at_infinity) {
     // trace_parallel_rays: every column of the axis, cell after cell from the face the source lies beyond
     const int axis = s.dir / 2, n = g.ng[axis];
@@ -585,7 +805,8 @@ int pion_gpu_raytrace_host(const pion_gpu_config *cfg, const pion_gpu_rt_source 
     const int a1 = (axis + 1) % 3, a2 = (axis + 2) % 3;
     for (i[a2] = 0; i[a2] < g.ng[a2]; i[a2]++)
       for (i[a1] = 0; i[a1] < g.ng[a1]; i[a1]++) {
-        double N = 0.0;
+        i[axis] = up ? -1 : n;
+        double N = (axis == g.ndim - 1 && (up ? q.glo : q.ghi)) ? col[rt_col_id(q, i[0], i[1], i[2])] : 0.0;
         for (int m = 0; m < n; m++) {
           i[axis] = up ? m : n - 1 - m;
           const long c = rt_state_id(q, i[0], i[1], i[2]);
@@ -597,7 +818,7 @@ int pion_gpu_raytrace_host(const pion_gpu_config *cfg, const pion_gpu_rt_source 
           dcol[o] = dc;
         }
       }
-    return 0;
+    return finish();
   }
   // octant by octant, outwards from the source: one valid order among the many the dependency admits
   const RtPlan p = rt_plan_of(g.ndim, g.ng, s);
@@ -612,7 +833,5 @@ int pion_gpu_raytrace_host(const pion_gpu_config *cfg, const pion_gpu_rt_source 
           rt_cell(P_soa, q, s, ix, iy, iz, colat, &col[o], &dcol[o]);
         }
   }
-  return 0;
+  return finish();
 }
-
-}  // extern "C"

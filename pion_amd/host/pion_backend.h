@@ -112,6 +112,18 @@ typedef struct pion_backend {
   int (*raytrace)(void *handle, int which);
   long (*rt_count)(void *handle, int planes);
   int (*columns_to_host_begin)(void *handle, int id, int what, int plane_lo, int plane_hi, int slot);
+  /* The ray tracer of a slab run (dev_raytrace.h, "a part"; pion_gpu_add_rt_source_part, pion_gpu_raytrace_part).  These
+   * two entries are read ONLY inside add_rt_source and write_columns of a sim that is one rank of a slab run: any other
+   * caller may hand the loop a table that ends before them.  Both NULL: the sim keeps the sources itself, and the
+   * writer takes array 0 through download and runs pion_gpu_raytrace_host_part on it.
+   *   add_rt_source_part:   pion_gpu_add_rt_source_part
+   *   raytrace_part_faces:  the plane received travels host -> device (face_in; NULL where the source's chain hands this
+   *                         rank none), source `id` is traced from array `which`, the rank's lowest and highest own
+   *                         plane of col travel device -> host (face_lo, face_hi; either may be NULL); each
+   *                         rt_count(handle, 1) doubles; complete on return */
+  int (*add_rt_source_part)(void *handle, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part, int *id,
+                            double *pos_used);
+  int (*raytrace_part_faces)(void *handle, int which, int id, const double *face_in, double *face_lo, double *face_hi);
 } pion_backend;
 
 /* the product's backend: libpion_gpu.so */

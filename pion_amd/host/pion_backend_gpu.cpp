@@ -232,6 +232,22 @@ int gpu_columns_to_host_begin(void *h, int id, int what, int plane_lo, int plane
   st->busy[slot] = true;
   return 0;
 }
+// one source of a slab run: slot 0's device buffer holds the three planes [received][lowest own][highest own]
+int gpu_raytrace_part_faces(void *h, int which, int id, const double *face_in, double *face_lo, double *face_hi)
+{
+  const long n = pion_gpu_rt_count(h, 1);
+  Staging *st;
+  if (int rc = staging_slot(h, 0, 3 * n, &st)) return rc;
+  hipStream_t s = compute_stream_of(h);
+  double *d = st->dev[0];
+  const size_t bytes = (size_t)n * sizeof(double);
+  if (face_in && hipMemcpyAsync(d, face_in, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return PION_GPU_EDEVICE;
+  if (int rc = pion_gpu_raytrace_part(h, which, id, face_in ? d : nullptr, face_lo ? d + n : nullptr, face_hi ? d + 2 * n : nullptr))
+    return rc;
+  if (face_lo && hipMemcpyAsync(face_lo, d + n, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return PION_GPU_EDEVICE;
+  if (face_hi && hipMemcpyAsync(face_hi, d + 2 * n, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return PION_GPU_EDEVICE;
+  return hipStreamSynchronize(s) == hipSuccess ? 0 : PION_GPU_EDEVICE;
+}
 void gpu_destroy(void *h)
 {
   Staging st;
@@ -286,6 +302,8 @@ const pion_backend k_gpu = {
     pion_gpu_raytrace,
     pion_gpu_rt_count,
     gpu_columns_to_host_begin,
+    pion_gpu_add_rt_source_part,
+    gpu_raytrace_part_faces,
 };
 
 }  // namespace

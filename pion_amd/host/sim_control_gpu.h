@@ -117,8 +117,11 @@ class sim_control_gpu {
   // dataIO/dataio_base.cpp:1267-1282), and per source two double-precision IMAGE extensions of the on-grid cells,
   // Col_Src_<n>_T0 (column to + through the cell) and DCol_Src_<n>_T0 (through it), traced from P as it stands (after
   // the boundary update) and streamed a chunk of planes at a time; a table without the entries downloads array 0 and runs
-  // pion_gpu_raytrace_host.  EINVAL and a text: what pion_gpu_add_rt_source refuses; no sources; a sim that is one rank
-  // of several (a slab extent, or a communicator of more than one rank)
+  // pion_gpu_raytrace_host.  EINVAL and a text: what pion_gpu_add_rt_source refuses; no sources; one rank of a slab run
+  // with only one of a slab extent and a communicator of more than one rank (or a communicator without both relay
+  // directions).  With both (set before the first source) the calls are collective (columns_io.cpp): sources are given
+  // at positions of the whole domain, per source the planes of col are handed from rank to rank away from the source,
+  // and every rank writes its own file with its own planes -- images and RT_* keys == the single-rank file's
   int add_rt_source(const pion_gpu_rt_source &src, int *id, double *pos_used);
   int write_columns(const char *path);
   // from now on every regular output of output_data() is accompanied by <base>_cols_<rank, 4 digits>.<step, 8
@@ -174,6 +177,11 @@ class sim_control_gpu {
   bool column_output_ = false;                   // set_column_output
   // columns_io.cpp
   int columns_refused(const char *who);
+  bool columns_collective() const;   // one rank of a slab run whose columns are handed along the ranks
+  pion_gpu_rt_part columns_part() const;
+  int relay_columns(int rc, int id, bool on_device, const double *A, double *col, double *dcol);
+  int agree_on(int rc);
+  bool rt_as_parts_ = false;         // the sources were added as sources of the whole domain (collective)
   // projection_io.cpp
   bool projection_collective() const;   // one rank of a slab run whose images are assembled along the ranks
   int project_images(int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part *part, long n, double *img);

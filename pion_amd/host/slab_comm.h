@@ -1,7 +1,8 @@
 // slab_comm.h -- what sim_control_gpu needs from a slab communicator (one process per GPU): the halo
 // exchange of BC_update_BCMPI (boundaries/MCMD_boundaries.cpp:122-237) split into a start and a finish around the
 // interior part of a stage, and the global minimum of the time step (sim_control_MPI.cpp:503-504).
-// Beside the step path: a buffer handed one rank up (the projected image of a slab run, write_projection).
+// Beside the step path: a buffer handed one rank up (the projected image of a slab run, write_projection) or one
+// rank up or down (a plane of column densities per source, write_columns).
 // The slab axis is the grid's last axis: z in 3-D, y in 2-D, where the "planes" below are rows.
 //
 // Two implementations:
@@ -49,6 +50,21 @@ class slab_comm {
     return -1;
   }
   virtual int send_to_above(const void *host, size_t bytes, int status)
+  {
+    (void)host, (void)bytes, (void)status;
+    return -1;
+  }
+  // The same pair one rank DOWN the chain (the planes of the ray tracer travel away from the source, both ways:
+  // columns_io.cpp): recv_from_above takes the message of rank + 1, send_to_below hands one to rank - 1; the last rank
+  // receives from nobody and rank 0 sends to nobody.  The same status-word protocol: a failing rank sends a status and
+  // no data, no rank blocks.  has_relay_down() tells whether the transport has the pair; the default has not.
+  virtual bool has_relay_down() const { return false; }
+  virtual int recv_from_above(void *host, size_t bytes, int *status)
+  {
+    (void)host, (void)bytes, (void)status;
+    return -1;
+  }
+  virtual int send_to_below(const void *host, size_t bytes, int status)
   {
     (void)host, (void)bytes, (void)status;
     return -1;

@@ -175,11 +175,10 @@ int slab_comm_rccl::relay_buffer(size_t bytes)
   return 0;
 }
 
-int slab_comm_rccl::send_to_above(const void *host, size_t bytes, int status)
+int slab_comm_rccl::relay_send(int peer, const char *who, const void *host, size_t bytes, int status)
 {
-  if (rank_ >= world_ - 1) return 0;
   if (!host && status == 0) {
-    err_ = "send_to_above: no buffer";
+    err_ = std::string(who) + ": no buffer";
     return PION_GPU_EINVAL;
   }
   const size_t n = status ? 0 : bytes;
@@ -189,38 +188,56 @@ int slab_comm_rccl::send_to_above(const void *host, size_t bytes, int status)
   PH_HIP(hipMemcpyAsync(relay_, head, sizeof head, hipMemcpyHostToDevice, s));
   if (n) PH_HIP(hipMemcpyAsync((char *)relay_ + 16, host, n, hipMemcpyHostToDevice, s));
   PH_HIP(hipStreamSynchronize(s));   // (head and, if pageable, host have left the caller's memory)
-  PH_NCCL(ncclSend(relay_, 16, ncclChar, rank_ + 1, (ncclComm_t)comm_, s));
-  if (n) PH_NCCL(ncclSend((char *)relay_ + 16, n, ncclChar, rank_ + 1, (ncclComm_t)comm_, s));
+  PH_NCCL(ncclSend(relay_, 16, ncclChar, peer, (ncclComm_t)comm_, s));
+  if (n) PH_NCCL(ncclSend((char *)relay_ + 16, n, ncclChar, peer, (ncclComm_t)comm_, s));
   PH_HIP(hipStreamSynchronize(s));
   return 0;
 }
 
-int slab_comm_rccl::recv_from_below(void *host, size_t bytes, int *status)
+int slab_comm_rccl::relay_recv(int peer, const char *who, void *host, size_t bytes, int *status)
 {
-  if (status) *status = 0;
-  if (rank_ == 0) return 0;
   if (int rc = relay_buffer(bytes)) return rc;
   hipStream_t s = (hipStream_t)cstream_;
   long long head[2] = {0, 0};
-  PH_NCCL(ncclRecv(relay_, 16, ncclChar, rank_ - 1, (ncclComm_t)comm_, s));
+  PH_NCCL(ncclRecv(relay_, 16, ncclChar, peer, (ncclComm_t)comm_, s));
   PH_HIP(hipMemcpyAsync(head, relay_, sizeof head, hipMemcpyDeviceToHost, s));
   PH_HIP(hipStreamSynchronize(s));
   if (status) *status = (int)head[0];
   const size_t n = (size_t)head[1];
+  const std::string whom = std::string(who) + ": the message of the rank " + (peer < rank_ ? "below" : "above") + " has ";
   if (n == 0 && (head[0] != 0 || bytes == 0)) return 0;   // a failure's message has no data
   if (n == 0) {
-    err_ = "recv_from_below: the message of the rank below has 0 bytes, expected " + std::to_string(bytes);
+    err_ = whom + "0 bytes, expected " + std::to_string(bytes);
     return PION_GPU_EINVAL;
   }
   if (int rc = relay_buffer(n)) return rc;   // (a message of another length is taken off the wire all the same)
-  PH_NCCL(ncclRecv((char *)relay_ + 16, n, ncclChar, rank_ - 1, (ncclComm_t)comm_, s));
+  PH_NCCL(ncclRecv((char *)relay_ + 16, n, ncclChar, peer, (ncclComm_t)comm_, s));
   if (host && n == bytes) PH_HIP(hipMemcpyAsync(host, (char *)relay_ + 16, n, hipMemcpyDeviceToHost, s));
   PH_HIP(hipStreamSynchronize(s));
   if (!host || n != bytes) {
-    err_ = "recv_from_below: the message of the rank below has " + std::to_string(n) + " bytes, expected " + std::to_string(bytes);
+    err_ = whom + std::to_string(n) + " bytes, expected " + std::to_string(bytes);
     return PION_GPU_EINVAL;
   }
   return 0;
+}
+
+int slab_comm_rccl::send_to_above(const void *host, size_t bytes, int status)
+{
+  return (rank_ >= world_ - 1) ? 0 : relay_send(rank_ + 1, "send_to_above", host, bytes, status);
+}
+int slab_comm_rccl::send_to_below(const void *host, size_t bytes, int status)
+{
+  return (rank_ == 0) ? 0 : relay_send(rank_ - 1, "send_to_below", host, bytes, status);
+}
+int slab_comm_rccl::recv_from_below(void *host, size_t bytes, int *status)
+{
+  if (status) *status = 0;
+  return (rank_ == 0) ? 0 : relay_recv(rank_ - 1, "recv_from_below", host, bytes, status);
+}
+int slab_comm_rccl::recv_from_above(void *host, size_t bytes, int *status)
+{
+  if (status) *status = 0;
+  return (rank_ >= world_ - 1) ? 0 : relay_recv(rank_ + 1, "recv_from_above", host, bytes, status);
 }
 
 }  // namespace pion_host

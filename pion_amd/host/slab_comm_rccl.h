@@ -58,6 +58,9 @@ class slab_comm_rccl : public slab_comm {
   bool has_relay() const override { return true; }
   int recv_from_below(void *host, size_t bytes, int *status) override;
   int send_to_above(const void *host, size_t bytes, int status) override;
+  bool has_relay_down() const override { return true; }
+  int recv_from_above(void *host, size_t bytes, int *status) override;
+  int send_to_below(const void *host, size_t bytes, int status) override;
 
   bool has_neighbours() const { return up_ >= 0 || down_ >= 0; }
   const std::string &last_error() const override { return err_; }
@@ -74,6 +77,8 @@ class slab_comm_rccl : public slab_comm {
   void *relay_ = nullptr;      // device buffer of the image relay: 16 bytes of header, then the data
   size_t relay_bytes_ = 0;
   int relay_buffer(size_t bytes);
+  int relay_send(int peer, const char *who, const void *host, size_t bytes, int status);
+  int relay_recv(int peer, const char *who, void *host, size_t bytes, int *status);
   std::string err_;
 };
 

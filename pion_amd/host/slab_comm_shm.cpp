@@ -59,12 +59,13 @@ slab_comm_shm::~slab_comm_shm()
 {
   if (seg_) munmap(seg_, seg_bytes_);
   if (rank_ == 0 && !name_.empty()) shm_unlink(name_.c_str());
-  // the image relay's channels: this rank's own [0] and the one of the rank above [1]
-  for (int k = 0; k < 2; k++)
-    if (img_seg_[k]) {
-      munmap(img_seg_[k], img_chan_bytes());
-      shm_unlink((name_ + "_img" + std::to_string(rank_ + k)).c_str());
-    }
+  // the relay's channels, upwards and downwards: this rank's own [0] and the one of the rank it sends to [1]
+  for (int down = 0; down < 2; down++)
+    for (int k = 0; k < 2; k++)
+      if (img_seg_[down][k]) {
+        munmap(img_seg_[down][k], img_chan_bytes());
+        shm_unlink((name_ + (down ? "_dwn" : "_img") + std::to_string(down ? rank_ - k : rank_ + k)).c_str());
+      }
   if (pinned_) {
     (void)hipHostFree(stage_lo_);
     (void)hipHostFree(stage_hi_);
@@ -242,7 +243,8 @@ int slab_comm_shm::reset()
   return finish();
 }
 
-// ---- the image relay.  Segment "<name>_img<r>": one Chan -- the channel rank r receives in, written by rank r - 1.
+// ---- the relay.  Segment "<name>_img<r>": one Chan -- the channel rank r receives in, written by rank r - 1; segment
+// "<name>_dwn<r>": the same downwards, written by rank r + 1 (the planes of the ray tracer travel both ways).
 // A message is a run of pieces; the first piece carries the status word and the message's length, and no data follows a
 // status != 0.  `written` and `consumed` count pieces: the writer fills the channel when consumed == written, the reader
 // empties it when written > consumed.  The counters of the halo mailboxes and of the reduction are not touched.
@@ -256,11 +258,12 @@ struct slab_comm_shm::Chan {
   char data[IMG_PIECE];
 };
 size_t slab_comm_shm::img_chan_bytes() { return sizeof(Chan); }
-slab_comm_shm::Chan *slab_comm_shm::chan(int rank)
+slab_comm_shm::Chan *slab_comm_shm::chan(int down, int rank)
 {
-  char *&seg = img_seg_[rank - rank_];   // rank_: the channel this rank receives in; rank_ + 1: the one it sends in
+  // rank_: the channel this rank receives in; rank_ + 1 (downwards: rank_ - 1): the one it sends in
+  char *&seg = img_seg_[down][down ? rank_ - rank : rank - rank_];
   if (!seg) {
-    const std::string n = name_ + "_img" + std::to_string(rank);
+    const std::string n = name_ + (down ? "_dwn" : "_img") + std::to_string(rank);
     const int fd = shm_open(n.c_str(), O_CREAT | O_RDWR, 0600);   // (a fresh segment is zero-filled)
     if (fd < 0 || ftruncate(fd, (off_t)sizeof(Chan)) != 0) {
       err_ = "shm_open / ftruncate failed for " + n;
@@ -278,43 +281,45 @@ slab_comm_shm::Chan *slab_comm_shm::chan(int rank)
   return reinterpret_cast<Chan *>(seg);
 }
 
-int slab_comm_shm::send_to_above(const void *host, size_t bytes, int status)
+int slab_comm_shm::relay_send(int down, const void *host, size_t bytes, int status)
 {
-  if (rank_ >= world_ - 1) return 0;
+  const char *who = down ? "send_to_below" : "send_to_above";
   if (!host && status == 0) {
-    err_ = "send_to_above: no buffer";
+    err_ = std::string(who) + ": no buffer";
     return PION_GPU_EINVAL;
   }
-  Chan *c = chan(rank_ + 1);
+  Chan *c = chan(down, down ? rank_ - 1 : rank_ + 1);
   if (!c) return PION_GPU_EDEVICE;
+  unsigned long long &sent = img_sent_[down];
   const char *src = static_cast<const char *>(host);
   size_t done = 0;
   bool first = true;
   while (first || done < bytes) {
-    if (int rc = wait_until(&c->consumed, img_sent_, "the rank above to take the previous piece of the image")) return rc;
+    if (int rc = wait_until(&c->consumed, sent, "the neighbouring rank to take the previous piece of the message")) return rc;
     const size_t n = status ? 0 : ((bytes - done < IMG_PIECE) ? bytes - done : IMG_PIECE);
     if (first) c->status = status, c->total = status ? 0 : (long long)bytes;
     if (n) memcpy(c->data, src + done, n);
-    c->written.store(++img_sent_, std::memory_order_release);
+    c->written.store(++sent, std::memory_order_release);
     done += n;
     first = false;
     if (status) break;
   }
   // the receiver has the whole message (and has mapped the segment) when this returns
-  return wait_until(&c->consumed, img_sent_, "the rank above to take the image");
+  return wait_until(&c->consumed, sent, "the neighbouring rank to take the message");
 }
 
-int slab_comm_shm::recv_from_below(void *host, size_t bytes, int *status)
+int slab_comm_shm::relay_recv(int down, void *host, size_t bytes, int *status)
 {
-  if (status) *status = 0;
-  if (rank_ == 0) return 0;
-  Chan *c = chan(rank_);
+  const char *who = down ? "recv_from_above" : "recv_from_below";
+  const char *whom = down ? "above" : "below";
+  Chan *c = chan(down, rank_);
   if (!c) return PION_GPU_EDEVICE;
+  unsigned long long &taken = img_taken_[down];
   char *dst = static_cast<char *>(host);
   size_t done = 0, total = 0;
   bool first = true, fits = true;
   while (first || done < total) {
-    if (int rc = wait_until(&c->written, img_taken_ + 1, "the image of the rank below")) return rc;
+    if (int rc = wait_until(&c->written, taken + 1, down ? "the message of the rank above" : "the image of the rank below")) return rc;
     if (first) {
       if (status) *status = (int)c->status;
       total = (size_t)c->total;
@@ -322,15 +327,34 @@ int slab_comm_shm::recv_from_below(void *host, size_t bytes, int *status)
     }
     const size_t n = (total - done < IMG_PIECE) ? total - done : IMG_PIECE;
     if (fits && n) memcpy(dst + done, c->data, n);
-    c->consumed.store(++img_taken_, std::memory_order_release);
+    c->consumed.store(++taken, std::memory_order_release);
     done += n;
     first = false;
   }
   if (!fits) {
-    err_ = "recv_from_below: the message of the rank below has " + std::to_string(total) + " bytes, expected " + std::to_string(bytes);
+    err_ = std::string(who) + ": the message of the rank " + whom + " has " + std::to_string(total) + " bytes, expected " + std::to_string(bytes);
     return PION_GPU_EINVAL;
   }
   return 0;
+}
+
+int slab_comm_shm::send_to_above(const void *host, size_t bytes, int status)
+{
+  return (rank_ >= world_ - 1) ? 0 : relay_send(0, host, bytes, status);
+}
+int slab_comm_shm::send_to_below(const void *host, size_t bytes, int status)
+{
+  return (rank_ == 0) ? 0 : relay_send(1, host, bytes, status);
+}
+int slab_comm_shm::recv_from_below(void *host, size_t bytes, int *status)
+{
+  if (status) *status = 0;
+  return (rank_ == 0) ? 0 : relay_recv(0, host, bytes, status);
+}
+int slab_comm_shm::recv_from_above(void *host, size_t bytes, int *status)
+{
+  if (status) *status = 0;
+  return (rank_ >= world_ - 1) ? 0 : relay_recv(1, host, bytes, status);
 }
 
 }  // namespace pion_host

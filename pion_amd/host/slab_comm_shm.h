@@ -39,6 +39,10 @@ class slab_comm_shm : public slab_comm {
   bool has_relay() const override { return true; }
   int recv_from_below(void *host, size_t bytes, int *status) override;
   int send_to_above(const void *host, size_t bytes, int status) override;
+  // the same downwards, through segments "<name>_dwn<r>" (the channel rank r receives in, used by r and r + 1)
+  bool has_relay_down() const override { return true; }
+  int recv_from_above(void *host, size_t bytes, int *status) override;
+  int send_to_below(const void *host, size_t bytes, int status) override;
   const std::string &last_error() const override { return err_; }
   int rank() const override { return rank_; }
   int world() const override { return world_; }
@@ -48,7 +52,9 @@ class slab_comm_shm : public slab_comm {
   Box *box(int rank, int side) const;
   int wait_until(const volatile void *counter, unsigned long long want, const char *what);
   struct Chan;  // one channel of the image relay
-  Chan *chan(int rank);
+  Chan *chan(int down, int rank);
+  int relay_send(int down, const void *host, size_t bytes, int status);
+  int relay_recv(int down, void *host, size_t bytes, int *status);
   static size_t img_chan_bytes();
 
   int rank_, world_, up_, down_;
@@ -58,8 +64,9 @@ class slab_comm_shm : public slab_comm {
   long count_;                 // doubles per face
   size_t box_bytes_, seg_bytes_;
   char *seg_;                  // the mapped segment
-  char *img_seg_[2] = {nullptr, nullptr};   // the image relay's channels, mapped at the first receive [0] / send [1]
-  unsigned long long img_sent_ = 0, img_taken_ = 0;   // pieces this rank has written upwards / taken from below
+  // the relay's channels [upwards, downwards], mapped at the first receive [.][0] / send [.][1]
+  char *img_seg_[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  unsigned long long img_sent_[2] = {0, 0}, img_taken_[2] = {0, 0};   // pieces this rank has written / taken, per direction
   double *stage_lo_, *stage_hi_;   // pinned staging: my bottom / top on-grid planes (out), then the ghosts (in)
   bool pinned_;
   int pending_;                // array of the exchange in flight, or -1

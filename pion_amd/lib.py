@@ -117,6 +117,15 @@ def load_library():
         lib.pion_gpu_raytrace_host.argtypes = [_cfgp, _srcp, _dp, _dp, _dp]
         lib.pion_gpu_rt_refused.argtypes = [_cfgp, _srcp]
         lib.pion_gpu_rt_refused.restype = C.c_char_p
+    if hasattr(lib, "pion_gpu_raytrace_part"):   # (likewise)
+        _partp, _ip, _lp = C.POINTER(abi.RtPart), C.POINTER(C.c_int), C.POINTER(C.c_long)
+        lib.pion_gpu_add_rt_source_part.argtypes = [C.c_void_p, _srcp, _partp, _ip, _dp]
+        lib.pion_gpu_rt_chain.argtypes = [_cfgp, _srcp, _partp, _ip, _ip, _ip]
+        lib.pion_gpu_raytrace_part.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.pion_gpu_raytrace_host_part.argtypes = [_cfgp, _srcp, _partp, _dp, _dp, _dp, _dp]
+        lib.pion_gpu_rt_plan_part.argtypes = [_cfgp, _srcp, _partp, _lp, _lp, _lp]
+        lib.pion_gpu_rt_part_refused.argtypes = [_cfgp, _srcp, _partp]
+        lib.pion_gpu_rt_part_refused.restype = C.c_char_p
     lib.pion_gpu_interface_flux.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _dp]
     if hasattr(lib, "pion_gpu_cell_advance"):   # (likewise)
         lib.pion_gpu_cell_advance.argtypes = [C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp]
@@ -152,6 +161,8 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_project_part_count", "pion_gpu_project_part",
     "pion_gpu_add_rt_source", "pion_gpu_raytrace", "pion_gpu_rt_columns", "pion_gpu_rt_count",
     "pion_gpu_pack_columns", "pion_gpu_rt_plan", "pion_gpu_raytrace_host", "pion_gpu_rt_refused",
+    "pion_gpu_add_rt_source_part", "pion_gpu_rt_chain", "pion_gpu_raytrace_part", "pion_gpu_raytrace_host_part",
+    "pion_gpu_rt_plan_part", "pion_gpu_rt_part_refused",
 ]
 
 
@@ -182,6 +193,58 @@ def raytrace_host(cfg, src, P):
     rc = load_library().pion_gpu_raytrace_host(C.byref(cfg), C.byref(abi.rt_source(src)), _p(P), _p(col), _p(dcol))
     if rc != 0:
         raise PionGpuError("raytrace_host", rc, rt_refused(cfg, src) or "invalid arguments")
+    return col, dcol
+
+
+def _partp(part):
+    return None if part is None else C.byref(abi.rt_part(part))
+
+
+def rt_part_refused(cfg, src, part):
+    """pion_gpu_rt_part_refused: the text with which the ray tracer refuses `src` on the part `part` (an abi.RtPart,
+    (plane_lo, global_planes, global_xmin) or None) of a slab run, or None.  Host only: needs no GPU."""
+    t = load_library().pion_gpu_rt_part_refused(C.byref(cfg), C.byref(abi.rt_source(src)), _partp(part))
+    return None if t is None else t.decode()
+
+
+def rt_chain(cfg, src, part):
+    """pion_gpu_rt_chain: (recv_side, send_lo, send_hi) -- the role of the rank that holds `part` in the trace of
+    `src`: abi.RT_RECV_NONE / _BELOW / _ABOVE, and whether its lowest / highest own plane goes to the neighbour below /
+    above.  Host only: needs no GPU."""
+    r, lo, hi = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    rc = load_library().pion_gpu_rt_chain(C.byref(cfg), C.byref(abi.rt_source(src)), _partp(part), C.byref(r),
+                                          C.byref(lo), C.byref(hi))
+    if rc != 0:
+        raise PionGpuError("rt_chain", rc, rt_part_refused(cfg, src, part) or "invalid arguments")
+    return r.value, lo.value, hi.value
+
+
+def rt_plan_part(cfg, src, part):
+    """pion_gpu_rt_plan_part: (launches, workgroups, workgroups_from_vertex) of the tiled kernel for `src` on `part`"""
+    l, w, w0 = C.c_long(-1), C.c_long(-1), C.c_long(-1)
+    rc = load_library().pion_gpu_rt_plan_part(C.byref(cfg), C.byref(abi.rt_source(src)), _partp(part), C.byref(l),
+                                              C.byref(w), C.byref(w0))
+    if rc != 0:
+        raise PionGpuError("rt_plan_part", rc, rt_part_refused(cfg, src, part) or "invalid arguments")
+    return l.value, w.value, w0.value
+
+
+def raytrace_host_part(cfg, src, part, P, face_in=None):
+    """pion_gpu_raytrace_host_part: (col, dcol) of the planes of `part`, each [nz][ny][nx] of cfg, from the host array
+    P of that part and the plane `face_in` the neighbouring rank handed over (None where rt_chain says nothing is
+    received).  Host only: needs no GPU."""
+    P = np.ascontiguousarray(P, dtype=np.float64).reshape(-1)
+    assert P.size == cfg.nvar * abi.ncell_all(cfg)
+    shape = (cfg.ng[2], cfg.ng[1], cfg.ng[0])
+    col, dcol = np.zeros(shape), np.zeros(shape)
+    if face_in is not None:
+        face_in = np.ascontiguousarray(face_in, dtype=np.float64).reshape(-1)
+        assert face_in.size == col.size // shape[0 if cfg.ndim == 3 else 1]
+    rc = load_library().pion_gpu_raytrace_host_part(C.byref(cfg), C.byref(abi.rt_source(src)), _partp(part), _p(P),
+                                                    None if face_in is None else _p(face_in), _p(col), _p(dcol))
+    if rc != 0:
+        raise PionGpuError("raytrace_host_part", rc, rt_part_refused(cfg, src, part)
+                           or "invalid arguments (no face where the chain hands one over?)")
     return col, dcol
 
 
@@ -473,11 +536,24 @@ class GpuSim:
         return n.value
 
     # --- ray-traced column densities
-    def add_rt_source(self, src):
-        """pion_gpu_add_rt_source: (id, pos_used) -- a finite source is moved to the nearest cell vertex per axis"""
+    def add_rt_source(self, src, part=None):
+        """pion_gpu_add_rt_source: (id, pos_used) -- a finite source is moved to the nearest cell vertex per axis.
+        part (an abi.RtPart or (plane_lo, global_planes, global_xmin)): pion_gpu_add_rt_source_part, the handle is a
+        slab of a decomposed run and src a source of the whole domain"""
         sid, pos = C.c_int(-1), (C.c_double * 3)()
-        self._chk(self.lib.pion_gpu_add_rt_source(self.h, C.byref(abi.rt_source(src)), C.byref(sid), pos), "add_rt_source")
+        if part is None:
+            self._chk(self.lib.pion_gpu_add_rt_source(self.h, C.byref(abi.rt_source(src)), C.byref(sid), pos), "add_rt_source")
+        else:
+            self._chk(self.lib.pion_gpu_add_rt_source_part(self.h, C.byref(abi.rt_source(src)), C.byref(abi.rt_part(part)),
+                                                           C.byref(sid), pos), "add_rt_source_part")
         return sid.value, tuple(pos)
+
+    def raytrace_part(self, sid, which=0, face_in_ptr=None, face_out_lo_ptr=None, face_out_hi_ptr=None):
+        """pion_gpu_raytrace_part: the columns of source sid alone; face_in_ptr: device buffer of the plane received
+        (None where nothing is), face_out_*_ptr: device buffers for the lowest and highest own plane of col (None: not
+        written), each rt_count(1) doubles; enqueued"""
+        self._chk(self.lib.pion_gpu_raytrace_part(self.h, int(which), int(sid), C.c_void_p(face_in_ptr),
+                                                  C.c_void_p(face_out_lo_ptr), C.c_void_p(face_out_hi_ptr)), "raytrace_part")
 
     def raytrace(self, which=0):
         """pion_gpu_raytrace: the columns of every source from array `which` (0 = P, 1 = Ph); enqueued"""
