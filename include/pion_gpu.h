@@ -249,6 +249,29 @@ typedef struct pion_gpu_proj_part {
 long pion_gpu_project_part_count(void *handle, int axis, int nfields, const pion_gpu_proj_part *part);
 int pion_gpu_project_part(void *handle, int which, int axis, int nfields, const pion_gpu_proj_field *fields,
                           const pion_gpu_proj_part *part, void *dimg);
+/* A 2-D cylindrical (z,R) grid seen at an angle to its symmetry axis (pion_amd/csrc/dev_project_angle.h states the rule):
+ * the reference's analysis/projection/angle_projection.cpp as written -- per pixel the ray, a hyperbola in the (z,R)
+ * plane, is walked from cell to cell (get_start_of_ray, get_entry_exit_points, generate_angle_image) and every field
+ * gains weight * (its value at the cell), weight = |sqrt(R_entry^2 - b^2) - sqrt(R_exit^2 - b^2)| / sin(angle).
+ * angle_deg: the angle between the line of sight and the axis, finite, 0 < angle_deg < 90; tan and 1 / sin of it are
+ * evaluated once on the host.  n_extra = (int) fabs(Xmax[R] / tan(angle) / dx) columns are added at each end in z:
+ * NI = NZ + 2 n_extra, NJ = NR, pixel (i, j) centred at z = Xmin[Z] + (i - n_extra + 0.5) dx, R = Xmin[R] + (j + 0.5) dx;
+ * the image's pixels are dx sin(angle) wide on the sky.  The fields are pion_gpu_project's.
+ *   pion_gpu_project_angle_count   doubles of one call, nfields NR NI; *n_extra (may be null) receives n_extra
+ *   pion_gpu_project_angle         writes [nfields][NR][NI] native-endian doubles into the DEVICE buffer dbuf from array
+ *                                  `which`; enqueued on the compute stream, returns at once.  Only on-grid cells are read.
+ *                                  Both floating-point builds give the same bits, and the bits of
+ *                                  pion_host_project_angle_on_host wherever the fields have b == 0.
+ *   pion_gpu_project_angle_status  synchronises; *ncapped = the pixels since the last call one of whose ray loops reached
+ *                                  the rule's limit of 2 (NZ + NR) + 8 trips before its end (none is expected: such an
+ *                                  image is not to be used), and clears the count.
+ * The count returns < 0, and both EINVAL with a text, for: every grid that is not 2-D cylindrical; NR == 1; a handle
+ * with a PION_BC_SLAB face (rays are not carried from rank to rank); an angle that is not finite or outside (0, 90) -- 90
+ * is PION_PROJ_AXIS_PERP's --; nfields NR NI above 2^31 - 1 (small angles); every field pion_gpu_project refuses; a null
+ * buffer. */
+long pion_gpu_project_angle_count(void *handle, double angle_deg, int nfields, int *n_extra);
+int pion_gpu_project_angle(void *handle, int which, double angle_deg, int nfields, const pion_gpu_proj_field *fields, void *dbuf);
+int pion_gpu_project_angle_status(void *handle, long *ncapped);
 /* Ray-traced column densities (pion_amd/csrc/dev_raytrace.h states the rules): the reference's short-characteristics
  * tracer raytracer_USC (raytracing/raytracer_SC.cpp), which leaves per cell and source the column density TO the cell and
  * the column THROUGH it in extra_data.  Here, per source, two arrays of the ON-GRID cells only, [nz][ny][nx] doubles:

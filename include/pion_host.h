@@ -121,6 +121,27 @@ int pion_host_sim_set_output_filetype(void *sim, int type);
  *   above it returns EINVAL, no file appears, no rank blocks. */
 int pion_host_sim_write_projection(void *sim, const char *path, int axis, int nfields, const pion_gpu_proj_field *fields);
 int pion_host_sim_set_projection_output(void *sim, int axis, int nfields, const pion_gpu_proj_field *fields);
+/* A cylindrical (z,R) grid seen at angle_deg (0 < angle_deg < 90) to its symmetry axis (pion_gpu_project_angle; the rule:
+ * pion_amd/csrc/dev_project_angle.h, the reference's analysis/projection/angle_projection.cpp as written).
+ * pion_host_sim_write_projection_angle: a FITS file with the primary header of pion_host_sim_write_fits plus
+ *   pion_proj_angle (degrees), pion_proj_n_extra, pion_proj_pixdx (the pixel size along image x, dx sin(angle)),
+ *   pion_proj_pixz0 (the image's origin in z: the centre of pixel (0, 0) times sin(angle); project2D.cpp:446-449) and
+ *   the per-field keys of pion_host_sim_write_projection; then one double-precision IMAGE extension per field, NAXIS1 =
+ *   NI = NZ + 2 n_extra, NAXIS2 = NR, EXTNAME = the field's name, big-endian, in units of (code units of the field) *
+ *   length.  Written under a ".part" name and renamed.  The images are made on the device; a backend table without the
+ *   two project_angle entries downloads the state and runs the same rule in a host loop.
+ * pion_host_sim_set_projection_angle_output: from now on every regular output of pion_host_sim_time_int is accompanied
+ *   by <base>_proja_<rank, 4 digits>.<step, 8 digits>.fits; nfields = 0 turns that off.  Independent of
+ *   pion_host_sim_set_projection_output.  Cadence, the time-step clip, checkpoints and every dt are untouched.
+ * pion_host_sim_write_projection_angle_trips: the writer over the host loop with the ray loops' trip limit given instead
+ *   of the rule's own 2 (NZ + NR) + 8 (trip_limit >= 1): for tests of the refusal below.
+ * EINVAL and a text, never an exit, and no file: everything pion_gpu_project_angle refuses; a path that cannot be
+ * created; a sim that is one rank of several (a slab extent or a communicator of more than one rank: rays are not
+ * carried from rank to rank); an image with a pixel whose ray loop reached the trip limit. */
+int pion_host_sim_write_projection_angle(void *sim, const char *path, double angle_deg, int nfields, const pion_gpu_proj_field *fields);
+int pion_host_sim_set_projection_angle_output(void *sim, double angle_deg, int nfields, const pion_gpu_proj_field *fields);
+int pion_host_sim_write_projection_angle_trips(void *sim, const char *path, double angle_deg, int nfields,
+                                               const pion_gpu_proj_field *fields, int trip_limit);
 /* Ray-traced column densities (pion_gpu_raytrace; the rules: pion_amd/csrc/dev_raytrace.h, after the reference's
  * short-characteristics tracer raytracing/raytracer_SC.cpp).
  * pion_host_sim_add_rt_source: Add_Source (:1183-1314) for one radiation source, pion_gpu_add_rt_source on the loop's
@@ -164,6 +185,20 @@ int pion_host_project_on_host(const pion_gpu_config *cfg, int axis, int nfields,
                               const double *A, double *img);
 int pion_host_project_part_on_host(const pion_gpu_config *cfg, int axis, int nfields, const pion_gpu_proj_field *fields,
                                    const pion_gpu_proj_part *part, const double *A, double *img);
+/* The rule of the inclined projection as host functions (pion_amd/csrc/dev_project_angle.h), likewise.
+ *   pion_host_project_angle_count:   doubles of the images, nfields NR NI, and *n_extra (may be NULL); < 0 for what
+ *                                    pion_gpu_project_angle_count refuses, *why (may be NULL) then points to the text
+ *   pion_host_project_angle_on_host: every pixel by angle_pixel in a host loop, img = [nfields][NR][NI]
+ *   pion_host_project_angle_rule:    the same with the ray loops' trip limit given (trip_limit >= 1), *ncapped = the
+ *                                    pixels whose loop reached it; tan_angle, inv_sin (either may be NULL): the two
+ *                                    numbers of the angle the rule was handed
+ * EINVAL for what is refused or null. */
+long pion_host_project_angle_count(const pion_gpu_config *cfg, double angle_deg, int nfields, int *n_extra, const char **why);
+int pion_host_project_angle_on_host(const pion_gpu_config *cfg, double angle_deg, int nfields, const pion_gpu_proj_field *fields,
+                                    const double *A, double *img);
+int pion_host_project_angle_rule(const pion_gpu_config *cfg, double angle_deg, int trip_limit, int nfields,
+                                 const pion_gpu_proj_field *fields, const double *A, double *img, long *ncapped,
+                                 double *tan_angle, double *inv_sin);
 typedef struct pion_host_snapshot_info {
   double t_start, t_finish, t_sim, min_timestep, last_dt;   /* SimPM.starttime, finishtime, simtime, min_timestep, last_dt */
   double opfreq_time, next_optime;

@@ -418,6 +418,8 @@ void pion_gpu_destroy(void *handle)
   hipFree(h->dscr_count);
   hipFree(h->ddE);
   hipFree(h->dfits_bad);
+  hipFree(h->dangle_vals);
+  hipFree(h->dangle_capped);
   if (h->bstream) hipStreamDestroy(h->bstream);
   if (h->ev_pre) hipEventDestroy(h->ev_pre);
   if (h->ev_bdone) hipEventDestroy(h->ev_bdone);

@@ -107,6 +107,12 @@ struct Handle {
   // FITS read (pion_output.hip): rejected elements counted by k_unpack_fits since the last pion_gpu_unpack_fits_status;
   // allocated at the first unpack
   unsigned long long *dfits_bad = nullptr;
+  // inclined projection (pion_project.hip): the field values of every on-grid cell, [nfields][NR][NZ], grown at the call
+  // that needs more, and the pixels whose ray loop reached its trip limit since the last pion_gpu_project_angle_status;
+  // both allocated at the first pion_gpu_project_angle
+  double *dangle_vals = nullptr;
+  long angle_vals_n = 0;
+  unsigned long long *dangle_capped = nullptr;
   // radiation sources (pion_raytrace.hip): the sources and their column arrays, created by the first
   // pion_gpu_add_rt_source; null: the handle traces nothing
   struct RtState *rt = nullptr;

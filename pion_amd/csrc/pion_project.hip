@@ -22,10 +22,13 @@
 // image of the whole domain: k_project_yz_along (the sum enters with the carried value), k_project_yz_rows /
 // k_project_x_rows (the rank's rows at their row offset), k_project_abel_part.  The whole-grid kernels are left as they
 // were, instruction for instruction.
+// pion_gpu_project_angle is the same grid seen at an angle to the axis (dev_project_angle.h): k_angle_values and
+// k_project_angle, described where they stand.
 // blockIdx.y: the field.  Unit, cell and buffer indices are long; the launch grid is checked against 2^31 - 1.
 #include <hip/hip_runtime.h>
 
 #include "dev_project.h"
+#include "dev_project_angle.h"
 #include "pion_handle.h"
 
 using namespace pion;
@@ -288,6 +291,42 @@ k_project_abel_part(const double *__restrict__ A, double *out, const GridDesc g,
     }
 }
 
+// ---- the inclined projection of a cylindrical grid (dev_project_angle.h).  Two launches per call:
+//   k_angle_values   dev_project.h's proj_value of every field at every on-grid cell, once, into V = [nfields][NR][NZ]
+//                    (blockIdx.y: the field): the exp / log of T^b is paid per cell, not per visit, and the walk only loads.
+//   k_project_angle  a lane per pixel, a wavefront = 64 consecutive i of one impact row j: the rays of neighbouring lanes
+//                    are copies shifted by one cell in z, so they take the same branches and load adjacent cells.  All
+//                    fields are summed in the one walk.  A pixel is a property of (i, j) alone: angle_pixel, the host
+//                    loop's function.  No LDS, no waiting on another workgroup; a capped pixel adds 1 to *capped
+//                    (a plain atomic that nothing polls).
+__global__ void __launch_bounds__(64 * PRJ_WAVES)
+k_angle_values(const double *__restrict__ A, double *__restrict__ V, const GridDesc g, const OutputCfg o, const ProjFields F)
+{
+  const long ncells = (long)g.ng[0] * g.ng[1];
+  const long u = (long)blockIdx.x * (64 * PRJ_WAVES) + threadIdx.x;
+  if (u >= ncells) return;
+  const long ir = u / g.ng[0], iz = u - ir * g.ng[0];
+  const long c = (g.nbc[0] + iz) + g.sy * (g.nbc[1] + ir);
+  V[(long)blockIdx.y * ncells + u] = proj_value(g, o, F.f[blockIdx.y], A, c);
+}
+
+__global__ void __launch_bounds__(64 * PRJ_WAVES)
+k_project_angle(const double *__restrict__ V, double *__restrict__ out, const AngleGeom q, const int nfields, const int trip_limit,
+                unsigned long long *__restrict__ capped)
+{
+  const int nseg = (q.ni + 63) / 64;
+  const long u = (long)blockIdx.x * PRJ_WAVES + (threadIdx.x >> 6);   // unit: (impact row j, 64 pixels of it)
+  if (u >= (long)q.nr * nseg) return;
+  const long j = u / nseg;
+  const long i = (u - j * nseg) * 64 + (long)(threadIdx.x & 63);
+  if (i >= q.ni) return;
+  double ans[PION_PROJ_MAX_FIELDS];
+  if (angle_pixel(q, V, nfields, i, (int)j, trip_limit, ans)) atomicAdd(capped, 1ULL);
+#pragma unroll
+  for (int f = 0; f < PION_PROJ_MAX_FIELDS; f++)
+    if (f < nfields) out[((long)f * q.nr + j) * q.ni + i] = ans[f];
+}
+
 OutputCfg project_cfg(const Handle *h)
 {
   OutputCfg o = out_cfg(h->cfg);
@@ -408,6 +447,79 @@ int pion_gpu_project_part(void *handle, int which, int axis, int nfields, const 
   else
     hipLaunchKernelGGL(k_project_yz_rows, grid, block, 0, h->stream, A, img, h->g, o, F, q, pp.plane_lo, njg);
   HCHECK(h, hipGetLastError());
+  return 0;
+}
+
+long pion_gpu_project_angle_count(void *handle, double angle_deg, int nfields, int *n_extra)
+{
+  Handle *h = (Handle *)handle;
+  if (!h) return PION_GPU_EINVAL;
+  AngleGeom q;
+  if (const char *why = angle_refused(h->g, h->cfg, angle_deg, nfields, &q)) {
+    h->err = why;
+    return PION_GPU_EINVAL;
+  }
+  if (n_extra) *n_extra = q.n_extra;
+  return angle_count(q, nfields);
+}
+
+int pion_gpu_project_angle(void *handle, int which, double angle_deg, int nfields, const pion_gpu_proj_field *fields, void *dbuf)
+{
+  Handle *h = use(handle);
+  if (!h) return PION_GPU_EINVAL;
+  const OutputCfg o = project_cfg(h);
+  AngleGeom q;
+  const char *why = angle_refused(h->g, h->cfg, angle_deg, nfields, &q);
+  if (!why) why = proj_refused_fields(o, nfields, fields);
+  if (!why && (which < 0 || which > 1)) why = "project: which is 0 (P) or 1 (Ph)";
+  if (!why && !dbuf) why = "project: no buffer";
+  if (why) {
+    h->err = why;
+    return PION_GPU_EINVAL;
+  }
+  const long ncells = (long)q.nr * q.nz;
+  const long nblk_v = (ncells + 64 * PRJ_WAVES - 1) / (64 * PRJ_WAVES);
+  const long nblk = ((long)q.nr * ((q.ni + 63) / 64) + PRJ_WAVES - 1) / PRJ_WAVES;
+  if (nblk > (1L << 31) - 1 || nblk_v > (1L << 31) - 1) {
+    h->err = "project: the image is too large for one launch";
+    return PION_GPU_EINVAL;
+  }
+  // (the scratch of the handle: a launch of an earlier call that reads the old one has to end before it is freed, and
+  // hipFree waits for it)
+  if (h->angle_vals_n < (long)nfields * ncells) {
+    if (h->dangle_vals) HCHECK(h, hipFree(h->dangle_vals));
+    h->dangle_vals = nullptr, h->angle_vals_n = 0;
+    HCHECK(h, hipMalloc((void **)&h->dangle_vals, (size_t)nfields * ncells * sizeof(double)));
+    h->angle_vals_n = (long)nfields * ncells;
+  }
+  if (!h->dangle_capped) {
+    HCHECK(h, hipMalloc((void **)&h->dangle_capped, sizeof(unsigned long long)));
+    HCHECK(h, hipMemsetAsync(h->dangle_capped, 0, sizeof(unsigned long long), h->stream));
+  }
+  ProjFields F;
+  F.n = nfields;
+  for (int i = 0; i < PION_PROJ_MAX_FIELDS; i++) F.f[i] = fields[i < nfields ? i : 0];
+  const double *A = which ? h->dPh : h->dP;
+  const dim3 block(64 * PRJ_WAVES);
+  hipLaunchKernelGGL(k_angle_values, dim3((unsigned)nblk_v, (unsigned)nfields), block, 0, h->stream, A, h->dangle_vals, h->g, o, F);
+  HCHECK(h, hipGetLastError());
+  hipLaunchKernelGGL(k_project_angle, dim3((unsigned)nblk), block, 0, h->stream, (const double *)h->dangle_vals, (double *)dbuf, q,
+                     nfields, angle_trip_limit(q), h->dangle_capped);
+  HCHECK(h, hipGetLastError());
+  return 0;
+}
+
+int pion_gpu_project_angle_status(void *handle, long *ncapped)
+{
+  Handle *h = use(handle);
+  if (!h || !ncapped) return PION_GPU_EINVAL;
+  *ncapped = 0;
+  if (!h->dangle_capped) return 0;   // nothing was projected yet
+  unsigned long long n = 0;
+  HCHECK(h, hipMemcpyAsync(&n, h->dangle_capped, sizeof n, hipMemcpyDeviceToHost, h->stream));
+  HCHECK(h, hipMemsetAsync(h->dangle_capped, 0, sizeof n, h->stream));
+  HCHECK(h, hipStreamSynchronize(h->stream));
+  *ncapped = (long)n;
   return 0;
 }
 }

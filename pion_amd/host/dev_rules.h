@@ -10,6 +10,7 @@
 #endif
 #include "../csrc/dev_output.h"
 #include "../csrc/dev_project.h"
+#include "../csrc/dev_project_angle.h"
 #include "../csrc/dev_raytrace.h"
 
 namespace pion_host {

@@ -124,6 +124,16 @@ typedef struct pion_backend {
   int (*add_rt_source_part)(void *handle, const pion_gpu_rt_source *src, const pion_gpu_rt_part *part, int *id,
                             double *pos_used);
   int (*raytrace_part_faces)(void *handle, int which, int id, const double *face_in, double *face_lo, double *face_hi);
+  /* The inclined projection of a (z,R) grid (projection_io.cpp; the rule: pion_amd/csrc/dev_project_angle.h;
+   * pion_gpu_project_angle).  These two entries are read ONLY inside sim_control_gpu::write_projection_angle: any
+   * other caller may hand the loop a table that ends before them.  Both NULL: the writer takes array 0 through
+   * download and runs the rule in a host loop.
+   *   project_angle_count:   pion_gpu_project_angle_count
+   *   project_angle_to_host: project array P on the device, copy the images into `host`, wait; *ncapped = the pixels
+   *                          whose ray loop reached the trip limit (pion_gpu_project_angle_status) */
+  long (*project_angle_count)(void *handle, double angle_deg, int nfields, int *n_extra);
+  int (*project_angle_to_host)(void *handle, double angle_deg, int nfields, const pion_gpu_proj_field *fields, double *host,
+                               long *ncapped);
 } pion_backend;
 
 /* the product's backend: libpion_gpu.so */

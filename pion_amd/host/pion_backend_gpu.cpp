@@ -218,6 +218,20 @@ int gpu_project_part_to_host(void *h, int axis, int nfields, const pion_gpu_proj
     return PION_GPU_EDEVICE;
   return hipStreamSynchronize(s) == hipSuccess ? 0 : PION_GPU_EDEVICE;
 }
+// the inclined images of one call: projected into slot 0's device buffer, copied, waited for (by the status call)
+int gpu_project_angle_to_host(void *h, double angle_deg, int nfields, const pion_gpu_proj_field *fields, double *host, long *ncapped)
+{
+  const long n = pion_gpu_project_angle_count(h, angle_deg, nfields, nullptr);
+  if (n < 0) return (int)n;
+  if (!host || !ncapped) return PION_GPU_EINVAL;
+  Staging *st;
+  if (int rc = staging_slot(h, 0, n, &st)) return rc;
+  if (int rc = pion_gpu_project_angle(h, 0, angle_deg, nfields, fields, st->dev[0])) return rc;
+  hipStream_t s = compute_stream_of(h);
+  if (hipMemcpyAsync(host, st->dev[0], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess)
+    return PION_GPU_EDEVICE;
+  return pion_gpu_project_angle_status(h, ncapped);
+}
 // a plane range of one column array: packed big-endian into the slot's device buffer, then copied
 int gpu_columns_to_host_begin(void *h, int id, int what, int plane_lo, int plane_hi, int slot)
 {
@@ -304,6 +318,8 @@ const pion_backend k_gpu = {
     gpu_columns_to_host_begin,
     pion_gpu_add_rt_source_part,
     gpu_raytrace_part_faces,
+    pion_gpu_project_angle_count,
+    gpu_project_angle_to_host,
 };
 
 }  // namespace

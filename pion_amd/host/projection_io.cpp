@@ -5,6 +5,9 @@
 // project_* entries; a table without them downloads array 0 and runs dev_project.h's functions in a host loop.  An
 // image is small, so it is written whole, through the file object of out_file.h.  One rank of a slab run hands the
 // image of the whole domain from rank to rank (relay_part), and the last rank writes the one file.
+// write_projection_angle / set_projection_angle_output: a (z,R) grid seen at an angle to its axis (the rule:
+// pion_amd/csrc/dev_project_angle.h), the same kind of file with pion_proj_angle, _n_extra, _pixdx, _pixz0 in place of
+// pion_proj_axis; single rank only.
 #include <string>
 #include <vector>
 
@@ -54,6 +57,55 @@ static void project_part_on_host(const pion::GridDesc &g, const pion::OutputCfg 
                    : pion::proj_column(g, o, fields[f], q, axis, A, first);
       }
   }
+}
+
+// the file of both writers: `params` (the primary header so far) gains the per-field keys; then one big-endian
+// double-precision IMAGE extension [nj][ni] per field, img = [nfields][nj][ni] native doubles
+static int write_image_file(const char *who, const char *path, std::string &err, std::vector<snapshot_param> &params, int nfields,
+                            const pion_gpu_proj_field *fields, long ni, long nj, const std::vector<double> &img)
+{
+  for (int i = 0; i < nfields; i++) {
+    const std::string k = "pion_proj_" + std::to_string(i) + "_";
+    params.push_back({k + "a", std::to_string(fields[i].a), 'i'});
+    params.push_back({k + "var", std::to_string(fields[i].var), 'i'});
+    params.push_back({k + "coef", fmt_d(fields[i].coef), 'd'});
+    params.push_back({k + "b", fmt_d(fields[i].b), 'd'});
+  }
+  const long npix = nj * ni, n = nfields * npix;
+  std::vector<unsigned long long> R((size_t)n);
+  for (long k = 0; k < n; k++) R[(size_t)k] = pion::out_be64(img[(size_t)k]);
+  const std::string primary = fits_primary_header(params);
+  const long naxis[2] = {ni, nj};
+  std::vector<std::string> ext((size_t)nfields);
+  for (int i = 0; i < nfields; i++) ext[(size_t)i] = fits_image_header(fields[i].name, 2, naxis);
+  const fits_layout L(primary, ext, npix * (long)sizeof(double));
+
+  PartFile f(who, path, err);
+  if (!f.ok()) return PION_GPU_EINVAL;
+  int rc = L.start(f);
+  for (int i = 0; i < nfields && !rc; i++) rc = f.write(R.data() + (size_t)i * npix, (size_t)npix * sizeof(double), L.data_at(i));
+  return f.commit(rc);
+}
+
+// dev_project_angle.h in a host loop: the field values of every on-grid cell once, then angle_pixel per pixel.
+// img = [nfields][NR][NI]; returns the pixels whose ray loop reached trip_limit
+static long project_angle_on_host(const pion::GridDesc &g, const pion::OutputCfg &o, const pion::AngleGeom &q, int nfields,
+                                  const pion_gpu_proj_field *fields, const double *A, int trip_limit, double *img)
+{
+  const long ncells = (long)q.nr * q.nz;
+  std::vector<double> V((size_t)nfields * ncells);
+  for (int f = 0; f < nfields; f++)
+    for (long ir = 0; ir < q.nr; ir++)
+      for (long iz = 0; iz < q.nz; iz++)
+        V[(size_t)(f * ncells + ir * q.nz + iz)] = pion::proj_value(g, o, fields[f], A, (g.nbc[0] + iz) + g.sy * (g.nbc[1] + ir));
+  long ncapped = 0;
+  for (int j = 0; j < q.nr; j++)
+    for (long i = 0; i < q.ni; i++) {
+      double ans[PION_PROJ_MAX_FIELDS];
+      ncapped += pion::angle_pixel(q, V.data(), nfields, i, j, trip_limit, ans);
+      for (int f = 0; f < nfields; f++) img[((long)f * q.nr + j) * q.ni + i] = ans[f];
+    }
+  return ncapped;
 }
 
 // one rank of a slab run whose images are assembled along the ranks: a slab extent AND a communicator of more than
@@ -196,29 +248,91 @@ int sim_control_gpu::write_projection(const char *path, int axis, int nfields, c
     }
   }
   if (rc) return rc;
-  const long npix = (long)q.nj * q.ni, n = pion::proj_count(q, nfields);
   params.push_back({"pion_proj_axis", std::to_string(axis), 'i'});
-  for (int i = 0; i < nfields; i++) {
-    const std::string k = "pion_proj_" + std::to_string(i) + "_";
-    params.push_back({k + "a", std::to_string(fields[i].a), 'i'});
-    params.push_back({k + "var", std::to_string(fields[i].var), 'i'});
-    params.push_back({k + "coef", fmt_d(fields[i].coef), 'd'});
-    params.push_back({k + "b", fmt_d(fields[i].b), 'd'});
-  }
-  // 2. the file: big-endian
-  std::vector<unsigned long long> R((size_t)n);
-  for (long k = 0; k < n; k++) R[(size_t)k] = pion::out_be64(img[(size_t)k]);
-  const std::string primary = fits_primary_header(params);
-  const long naxis[2] = {q.ni, q.nj};
-  std::vector<std::string> ext((size_t)nfields);
-  for (int i = 0; i < nfields; i++) ext[(size_t)i] = fits_image_header(fields[i].name, 2, naxis);
-  const fits_layout L(primary, ext, npix * (long)sizeof(double));
+  // 2. the file
+  return write_image_file("write_projection", path, io_error_, params, nfields, fields, q.ni, q.nj, img);
+}
 
-  PartFile f("write_projection", path, io_error_);
-  if (!f.ok()) return PION_GPU_EINVAL;
-  rc = L.start(f);
-  for (int i = 0; i < nfields && !rc; i++) rc = f.write(R.data() + (size_t)i * npix, (size_t)npix * sizeof(double), L.data_at(i));
-  return f.commit(rc);
+// ---- the inclined projection of a (z,R) grid (dev_project_angle.h)
+int sim_control_gpu::projection_angle_refused(double angle_deg, int nfields, const pion_gpu_proj_field *fields, const char *who)
+{
+  const char *why = nullptr;
+  if (slab.set || (comm_ && comm_->world() > 1))
+    why = "project_angle: this sim is one rank of several, and rays are not carried from rank to rank";
+  pion::AngleGeom q;
+  if (!why) why = pion::angle_refused(grid_desc(cfg), cfg, angle_deg, nfields, &q);
+  if (!why) why = pion::proj_refused_fields(pion::out_cfg(cfg), nfields, fields);
+  if (!why) return 0;
+  io_error_ = std::string(who) + ": " + why;
+  return PION_GPU_EINVAL;
+}
+
+int sim_control_gpu::set_projection_angle_output(double angle_deg, int nfields, const pion_gpu_proj_field *fields)
+{
+  io_error_.clear();
+  if (nfields == 0) {
+    proja_fields_.clear();
+    return 0;
+  }
+  if (int rc = projection_angle_refused(angle_deg, nfields, fields, "set_projection_angle_output")) return rc;
+  proja_angle_ = angle_deg;
+  proja_fields_.assign(fields, fields + nfields);
+  return 0;
+}
+
+int sim_control_gpu::write_projection_angle(const char *path, double angle_deg, int nfields, const pion_gpu_proj_field *fields,
+                                            int trip_limit)
+{
+  const char *who = "write_projection_angle";
+  if (int rc = path_refused(who, path)) return rc;
+  if (int rc = projection_angle_refused(angle_deg, nfields, fields, who)) return rc;
+  if (trip_limit < 0) {
+    io_error_ = std::string(who) + ": the trip limit is not negative";
+    return PION_GPU_EINVAL;
+  }
+  std::vector<snapshot_param> params;
+  long nloc = 0;
+  if (int rc = writer_params(who, params, nloc)) return rc;
+
+  // 1. the images, native doubles [nfields][NR][NI]
+  const pion::GridDesc g = grid_desc(cfg);
+  pion::AngleGeom q;
+  (void)pion::angle_refused(g, cfg, angle_deg, nfields, &q);
+  const long n = pion::angle_count(q, nfields);
+  std::vector<double> img((size_t)n, 0.0);
+  long ncapped = 0;
+  if (trip_limit == 0 && be_->project_angle_count && be_->project_angle_to_host) {
+    int n_extra = -1;
+    if (be_->project_angle_count(h_, angle_deg, nfields, &n_extra) != n || n_extra != q.n_extra) {
+      io_error_ = std::string(who) + ": the backend refuses: " + last_error();
+      return PION_GPU_EINVAL;
+    }
+    if (int rc = be_->project_angle_to_host(h_, angle_deg, nfields, fields, img.data(), &ncapped)) {
+      io_error_ = std::string(who) + ": project_angle_to_host failed: " + last_error();
+      return rc;
+    }
+  }
+  else {
+    std::vector<double> A((size_t)cfg.nvar * g.ncell);
+    if (int rc = be_->download(h_, 0, A.data())) {
+      io_error_ = std::string(who) + ": download failed: " + last_error();
+      return rc;
+    }
+    ncapped = project_angle_on_host(g, pion::out_cfg(cfg), q, nfields, fields, A.data(),
+                                    trip_limit ? trip_limit : pion::angle_trip_limit(q), img.data());
+  }
+  if (ncapped) {
+    io_error_ = std::string(who) + ": " + std::to_string(ncapped) + " pixel(s) reached the trip limit of their ray loop: "
+                "the image is not complete and no file is written";
+    return PION_GPU_EINVAL;
+  }
+  double tn, invst, st;
+  pion::angle_numbers(angle_deg, &tn, &invst, &st);
+  params.push_back({"pion_proj_angle", fmt_d(angle_deg), 'd'});
+  params.push_back({"pion_proj_n_extra", std::to_string(q.n_extra), 'i'});
+  params.push_back({"pion_proj_pixdx", fmt_d(q.dx * st), 'd'});                        // project2D.cpp:449
+  params.push_back({"pion_proj_pixz0", fmt_d(pion::angle_pos_z(q, 0) * st), 'd'});     // project2D.cpp:446-447
+  return write_image_file(who, path, io_error_, params, nfields, fields, q.ni, q.nr, img);
 }
 
 // ---- C view of dev_project.h's host functions (ctypes: tests; a caller that assembles images with a transport of its
@@ -254,6 +368,47 @@ int pion_host_project_part_on_host(const pion_gpu_config *cfg, int axis, int nfi
   const pion::ProjPart pp = {part->plane_lo, part->global_planes, part->last ? 1 : 0, part->global_xmin};
   project_part_on_host(grid_desc(*cfg), pion::out_cfg(*cfg), axis, nfields, fields, pp, A, img);
   return 0;
+}
+// dev_project_angle.h: the count, and angle_pixel over every pixel
+long pion_host_project_angle_count(const pion_gpu_config *cfg, double angle_deg, int nfields, int *n_extra, const char **why)
+{
+  if (why) *why = nullptr;
+  if (!cfg) return PION_GPU_EINVAL;
+  pion::AngleGeom q;
+  if (const char *w = pion::angle_refused(grid_desc(*cfg), *cfg, angle_deg, nfields, &q)) {
+    if (why) *why = w;
+    return PION_GPU_EINVAL;
+  }
+  if (n_extra) *n_extra = q.n_extra;
+  return pion::angle_count(q, nfields);
+}
+// trip_limit 0: the rule's own
+static int angle_rule(const pion_gpu_config *cfg, double angle_deg, int trip_limit, int nfields, const pion_gpu_proj_field *fields,
+                      const double *A, double *img, long *ncapped, double *tan_angle, double *inv_sin)
+{
+  if (!cfg || !A || !img) return PION_GPU_EINVAL;
+  const pion::GridDesc g = grid_desc(*cfg);
+  pion::AngleGeom q;
+  if (pion::angle_refused(g, *cfg, angle_deg, nfields, &q) || pion::proj_refused_fields(pion::out_cfg(*cfg), nfields, fields))
+    return PION_GPU_EINVAL;
+  if (tan_angle) *tan_angle = q.tn;
+  if (inv_sin) *inv_sin = q.invst;
+  const long n = project_angle_on_host(g, pion::out_cfg(*cfg), q, nfields, fields, A,
+                                       trip_limit ? trip_limit : pion::angle_trip_limit(q), img);
+  if (ncapped) *ncapped = n;
+  return 0;
+}
+int pion_host_project_angle_rule(const pion_gpu_config *cfg, double angle_deg, int trip_limit, int nfields,
+                                 const pion_gpu_proj_field *fields, const double *A, double *img, long *ncapped,
+                                 double *tan_angle, double *inv_sin)
+{
+  if (!ncapped || trip_limit < 1) return PION_GPU_EINVAL;
+  return angle_rule(cfg, angle_deg, trip_limit, nfields, fields, A, img, ncapped, tan_angle, inv_sin);
+}
+int pion_host_project_angle_on_host(const pion_gpu_config *cfg, double angle_deg, int nfields, const pion_gpu_proj_field *fields,
+                                    const double *A, double *img)
+{
+  return angle_rule(cfg, angle_deg, 0, nfields, fields, A, img, nullptr, nullptr, nullptr);
 }
 }
 

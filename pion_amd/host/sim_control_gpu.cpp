@@ -224,6 +224,13 @@ std::string sim_control_gpu::projection_name(long step) const
   return T.outfile + b;
 }
 
+std::string sim_control_gpu::projection_angle_name(long step) const
+{
+  char b[64];
+  snprintf(b, sizeof b, "_proja_%04d.%08ld.fits", comm_ ? comm_->rank() : 0, step);
+  return T.outfile + b;
+}
+
 std::string sim_control_gpu::columns_name(long step) const
 {
   char b[64];
@@ -267,6 +274,10 @@ int sim_control_gpu::output_data()
   if (int rc = write_output(output_name(T.timestep).c_str())) return rc;
   if (!proj_fields_.empty())
     if (int rc = write_projection(projection_name(T.timestep).c_str(), proj_axis_, (int)proj_fields_.size(), proj_fields_.data()))
+      return rc;
+  if (!proja_fields_.empty())
+    if (int rc = write_projection_angle(projection_angle_name(T.timestep).c_str(), proja_angle_, (int)proja_fields_.size(),
+                                        proja_fields_.data()))
       return rc;
   if (column_output_)
     if (int rc = write_columns(columns_name(T.timestep).c_str())) return rc;
@@ -440,6 +451,35 @@ int pion_host_sim_set_projection_output(void *s, int axis, int nfields, const pi
   auto *c = static_cast<pion_host::sim_control_gpu *>(s);
   try {
     return io_result(c, c->set_projection_output(axis, nfields, fields));
+  }
+  catch (const std::exception &e) {
+    g_last_exception = e.what();
+    return PION_GPU_EINVAL;
+  }
+}
+int pion_host_sim_write_projection_angle_trips(void *s, const char *path, double angle_deg, int nfields,
+                                               const pion_gpu_proj_field *fields, int trip_limit)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  try {
+    return io_result(c, c->write_projection_angle(path, angle_deg, nfields, fields, trip_limit));
+  }
+  catch (const std::exception &e) {
+    g_last_exception = e.what();
+    return PION_GPU_EINVAL;
+  }
+}
+int pion_host_sim_write_projection_angle(void *s, const char *path, double angle_deg, int nfields, const pion_gpu_proj_field *fields)
+{
+  return pion_host_sim_write_projection_angle_trips(s, path, angle_deg, nfields, fields, 0);
+}
+int pion_host_sim_set_projection_angle_output(void *s, double angle_deg, int nfields, const pion_gpu_proj_field *fields)
+{
+  if (!s) return PION_GPU_EINVAL;
+  auto *c = static_cast<pion_host::sim_control_gpu *>(s);
+  try {
+    return io_result(c, c->set_projection_angle_output(angle_deg, nfields, fields));
   }
   catch (const std::exception &e) {
     g_last_exception = e.what();

@@ -109,6 +109,18 @@ class sim_control_gpu {
   // digits>.fits (the one file of a slab run: rank 0000); nfields 0 turns it off again.  The same refusals, made here.  Cadence and time steps are untouched
   int set_projection_output(int axis, int nfields, const pion_gpu_proj_field *fields);
   std::string projection_name(long step) const;
+  // A cylindrical (z,R) grid seen at angle_deg (0 < angle_deg < 90) to its axis (projection_io.cpp; the rule:
+  // pion_amd/csrc/dev_project_angle.h, after the reference's analysis/projection/angle_projection.cpp): write_fits'
+  // primary header plus pion_proj_angle, pion_proj_n_extra, pion_proj_pixdx, pion_proj_pixz0 and the per-field keys, and
+  // one double-precision IMAGE extension [NR][NZ + 2 n_extra] per field.  Projected on the device (backend entries
+  // project_angle_*), or -- a table without them, or trip_limit > 0 -- from a download by the same rule in a host loop
+  // (trip_limit 0: the rule's own limit).  EINVAL, a text and no file: what pion_gpu_project_angle refuses; one rank of
+  // several; a pixel whose ray loop reached the trip limit
+  int write_projection_angle(const char *path, double angle_deg, int nfields, const pion_gpu_proj_field *fields, int trip_limit = 0);
+  // from now on every regular output of output_data() is accompanied by <base>_proja_<rank, 4 digits>.<step, 8
+  // digits>.fits; nfields 0 turns it off again.  Independent of set_projection_output
+  int set_projection_angle_output(double angle_deg, int nfields, const pion_gpu_proj_field *fields);
+  std::string projection_angle_name(long step) const;
   // Ray-traced column densities (columns_io.cpp; pion_gpu_raytrace; the rules: pion_amd/csrc/dev_raytrace.h, after the reference's
   // raytracer_USC).  add_rt_source: Add_Source for one radiation source -- on the backend's handle (entry
   // add_rt_source), or, a table without it, kept here; pos_used (PION_MAX_DIM doubles, may be null): the cell vertex a
@@ -172,6 +184,8 @@ class sim_control_gpu {
   int filetype_ = 0;             // PION_HOST_FILE_*
   int proj_axis_ = 0;            // set_projection_output: the images that accompany a regular output (none: empty)
   std::vector<pion_gpu_proj_field> proj_fields_;
+  double proja_angle_ = 0.0;     // set_projection_angle_output, likewise
+  std::vector<pion_gpu_proj_field> proja_fields_;
   std::vector<pion_gpu_rt_source> rt_sources_, rt_moved_;   // add_rt_source: the sources as given, and at the positions used
   bool rt_on_backend_ = false;                   // they live on the backend's handle too
   bool column_output_ = false;                   // set_column_output
@@ -188,6 +202,7 @@ class sim_control_gpu {
   int relay_part(int rc, int axis, int nfields, const pion_gpu_proj_field *fields, const pion_gpu_proj_part &part,
                  std::vector<double> &img);
   int projection_refused(int axis, int nfields, const pion_gpu_proj_field *fields, const char *who);
+  int projection_angle_refused(double angle_deg, int nfields, const pion_gpu_proj_field *fields, const char *who);
   // snapshot_io.cpp: what the four writers share (the file itself: out_file.h)
   int path_refused(const char *who, const char *path);
   int snapshot_params(std::vector<snapshot_param> &out, long &slab_n);

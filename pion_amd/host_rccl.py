@@ -116,6 +116,15 @@ def load_host_library():
         h.pion_host_project_part_refused.restype = C.c_char_p
         h.pion_host_project_on_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, _dp, _dp]
         h.pion_host_project_part_on_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp, _dp]
+    if hasattr(h, "pion_host_sim_write_projection_angle"):   # (likewise)
+        h.pion_host_sim_write_projection_angle.argtypes = [C.c_void_p, C.c_char_p, C.c_double, C.c_int, C.c_void_p]
+        h.pion_host_sim_write_projection_angle_trips.argtypes = [C.c_void_p, C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.c_int]
+        h.pion_host_sim_set_projection_angle_output.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p]
+        h.pion_host_project_angle_count.argtypes = [C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_char_p)]
+        h.pion_host_project_angle_count.restype = C.c_long
+        h.pion_host_project_angle_on_host.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, _dp, _dp]
+        h.pion_host_project_angle_rule.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, _dp, _dp,
+                                                   C.POINTER(C.c_long), _dp, _dp]
     h.pion_host_comm_unique_id.argtypes = [C.c_void_p]
     h.pion_host_comm_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
     h.pion_host_comm_destroy.argtypes = [C.c_void_p]
@@ -275,6 +284,27 @@ class HostSim:
         rc = self.lib.pion_host_sim_set_projection_output(self.s, int(axis), len(fields), abi.proj_fields(fields))
         if rc != 0:
             raise ValueError("pion_host_sim_set_projection_output rc=%d: %s" % (rc, self.last_error()))
+
+    def write_projection_angle(self, path, angle_deg, fields, trip_limit=None):
+        """the FITS file of the images of a cylindrical (z,R) grid seen at angle_deg (0 < angle_deg < 90) to its axis
+        (pion_host_sim_write_projection_angle): [NR][NZ + 2 n_extra] per field, pion_proj_angle, pion_proj_n_extra,
+        pion_proj_pixdx and pion_proj_pixz0 in the header.  trip_limit: the host loop with that trip limit of the ray
+        loops (pion_host_sim_write_projection_angle_trips; tests of the refusal)"""
+        arr = abi.proj_fields(fields)
+        if trip_limit is None:
+            rc = self.lib.pion_host_sim_write_projection_angle(self.s, os.fsencode(path), float(angle_deg), len(fields), arr)
+        else:
+            rc = self.lib.pion_host_sim_write_projection_angle_trips(self.s, os.fsencode(path), float(angle_deg), len(fields),
+                                                                     arr, int(trip_limit))
+        if rc != 0:
+            raise RuntimeError("pion_host_sim_write_projection_angle rc=%d: %s" % (rc, self.last_error()))
+
+    def set_projection_angle_output(self, angle_deg, fields):
+        """from now on every regular output of time_int is accompanied by <base>_proja_<rank>.<step>.fits with these
+        images (pion_host_sim_set_projection_angle_output); no fields turns it off"""
+        rc = self.lib.pion_host_sim_set_projection_angle_output(self.s, float(angle_deg), len(fields), abi.proj_fields(fields))
+        if rc != 0:
+            raise ValueError("pion_host_sim_set_projection_angle_output rc=%d: %s" % (rc, self.last_error()))
 
     def add_rt_source(self, src):
         """pion_host_sim_add_rt_source: a radiation source (an abi.RtSource, or what abi.rt_source takes) for the

@@ -105,6 +105,11 @@ def load_library():
         lib.pion_gpu_project_part_count.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         lib.pion_gpu_project_part_count.restype = C.c_long
         lib.pion_gpu_project_part.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "pion_gpu_project_angle"):   # (likewise)
+        lib.pion_gpu_project_angle_count.argtypes = [C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_int)]
+        lib.pion_gpu_project_angle_count.restype = C.c_long
+        lib.pion_gpu_project_angle.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+        lib.pion_gpu_project_angle_status.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
     if hasattr(lib, "pion_gpu_raytrace"):   # (likewise)
         _cfgp, _srcp = C.POINTER(abi.PionGpuConfig), C.POINTER(abi.RtSource)
         lib.pion_gpu_add_rt_source.argtypes = [C.c_void_p, _srcp, C.POINTER(C.c_int), _dp]
@@ -159,11 +164,38 @@ EXPORTED_SYMBOLS = [
     "pion_gpu_fits_prim_count", "pion_gpu_unpack_fits", "pion_gpu_unpack_fits_status",
     "pion_gpu_cell_advance", "pion_gpu_project_count", "pion_gpu_project",
     "pion_gpu_project_part_count", "pion_gpu_project_part",
+    "pion_gpu_project_angle_count", "pion_gpu_project_angle", "pion_gpu_project_angle_status",
     "pion_gpu_add_rt_source", "pion_gpu_raytrace", "pion_gpu_rt_columns", "pion_gpu_rt_count",
     "pion_gpu_pack_columns", "pion_gpu_rt_plan", "pion_gpu_raytrace_host", "pion_gpu_rt_refused",
     "pion_gpu_add_rt_source_part", "pion_gpu_rt_chain", "pion_gpu_raytrace_part", "pion_gpu_raytrace_host_part",
     "pion_gpu_rt_plan_part", "pion_gpu_rt_part_refused",
 ]
+
+
+def project_angle_on_host(cfg, angle_deg, fields, A, trip_limit=None, info=None):
+    """pion_host_project_angle_on_host: the images [nfields][NR][NI] of a cylindrical (z,R) grid seen at angle_deg to
+    its axis, by the rule of pion_amd/csrc/dev_project_angle.h in a host loop over the whole array A ([nvar][ncell_all],
+    ghosts included).  Host only: needs no GPU.  trip_limit: the ray loops' trip limit instead of the rule's own
+    (pion_host_project_angle_rule); info (a dict) receives n_extra, ncapped, tan and inv_sin"""
+    from . import host_rccl
+    h = host_rccl.load_host_library()
+    arr = fields if isinstance(fields, C.Array) else abi.proj_fields(fields)
+    nf, ne, why = len(fields), C.c_int(-1), C.c_char_p()
+    n = h.pion_host_project_angle_count(C.byref(cfg), float(angle_deg), max(1, min(nf, abi.PROJ_MAX_FIELDS)), C.byref(ne),
+                                        C.byref(why))
+    if n < 0:
+        raise PionGpuError("project_angle_on_host", n, (why.value or b"").decode())
+    A = np.ascontiguousarray(A, dtype=np.float64).reshape(-1)
+    img = np.empty(n, dtype=np.float64)
+    ncapped, tn, invst = C.c_long(0), C.c_double(), C.c_double()
+    limit = 2 * (cfg.ng[0] + cfg.ng[1]) + 8 if trip_limit is None else int(trip_limit)
+    rc = h.pion_host_project_angle_rule(C.byref(cfg), float(angle_deg), limit, nf, arr, A.ctypes.data_as(_dp),
+                                        img.ctypes.data_as(_dp), C.byref(ncapped), C.byref(tn), C.byref(invst))
+    if rc != 0:
+        raise PionGpuError("project_angle_on_host", rc, "refused (a bad field, or a trip limit below 1)")
+    if info is not None:
+        info.update(n_extra=ne.value, ncapped=ncapped.value, tan=tn.value, inv_sin=invst.value)
+    return img[:n].reshape(nf, cfg.ng[1], -1)
 
 
 def rt_refused(cfg, src):
@@ -632,6 +664,43 @@ class GpuSim:
                                                  C.c_void_p(buf.data_ptr())), "project_part")
         self.synchronize()
         return buf.cpu().numpy().reshape(nf, -1, self.project_shape(axis)[1])
+
+    def project_angle_count(self, angle_deg, nfields):
+        """pion_gpu_project_angle_count: (doubles one project_angle() call writes, n_extra) -- [nfields][NR][NI] with
+        NI = NZ + 2 n_extra; raises for a grid or an angle the inclined projection refuses (no device call)"""
+        ne = C.c_int(-1)
+        n = self.lib.pion_gpu_project_angle_count(self.h, float(angle_deg), int(nfields), C.byref(ne))
+        if n < 0:
+            raise PionGpuError("project_angle_count", n, self._err())
+        return n, ne.value
+
+    def project_angle(self, angle_deg, fields, which=0, dbuf_ptr=None):
+        """pion_gpu_project_angle: the images of a cylindrical (z,R) grid seen at angle_deg (0 < angle_deg < 90) to its
+        axis, every pixel's ray walked from cell to cell (the reference's angle_projection.cpp).  fields: as project()
+        takes them.  With dbuf_ptr the images go into that device buffer, enqueued on the compute stream; without it
+        they are returned as an ndarray [nfields][NR][NI], and a pixel whose ray loop reached its trip limit raises."""
+        arr = fields if isinstance(fields, C.Array) else abi.proj_fields(fields)
+        nf = len(fields)
+        if dbuf_ptr is not None:
+            self._chk(self.lib.pion_gpu_project_angle(self.h, int(which), float(angle_deg), nf, arr, C.c_void_p(dbuf_ptr)),
+                      "project_angle")
+            return None
+        n = self.lib.pion_gpu_project_angle_count(self.h, float(angle_deg), max(1, min(nf, abi.PROJ_MAX_FIELDS)), None)
+        import torch
+        buf = torch.empty((max(n, 1),), dtype=torch.float64, device="cuda:%d" % torch.cuda.current_device())
+        self._chk(self.lib.pion_gpu_project_angle(self.h, int(which), float(angle_deg), nf, arr, C.c_void_p(buf.data_ptr())),
+                  "project_angle")
+        ncapped = self.project_angle_status()
+        if ncapped:
+            raise PionGpuError("project_angle", abi.E_INVAL, "%d pixel(s) reached the trip limit of their ray loop" % ncapped)
+        return buf.cpu().numpy().reshape(nf, self.cfg.ng[1], -1)
+
+    def project_angle_status(self):
+        """pion_gpu_project_angle_status: synchronises; the pixels since the last call whose ray loop reached its trip
+        limit (none is expected), cleared"""
+        n = C.c_long(-1)
+        self._chk(self.lib.pion_gpu_project_angle_status(self.h, C.byref(n)), "project_angle_status")
+        return n.value
 
     def project_shape(self, axis):
         """(NJ, NI) of an image along `axis`"""

@@ -46,15 +46,77 @@ def bound_state(g, cfg, torch):
     return st
 
 
+def cells_crossed(nz, nr, dx, zmin, deg, n_extra):
+    """cells every ray of the inclined image crosses, counted from the geometry (numpy, no walk): the columns the ray
+    spans inside the grid plus the rows it climbs on its incoming and on its outgoing branch -- every column or row
+    boundary crossed is one more cell.  (Equal to the count of the walk of tests/angle_projection_restate.py on 70 x 37
+    and 40 x 20 at 41 degrees and on 24 x 16 at 20 degrees: 269006, 45040 and 32684 cells.)"""
+    import numpy as np
+    tn = np.tan(np.deg2rad(deg))
+    zmax, rmax = zmin + nz * dx, nr * dx
+    pz = (zmin - n_extra * dx) + (np.arange(nz + 2 * n_extra) + 0.5) * dx
+    total = 0
+    for j in range(nr):
+        b = (j + 0.5) * dx
+        S = np.sqrt(rmax * rmax - b * b) / tn
+        lo, hi = np.maximum(zmin, pz - S), np.minimum(zmax, pz + S)
+        ok = hi > lo
+        R = lambda z: np.sqrt(b * b + (z - pz) ** 2 * tn * tn)
+        cols = np.ceil((hi - zmin) / dx) - np.floor((lo - zmin) / dx)
+        row = lambda z: np.minimum(np.floor(R(z) / dx), nr - 1)
+        rows_in = np.where(hi > pz, row(hi) - row(np.maximum(pz, lo)), 0)
+        rows_out = np.where(lo < pz, row(lo) - row(np.minimum(pz, hi)), 0)
+        total += int(np.where(ok, cols + rows_in + rows_out, 0).sum())
+    return total
+
+
+# issue cycles of one wavefront instruction (profiles/r02_valu_rates.txt): v_sqrt_f64 / v_rsq_f64 / v_rcp_f64 11.7; 1024
+# SIMDs at the 1.7 GHz the chip sustains under fp64 load
+TRANS_CYCLES, SIMD_CYCLES_PER_S = 11.7, 1024 * 1.7e9
+
+
+def angle_cost(a, torch, abi, lib):
+    """pion_gpu_project_angle on a cylindrical Euler + 1 tracer grid, three fields, per angle: median of --reps calls
+    after a warm-up.  Floor: 8 fp64 square roots and 3 divisions per cell crossed, each counted as ONE transcendental
+    instruction (the rsq / rcp seed; the Newton steps that make them IEEE are not counted), 64 cells per instruction"""
+    nz, nr = (int(x) for x in a.abel.split("x"))
+    cfg = abi.make_config(2, [nz, nr], abi.EQEUL, abi.FLUX_RSroe, ntracer=1, coord_sys=2, dx=1.0 / nr, strict_fp=0,
+                          bcs=["outflow", "outflow", "axisymmetric", "outflow"])
+    fields = [("coldens", 1, -1, 1.0, 0.0), ("emmeasure", 2, -1, 1.0, 0.0), ("windcol", 1, 5, 1.0, 0.0)]
+    out = {}
+    with lib.GpuSim(cfg, 0) as g:
+        st = bound_state(g, cfg, torch)
+        for deg in (float(x) for x in a.angle.split(",")):
+            n, n_extra = g.project_angle_count(deg, 3)
+            buf = torch.empty(n, dtype=torch.float64, device="cuda:0")
+            k = timed(lambda: g.project_angle(deg, fields, dbuf_ptr=buf.data_ptr()), g.synchronize, a.reps)
+            assert g.project_angle_status() == 0 and bool(torch.isfinite(buf).all())
+            cells = cells_crossed(nz, nr, cfg.dx, 0.0, deg, n_extra)
+            k.update(nz=nz, nr=nr, nfields=3, n_extra=n_extra, pixels=n // 3, cells_crossed=cells,
+                     cells_per_pixel=cells / (n // 3), cells_per_s=cells / (1e-3 * k["median_ms"]),
+                     floor_issue_ms=1e3 * (8 + 3) * TRANS_CYCLES * cells / 64 / SIMD_CYCLES_PER_S)
+            k["ratio_to_issue_floor"] = k["median_ms"] / k["floor_issue_ms"]
+            out["%g" % deg] = k
+            del buf
+        del st
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--abel", default="4096x2048")
     ap.add_argument("--box", type=int, default=512)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--angle", default="", help="degrees, comma separated: time the inclined projection of the --abel grid "
+                    "at these angles (profiles/projection_angle.json) instead of the perpendicular images")
     a = ap.parse_args()
     import torch
     from pion_amd import abi, lib
     res = {"gpu_lib": os.environ.get("PION_GPU_LIB", "in-tree"), "reps": a.reps}
+    if a.angle:
+        res["angle"] = angle_cost(a, torch, abi, lib)
+        print(json.dumps(res))
+        return
 
     nz, nr = (int(x) for x in a.abel.split("x"))
     cfg = abi.make_config(2, [nz, nr], abi.EQEUL, abi.FLUX_RSroe, ntracer=1, coord_sys=2, dx=1.0 / nr, strict_fp=0,
